@@ -7,6 +7,10 @@ driver's N > 1 launch, WORLD_SIZE set) the process is one rank of the job; start
 one control step (10 physics substeps + observation / reward / termination epilogue) of every
 environment of the batch; environments are sharded across ranks with no data-path collective ("weak" scaling: 4096 envs per GPU, BASELINE.json configs[1]).
 Prints ONE JSON line on rank 0.
+
+A plain run times the headline leg only.  `--full` adds every secondary measurement: the FP32 build, the pipelined sub-batch
+legs, flight_imitation, DMPO training, the oracle replay of sampled environments and the CPU baseline.  `--dump-outputs DIR`
+writes what the headline leg's last timed step left in the batch (rank 0's shard) as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -29,6 +33,23 @@ FLIGHT_BYTES_PER_ENV_STEP = {32: 1156.0, 64: 2*(43 + 42)*8.0 + (12 + 104 + 3)*4.
 FLIGHT_FLOP_PER_ENV_STEP = 0.534e6
 HBM_PEAK_GBS = 8000.0                  # MI355X_MICROARCH.md
 VALU_PEAK_TFLOPS = {32: 157.3, 64: 78.6}
+DUMP_CAP_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: one .npy per array; beyond DUMP_CAP_BYTES a fixed, seeded sample of the environments (rows), whose ids go
+    to env_ids.npy."""
+    import numpy as np
+    n = len(next(iter(arrays.values())))
+    row_bytes = sum(a.nbytes // n for a in arrays.values())
+    keep = min(n, DUMP_CAP_BYTES // row_bytes)
+    if keep < n:
+        ids = np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+        arrays = {k: a[ids] for k, a in arrays.items()}
+        arrays['env_ids'] = ids.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + '.npy'), a)
 
 
 def cpu_baseline(seconds=12.0):
@@ -113,6 +134,10 @@ def main():
     # chaotically like any single-precision MuJoCo (median environment inside 1e-4 after 100 physics steps, not every one);
     # its throughput is reported next to the headline as `f32_mode`, never as `value`.
     ap.add_argument('--precision', type=int, default=int(os.environ.get('FB_PRECISION', '64')), choices=[32, 64])
+    ap.add_argument('--full', action='store_true', help='run every secondary measurement after the headline leg (the --no-* options below '
+                    'leave single ones out); without it only the headline leg runs')
+    ap.add_argument('--dump-outputs', metavar='DIR', help='write the state and step results of the headline leg\'s last timed step (rank 0\'s '
+                    'shard; a fixed sample of its environments beyond %d MB) as DIR/<name>.npy' % (DUMP_CAP_BYTES >> 20))
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-f32-leg', action='store_true', help='skip the secondary FP32-build measurement')
     ap.add_argument('--no-split-leg', action='store_true', help='skip the secondary two-half-batches-on-two-streams measurement')
@@ -204,9 +229,10 @@ def main():
     id_base = rank*n_env                       # global id of this rank's environment 0: action streams and stagger groups are keyed by it
     P = max(1, args.preroll)
 
-    def run_leg(precision, extras=None):
+    def run_leg(precision, extras=None, outputs=None):
         """P staggering + W warm-up control steps untimed, then K timed control steps of the whole batch; returns (seconds, kernel ms
-        total, launches, finite).  extras (dict): filled with the end state of the sampled environments and the FB_WARN population."""
+        total, launches, finite).  extras (dict): filled with the end state of the sampled environments and the FB_WARN population.
+        outputs (dict): filled with the last timed step's action and what it left in the batch (state, observation, reward, ...)."""
         batch = engine.Batch(model_headline if precision == args.precision else model, n_env, device=local_rank, precision=precision)
         batch.set_reference(qp, qv, terminal_com_dist=float('inf'))
         batch.reset(stream=stream)
@@ -239,6 +265,10 @@ def main():
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             dt = float(t.item())
         finite = bool(np.isfinite(batch.get('QPOS')).all())
+        if outputs is not None:
+            outputs.update(action=action.cpu().numpy(), qpos=batch.get('QPOS'), qvel=batch.get('QVEL'), act=batch.get('ACT'),
+                           obs=batch.get('OBS'), reward=batch.get('REWARD'), discount=batch.get('DISCOUNT'),
+                           step_type=batch.get('STEP_TYPE').astype(np.float32))
         if extras is not None:
             sc1 = batch.get('STEP_COUNT').ravel().astype(np.int64)
             # an environment that was auto-reset inside the timed region spent ONE of its K launches on the reset (a forward pass,
@@ -422,18 +452,21 @@ def main():
         return dt, finite, sum(sizes)
 
     extras = {}
-    dt, kernel_ms, nlaunch, finite = run_leg(args.precision, extras)
-    split = None if args.no_split_leg else run_split_leg(args.precision)
+    outputs = {} if args.dump_outputs and rank == 0 else None
+    dt, kernel_ms, nlaunch, finite = run_leg(args.precision, extras, outputs)
+    if outputs is not None:
+        dump_outputs(args.dump_outputs, outputs)
+    split = run_split_leg(args.precision) if args.full and not args.no_split_leg else None
     # ... and on the 12-environments-per-CU build of the same kernel (engine.HIP_LIB_DENSE) as three sub-batches: slower than the
     # default build in lock-step, faster pipelined (more resident environments)
     split_dense = None
-    if not args.no_split_leg and args.precision == 64 and os.path.exists(engine.HIP_LIB_DENSE):
+    if args.full and not args.no_split_leg and args.precision == 64 and os.path.exists(engine.HIP_LIB_DENSE):
         split_dense = run_split_leg(64, parts=3, dense=True)
     f32 = None
-    if args.precision == 64 and not args.no_f32_leg:
+    if args.full and args.precision == 64 and not args.no_f32_leg:
         f32 = run_leg(32)
     flight = dmpo = None
-    if not args.no_secondary_configs:
+    if args.full and not args.no_secondary_configs:
         if not args.no_flight_leg:
             flight = {f'f{p}': run_flight_leg(p, max(10, args.steps), max(5, args.warmup)) for p in ((64, 32) if args.precision == 64 else (32,))}
         if rank == 0:
@@ -455,7 +488,7 @@ def main():
                     pass
         barrier()
     parity = None
-    if rank == 0 and args.precision == 64 and not args.no_parity_sample:
+    if args.full and rank == 0 and args.precision == 64 and not args.no_parity_sample:
         parity = parity_sample(extras)
     traffic = None
     tr_path = os.path.join(ROOT, 'profiles', f'pmc_traffic_f{args.precision}.json')
@@ -538,7 +571,7 @@ def main():
                        ('configs[4]: walk_imitation DMPO, %d envs sharded across %d GPUs (%d per GPU), gradient all-reduce over %s, SPI 15'
                         % (args.dmpo_envs*world, world, args.dmpo_envs, 'RCCL / xGMI' if backend == 'nccl' else 'gloo (one-GPU functional run)'))
             out['dmpo_mode'] = {'config': cfg_name, **dmpo}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out['cpu_baseline'] = cpu_baseline()
         print(json.dumps(out))
     if world > 1:

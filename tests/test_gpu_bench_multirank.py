@@ -20,7 +20,7 @@ def test_bench_two_ranks_on_one_gpu():
     env = dict(os.environ, FB_BENCH_DEVICE='0', FB_BENCH_BACKEND='gloo', MASTER_ADDR='127.0.0.1')
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr', '127.0.0.1',
            '--master-port', str(port), os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '4', '--warmup', '2',
-           '--preroll', '235', '--envs-per-gpu', '256', '--no-f32-leg', '--no-cpu-baseline', '--no-secondary-configs']
+           '--preroll', '235', '--envs-per-gpu', '256', '--full', '--no-f32-leg', '--no-cpu-baseline', '--no-secondary-configs']
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith('{')]
@@ -66,7 +66,7 @@ def test_rccl_dry_run_reports_unexercised_on_one_gpu():
     import torch
     env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'FB_BENCH_DEVICE', 'FB_BENCH_BACKEND')}
     cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--rccl-dry-run', '--steps', '3', '--warmup', '1', '--preroll', '0', '--envs-per-gpu', '256',
-           '--no-f32-leg', '--no-split-leg', '--no-cpu-baseline', '--no-secondary-configs']
+           '--full', '--no-f32-leg', '--no-split-leg', '--no-cpu-baseline', '--no-secondary-configs']
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     out = json.loads([l for l in r.stdout.splitlines() if l.startswith('{')][-1])
@@ -85,7 +85,7 @@ def test_dmpo_leg_runs_under_several_ranks():
     and reports whole-job env- and learner-steps/s.  Two ranks on this one-GPU box (gloo stands in for RCCL: --rccl-dry-run)."""
     env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'FB_BENCH_DEVICE', 'FB_BENCH_BACKEND')}
     cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--rccl-dry-run', '--steps', '2', '--warmup', '1', '--preroll', '0', '--envs-per-gpu', '128',
-           '--no-f32-leg', '--no-split-leg', '--no-cpu-baseline', '--no-parity-sample', '--no-flight-leg',
+           '--full', '--no-f32-leg', '--no-split-leg', '--no-cpu-baseline', '--no-parity-sample', '--no-flight-leg',
            '--dmpo-envs', '256', '--dmpo-iters', '4', '--dmpo-warmup', '6', '--dmpo-min-replay', '512', '--dmpo-replay-capacity', '50000']
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]

@@ -177,9 +177,9 @@ def test_fixed_tendons_have_no_limits(walk_arrays):
     for key in ('tendon_limited', 'tendon_range'):
         if key in walk_arrays:
             assert not np.any(walk_arrays[key])
-    import os
-    xml = os.environ.get('FLYBODY_XML', '/root/reference/flybody/fruitfly/assets/fruitfly.xml')
-    if os.path.exists(xml):
+    from flybody_amd import model_zoo
+    xml = model_zoo.find_xml()
+    if xml is not None:
         import xml.etree.ElementTree as ET
         for t in ET.parse(xml).getroot().find('tendon'):
             assert 'range' not in t.attrib and t.attrib.get('limited', 'false') == 'false', t.attrib
