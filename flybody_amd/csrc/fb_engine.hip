@@ -22,6 +22,7 @@ extern "C" { long long fb_stats[64]; }
 
 #include "../../include/flybody_engine.h"
 #include "fb_step.hpp"
+#include "fb_ik.hpp"
 
 static thread_local std::string g_err;
 static int fail(const std::string& s) { g_err = s; return -1; }
@@ -888,6 +889,8 @@ struct fb_batch {
   bool have_ref = false, have_wbpg = false;
   hipEvent_t ev0 = nullptr, ev1 = nullptr; int timed_launches = 0; bool timing = false;
   std::vector<hipEvent_t> lev;        // per-launch event pairs of the timed region (fb_batch_timing_launches), created on first use
+  double* ik_err = nullptr; int* ik_steps = nullptr;      // fb_batch_ik results (FB_IK_ERR / FB_IK_STEPS), allocated on the first call
+  void* ik_buf = nullptr; size_t ik_buf_bytes = 0;        // ... its tables and targets (grown as needed)
 };
 
 template <typename real, typename T, typename P>
@@ -1109,7 +1112,7 @@ extern "C" void fb_batch_destroy(fb_batch* b) {
   if (!b) return;
   (void)hipSetDevice(b->device);
   for (void* p : b->allocs) (void)hipFree(p);
-  void* frees_[] = {b->rarena, b->iarena, b->obs, b->reward, b->discount, b->step_type, b->d_ids, b->sched, b->cost, b->order, b->ref_qpos, b->ref_qvel, b->dM, b->tick, b->done, b->sched_err, b->park, b->probe_word, b->torder};
+  void* frees_[] = {b->rarena, b->iarena, b->obs, b->reward, b->discount, b->step_type, b->d_ids, b->sched, b->cost, b->order, b->ref_qpos, b->ref_qvel, b->dM, b->tick, b->done, b->sched_err, b->park, b->probe_word, b->torder, b->ik_err, b->ik_steps, b->ik_buf};
   for (void* p : frees_) (void)hipFree(p);
 
   if (b->ev0) (void)hipEventDestroy(b->ev0);
@@ -1405,8 +1408,87 @@ extern "C" int fb_batch_stage(fb_batch* b, int stage_word, const float* action, 
   return launch(b, MODE_STAGE, action, nullptr, b->n_env, stage_word, stream);
 }
 
+// ------------------------------------------------------------------ inverse kinematics
+// Multi-site IK, one frame per environment (fb_ik.hpp: k_ik).  Not a control step: it does not go through launch(), is not a timed launch
+// and changes nothing of the environment's state but qpos and the position-stage outputs computed from it.
+extern "C" int fb_batch_ik(fb_batch* b, const fb_ik_config* cfg, const double* target_xpos, void* stream) {
+  if (!b || !cfg || !target_xpos) return fail("fb_batch_ik: null argument");
+  if (b->precision != 64) return fail("fb_batch_ik: inverse kinematics needs an FP64 batch (precision 64)");
+  const fb_model* m = b->m;
+  const int ns = cfg->n_site, nj = cfg->n_joint, n = b->n_env;
+  if (ns < 1 || !cfg->site_ids || !cfg->include) return fail("fb_batch_ik: at least one site (and its include mask) is required");
+  if (nj < 0 || (nj > 0 && !cfg->joint_ids)) return fail("fb_batch_ik: bad joint list");
+  if (!std::isfinite(cfg->reg_strength) || !std::isfinite(cfg->lr) || !std::isfinite(cfg->beta) || !std::isfinite(cfg->progress_threshold))
+    return fail("fb_batch_ik: hyper-parameters must be finite");
+  if (cfg->max_steps < 1) return fail("fb_batch_ik: max_steps must be >= 1");
+  if (std::max({7*m->nbody + 10*m->njnt, 6*m->nv + 10*m->nbody, 7*m->nv + 6*m->nbody}) > FB_IK_POOL) return fail("fb_batch_ik: model exceeds the IK LDS pool (FB_IK_POOL)");
+  FB_GUARD_BEGIN
+  const int *sbody = m->i("site_bodyid"), *jt = m->i("jnt_type"), *jda = m->i("jnt_dofadr"), *jqa = m->i("jnt_qposadr");
+  std::vector<char> seen(std::max(m->nsite, m->njnt), 0);
+  for (int k = 0; k < ns; k++) {
+    const int s = cfg->site_ids[k];
+    if (s < 0 || s >= m->nsite) return fail("fb_batch_ik: site id out of range");
+    if (seen[s]) return fail("fb_batch_ik: duplicate site id");
+    seen[s] = 1;
+  }
+  for (int k = 0; k < 3*ns; k++) if (cfg->include[k] != 0 && cfg->include[k] != 1) return fail("fb_batch_ik: include mask entries must be 0 or 1");
+  std::fill(seen.begin(), seen.end(), 0);
+  // joints -> dofs (the reference's dof_jntid row indexer), hinge dofs carry their qpos address (regularisation)
+  std::vector<int> dof, dof_hq;
+  for (int k = 0; k < nj; k++) {
+    const int j = cfg->joint_ids[k];
+    if (j < 0 || j >= m->njnt) return fail("fb_batch_ik: joint id out of range");
+    if (seen[j]) return fail("fb_batch_ik: duplicate joint id");
+    seen[j] = 1;
+    const int nd = jt[j] == JNT_FREE ? 6 : (jt[j] == JNT_BALL ? 3 : 1);
+    for (int d = 0; d < nd; d++) { dof.push_back(jda[j] + d); dof_hq.push_back(jt[j] == JNT_HINGE ? jqa[j] : -1); }
+  }
+  if ((int)dof.size() > 2*FB_WAVE) return fail("fb_batch_ik: more than 128 dofs");
+  for (size_t k = 0; k < (size_t)n*3*ns; k++) if (std::isnan(target_xpos[k])) return fail("fb_batch_ik: target_xpos holds NaN");
+  // the sites of every body (the kernel sums a body's point forces on one lane, in site-list order)
+  std::vector<int> boff(m->nbody + 1, 0), bsite(ns);
+  for (int k = 0; k < ns; k++) boff[sbody[cfg->site_ids[k]] + 1]++;
+  for (int bb = 0; bb < m->nbody; bb++) boff[bb + 1] += boff[bb];
+  { std::vector<int> fill(boff.begin(), boff.end() - 1); for (int k = 0; k < ns; k++) bsite[fill[sbody[cfg->site_ids[k]]]++] = k; }
+  // one device buffer: int tables, then the targets
+  const size_t nd = dof.size();
+  std::vector<int> it;
+  auto put = [&](const int* p, size_t c) { size_t o = it.size(); it.insert(it.end(), p, p + c); return o; };
+  const size_t o_site = put(cfg->site_ids, ns), o_boff = put(boff.data(), boff.size()), o_bsite = put(bsite.data(), ns),
+               o_inc = put(cfg->include, 3*(size_t)ns), o_dof = put(dof.data(), nd), o_hq = put(dof_hq.data(), nd);
+  const size_t tgt_off = ((it.size()*sizeof(int) + 255) & ~(size_t)255), bytes = tgt_off + (size_t)n*3*ns*sizeof(double);
+  HIPCHK(hipSetDevice(b->device));
+  HIPCHK(hipDeviceSynchronize());                      // (a previous IK launch may still read the buffer)
+  if (!b->ik_err) {
+    HIPCHK(hipMalloc((void**)&b->ik_err, (size_t)n*2*sizeof(double))); HIPCHK(hipMemset(b->ik_err, 0, (size_t)n*2*sizeof(double)));
+    HIPCHK(hipMalloc((void**)&b->ik_steps, (size_t)n*2*sizeof(int))); HIPCHK(hipMemset(b->ik_steps, 0, (size_t)n*2*sizeof(int)));
+  }
+  if (b->ik_buf_bytes < bytes) {
+    (void)hipFree(b->ik_buf); b->ik_buf = nullptr; b->ik_buf_bytes = 0;
+    HIPCHK(hipMalloc(&b->ik_buf, bytes)); b->ik_buf_bytes = bytes;
+  }
+  HIPCHK(hipMemcpy(b->ik_buf, it.data(), it.size()*sizeof(int), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy((char*)b->ik_buf + tgt_off, target_xpos, (size_t)n*3*ns*sizeof(double), hipMemcpyHostToDevice));
+  // the device copy of the model struct follows the host copy (as in launch())
+  if (!b->dM) { HIPCHK(hipMalloc(&b->dM, sizeof(b->M64))); memset(&b->M64_dev, 0xff, sizeof(b->M64)); }
+  if (memcmp(&b->M64, &b->M64_dev, sizeof(b->M64)) != 0) {
+    HIPCHK(hipMemcpy(b->dM, &b->M64, sizeof(b->M64), hipMemcpyHostToDevice));
+    memcpy(&b->M64_dev, &b->M64, sizeof(b->M64));
+  }
+  const int* ib = (const int*)b->ik_buf;
+  IKArgs<double> A;
+  A.site = ib + o_site; A.bsite_off = ib + o_boff; A.bsite = ib + o_bsite; A.include = ib + o_inc; A.dof = ib + o_dof; A.dof_hq = ib + o_hq;
+  A.target = (const double*)((const char*)b->ik_buf + tgt_off); A.err = b->ik_err; A.steps = b->ik_steps;
+  A.n_site = ns; A.n_dof = (int)nd; A.max_steps = cfg->max_steps; A.n_env = n;
+  A.reg = cfg->reg_strength; A.lr = cfg->lr; A.beta = cfg->beta; A.thr = cfg->progress_threshold;
+  hipLaunchKernelGGL((k_ik<double>), dim3(n), dim3(FB_WAVE), 0, (hipStream_t)stream, (const DevModel<double>*)b->dM, (double*)b->rarena, b->iarena, A);
+  HIPCHK(hipGetLastError());
+  return 0;
+  FB_GUARD_END
+}
+
 // ------------------------------------------------------------------ field access
-struct FieldDesc { int kind; /*0 real arena, 1 int arena, 2 f32 array, 3 i32 array*/ size_t off, width; void* base; };
+struct FieldDesc { int kind; /*0 real arena, 1 int arena, 2 f32 array, 3 i32 array, 4 f64 array*/ size_t off, width; void* base; };
 
 static int field_desc(fb_batch* b, int field, FieldDesc* f) {
   const fb_model* m = b->m; const WSOff& o = b->off;
@@ -1445,6 +1527,9 @@ static int field_desc(fb_batch* b, int field, FieldDesc* f) {
     case FB_SIZE_STATS: *f = {1, o.istate + IS_MAX_NCON, 4, nullptr}; break;
     case FB_STEP_TICKS: *f = {3, 0, 1, b->cost}; break;
     case FB_LAUNCH_ORDER: *f = {3, 0, 1, b->order}; break;
+    case FB_SITE_XPOS: *f = {0, o.sxpos, (size_t)3*m->nsite, nullptr}; break;
+    case FB_IK_ERR: *f = {4, 0, 2, b->ik_err}; break;
+    case FB_IK_STEPS: *f = {3, 0, 2, b->ik_steps}; break;
     default: return fail("unknown field");
   }
   return 0;
@@ -1488,8 +1573,9 @@ extern "C" int fb_batch_get(fb_batch* b, int field, void* dst, size_t bytes) {
     if (bytes != (size_t)n*f.width*sizeof(int)) return fail("fb_batch_get: size mismatch");
     HIPCHK(hipMemcpy2D(dst, f.width*4, (char*)b->iarena + f.off*4, (size_t)b->off.nint*4, f.width*4, n, hipMemcpyDeviceToHost));
   } else {
-    if (!f.base) return fail("fb_batch_get: field not allocated yet (set a reference first)");
-    if (bytes != (size_t)n*f.width*4) return fail("fb_batch_get: size mismatch");
+    if (!f.base) return fail(field == FB_IK_ERR || field == FB_IK_STEPS ? "fb_batch_get: field not allocated yet (run fb_batch_ik first)"
+                                                                         : "fb_batch_get: field not allocated yet (set a reference first)");
+    if (bytes != (size_t)n*f.width*(f.kind == 4 ? 8 : 4)) return fail("fb_batch_get: size mismatch");
     HIPCHK(hipMemcpy(dst, f.base, bytes, hipMemcpyDeviceToHost));
   }
   return 0;

@@ -29,8 +29,9 @@ ASSETS = os.path.join(_HERE, 'assets')
 FIELDS = dict(QPOS=0, QVEL=1, ACT=2, CTRL=3, QACC=4, XPOS=5, XQUAT=6, SENSORDATA=7, OBS=8, REWARD=9,
               DISCOUNT=10, STEP_TYPE=11, NCON=12, NEFC=13, SOLVER_NITER=14, QFRC_BIAS=15, QFRC_PASSIVE=16,
               QACC_SMOOTH=17, QM=18, CONTACT=19, EFC_FORCE=20, QFRC_ACTUATOR=21, QFRC_CONSTRAINT=22,
-              STEP_COUNT=23, SUBTREE_COM=24, PROF=25, REWARD_FACTORS=26, GEOM_XPOS=27, GEOM_XMAT=28, CVEL=29, STEP_TICKS=30, LAUNCH_ORDER=31, WARN=32, WARN_EVER=33, SIZE_STATS=34)
-_INT_FIELDS = {'STEP_TYPE', 'NCON', 'NEFC', 'SOLVER_NITER', 'STEP_COUNT', 'PROF', 'STEP_TICKS', 'LAUNCH_ORDER', 'WARN', 'WARN_EVER', 'SIZE_STATS'}
+              STEP_COUNT=23, SUBTREE_COM=24, PROF=25, REWARD_FACTORS=26, GEOM_XPOS=27, GEOM_XMAT=28, CVEL=29, STEP_TICKS=30, LAUNCH_ORDER=31, WARN=32, WARN_EVER=33, SIZE_STATS=34,
+              SITE_XPOS=35, IK_ERR=36, IK_STEPS=37)
+_INT_FIELDS = {'STEP_TYPE', 'NCON', 'NEFC', 'SOLVER_NITER', 'STEP_COUNT', 'PROF', 'STEP_TICKS', 'LAUNCH_ORDER', 'WARN', 'WARN_EVER', 'SIZE_STATS', 'IK_STEPS'}
 # bits of WARN / WARN_EVER (include/flybody_engine.h): the caps MuJoCo reports as nconmax / njmax warnings, and iteration limits
 WARN_BITS = dict(CONTACT_CAP=1, EFC_CAP=2, SOLVER_MAXITER=4, CCD_MAXITER=8, SCHED_WAIT=16, SOLVER_FALLBACK=32)
 _F32_FIELDS = {'OBS', 'REWARD', 'DISCOUNT'}
@@ -107,6 +108,8 @@ def load_library(lib_path: Optional[str] = None) -> C.CDLL:
     L.fb_batch_timing_end.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_int)]
     if hasattr(L, 'fb_batch_timing_launches'):
         L.fb_batch_timing_launches.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+    if hasattr(L, 'fb_batch_ik'):           # (A/B builds of older sources lack it)
+        L.fb_batch_ik.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     _libs[path] = L
     return L
 
@@ -132,6 +135,12 @@ def source_hash() -> str:
 def _check(L, rc):
     if rc != 0:
         raise EngineError(L.fb_last_error().decode())
+
+
+class _IKConfig(C.Structure):
+    """fb_ik_config (include/flybody_engine.h)."""
+    _fields_ = [('n_site', C.c_int32), ('n_joint', C.c_int32), ('site_ids', C.c_void_p), ('joint_ids', C.c_void_p), ('include', C.c_void_p),
+                ('reg_strength', C.c_double), ('lr', C.c_double), ('beta', C.c_double), ('progress_threshold', C.c_double), ('max_steps', C.c_int32)]
 
 
 class Model:
@@ -259,6 +268,20 @@ class Batch:
         """Profiling: one stage of a control step for every environment (fb_batch_stage; sequence: engine.stage_sequence)."""
         _check(self.L, self.L.fb_batch_stage(self.h, int(stage_word), C.c_void_p(action_dev_ptr) if action_dev_ptr else None, stream))
 
+    def ik(self, site_ids, joint_ids, target_xpos, include=None, reg_strength=0.0, lr=0.01, beta=0.99, progress_threshold=0.01,
+           max_steps=20_000, stream=None):
+        """Multi-site inverse kinematics for every environment (fb_batch_ik): environment e fits target_xpos[e] ([n_env][n_site][3])
+        from its QPOS and leaves the result there; per-environment results in IK_ERR (err_norm, err_norm_first_term) and IK_STEPS
+        (steps, success).  include: [3 n_site] 0 / 1 mask of the components that enter the objective (None: all).  Asynchronous."""
+        s = np.ascontiguousarray(site_ids, np.int32); j = np.ascontiguousarray(joint_ids, np.int32)
+        inc = np.ones(3*len(s), np.int32) if include is None else np.ascontiguousarray(include, np.int32)
+        t = np.ascontiguousarray(target_xpos, np.float64)
+        if inc.shape != (3*len(s),) or t.shape != (self.n_env, len(s), 3):
+            raise ValueError(f'include must be [{3*len(s)}] and target_xpos [{self.n_env}, {len(s)}, 3]')
+        cfg = _IKConfig(len(s), len(j), s.ctypes.data, j.ctypes.data if len(j) else None, inc.ctypes.data, float(reg_strength), float(lr),
+                        float(beta), float(progress_threshold), int(max_steps))
+        _check(self.L, self.L.fb_batch_ik(self.h, C.byref(cfg), t.ctypes.data, stream))
+
     def synchronize(self, stream=None):
         _check(self.L, self.L.fb_batch_synchronize(self.h, stream))
 
@@ -282,7 +305,8 @@ class Batch:
                     QFRC_PASSIVE=m.dim('nv'), QACC_SMOOTH=m.dim('nv'), QM=m.dim('nM'), CONTACT=MAXCON*8,
                     EFC_FORCE=MAXEFC, QFRC_ACTUATOR=m.dim('nv'), QFRC_CONSTRAINT=m.dim('nv'), STEP_COUNT=1,
                     SUBTREE_COM=3, PROF=112, REWARD_FACTORS=5, GEOM_XPOS=3*m.dim('ngeom'),
-                    GEOM_XMAT=9*m.dim('ngeom'), CVEL=6*m.dim('nbody'), STEP_TICKS=1, LAUNCH_ORDER=1, WARN=1, WARN_EVER=1, SIZE_STATS=4)[name]
+                    GEOM_XMAT=9*m.dim('ngeom'), CVEL=6*m.dim('nbody'), STEP_TICKS=1, LAUNCH_ORDER=1, WARN=1, WARN_EVER=1, SIZE_STATS=4,
+                    SITE_XPOS=3*m.dim('nsite'), IK_ERR=2, IK_STEPS=2)[name]
 
     def get(self, name: str) -> np.ndarray:
         w = self._width(name)

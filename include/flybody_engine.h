@@ -70,6 +70,9 @@ enum {
                          set-up since the batch was created, i.e. every substep AND every forward evaluation (fb_batch_forward, the
                          forward pass of a reset); not cleared by resets; fb_batch_set(FB_SIZE_STATS, zeros) clears.  Against FB_MAXCON / FB_MAXEFC and
                          MuJoCo's nconmax 100 / njmax 300 (fruitfly.xml:6) this says how close a run came to the caps. */
+  FB_SITE_XPOS = 35,  /* [n_env][nsite][3] site positions (position stage) */
+  FB_IK_ERR = 36,     /* [n_env][2] FP64: err_norm, err_norm_first_term of the last fb_batch_ik (read-only; allocated by the first call) */
+  FB_IK_STEPS = 37,   /* [n_env][2] int32: steps, success of the last fb_batch_ik (read-only; allocated by the first call) */
   FB_NFIELD
 };
 
@@ -210,6 +213,24 @@ int fb_batch_forget_stream(fb_batch* b, void* stream);
  * number of ranks its batch is sharded over (the reference steps one independent environment per actor process,
  * agents/ray_distributed_dmpo.py:232).  dist 0: N(0,1) clipped to [-1, 1]; dist 1: U(-1, 1).  Asynchronous on `stream`. */
 int fb_random_actions(float* action, const int32_t* env_ids, int n_env, int nact, uint64_t seed, int step, int env_id_base, int dist, void* stream);
+
+/* Multi-site inverse kinematics, the reference's qpos_from_site_xpos (flybody/inverse_kinematics.py) for every environment at once:
+ * momentum gradient descent of |site_xpos - target|^2 (over the included components) + reg_strength |hinge qpos|^2 over the dofs of
+ * the listed joints, up to max_steps iterations, stopping a frame when lr |update| / err < progress_threshold (checked every 100 steps).
+ * Environment e fits target_xpos[e] (HOST pointer, FP64 [n_env][n_site][3]) starting from its FB_QPOS, and leaves the result there (the
+ * reference's inplace=True); the position-stage outputs (FB_XPOS, FB_SITE_XPOS, ...) are left consistent with it, nothing else of the
+ * environment changes.  Results per environment in FB_IK_ERR / FB_IK_STEPS.  FP64 batches only.  Validates every argument (ids in range
+ * and unique, n_site >= 1, finite hyper-parameters, max_steps >= 1, no NaN target, include entries 0 / 1).  Asynchronous on `stream`
+ * after the (blocking) upload of the targets. */
+typedef struct fb_ik_config {
+  int32_t n_site, n_joint;
+  const int32_t* site_ids;        /* [n_site] model site ids */
+  const int32_t* joint_ids;       /* [n_joint] model joint ids (expanded to their dofs) */
+  const int32_t* include;         /* [3 n_site] 1: the component of target_xpos enters the objective (the reference's include_inds), 0: ignored */
+  double reg_strength, lr, beta, progress_threshold;
+  int32_t max_steps;
+} fb_ik_config;
+int fb_batch_ik(fb_batch* b, const fb_ik_config* cfg, const double* target_xpos, void* stream);
 
 const char* fb_last_error(void);
 
