@@ -23,6 +23,7 @@ extern "C" { long long fb_stats[64]; }
 #include "../../include/flybody_engine.h"
 #include "fb_step.hpp"
 #include "fb_ik.hpp"
+#include "fb_inverse.hpp"
 
 static thread_local std::string g_err;
 static int fail(const std::string& s) { g_err = s; return -1; }
@@ -891,6 +892,7 @@ struct fb_batch {
   std::vector<hipEvent_t> lev;        // per-launch event pairs of the timed region (fb_batch_timing_launches), created on first use
   double* ik_err = nullptr; int* ik_steps = nullptr;      // fb_batch_ik results (FB_IK_ERR / FB_IK_STEPS), allocated on the first call
   void* ik_buf = nullptr; size_t ik_buf_bytes = 0;        // ... its tables and targets (grown as needed)
+  double* inv_qfrc = nullptr; double* inv_cforce = nullptr;      // fb_batch_inverse results (FB_QFRC_INVERSE / FB_CONTACT_FORCE), allocated on the first call
 };
 
 template <typename real, typename T, typename P>
@@ -1112,7 +1114,7 @@ extern "C" void fb_batch_destroy(fb_batch* b) {
   if (!b) return;
   (void)hipSetDevice(b->device);
   for (void* p : b->allocs) (void)hipFree(p);
-  void* frees_[] = {b->rarena, b->iarena, b->obs, b->reward, b->discount, b->step_type, b->d_ids, b->sched, b->cost, b->order, b->ref_qpos, b->ref_qvel, b->dM, b->tick, b->done, b->sched_err, b->park, b->probe_word, b->torder, b->ik_err, b->ik_steps, b->ik_buf};
+  void* frees_[] = {b->rarena, b->iarena, b->obs, b->reward, b->discount, b->step_type, b->d_ids, b->sched, b->cost, b->order, b->ref_qpos, b->ref_qvel, b->dM, b->tick, b->done, b->sched_err, b->park, b->probe_word, b->torder, b->ik_err, b->ik_steps, b->ik_buf, b->inv_qfrc, b->inv_cforce};
   for (void* p : frees_) (void)hipFree(p);
 
   if (b->ev0) (void)hipEventDestroy(b->ev0);
@@ -1487,6 +1489,44 @@ extern "C" int fb_batch_ik(fb_batch* b, const fb_ik_config* cfg, const double* t
   FB_GUARD_END
 }
 
+// ------------------------------------------------------------------ inverse dynamics
+// mj_inverse, one frame per environment (fb_inverse.hpp: k_inverse).  Like fb_batch_ik it does not go through launch() and is not a
+// timed launch; it reads FB_QPOS / FB_QVEL / FB_QACC and changes nothing a later control step reads (see fb_inverse.hpp).
+extern "C" int fb_batch_inverse(fb_batch* b, int flags, void* stream) {
+  if (!b) return fail("fb_batch_inverse: null batch");
+  if (b->precision != 64) return fail("fb_batch_inverse: inverse dynamics needs an FP64 batch (precision 64)");
+  if (flags & ~FB_INV_DISCRETE) return fail("fb_batch_inverse: unknown flags");
+  FB_GUARD_BEGIN
+  const int n = b->n_env, nv = b->m->nv;
+  HIPCHK(hipSetDevice(b->device));
+  HIPCHK(hipDeviceSynchronize());                      // (the qacc check below reads what earlier launches wrote)
+  {
+    std::vector<double> qacc((size_t)n*nv);
+    HIPCHK(hipMemcpy2D(qacc.data(), (size_t)nv*8, (char*)b->rarena + (size_t)b->off.qacc*8, (size_t)b->off.nreal*8, (size_t)nv*8, n, hipMemcpyDeviceToHost));
+    for (size_t k = 0; k < qacc.size(); k++)
+      if (!std::isfinite(qacc[k])) return fail("fb_batch_inverse: FB_QACC of environment " + std::to_string(k/nv) + " is not finite");
+  }
+  if (!b->inv_qfrc) {
+    HIPCHK(hipMalloc((void**)&b->inv_qfrc, (size_t)n*nv*sizeof(double))); HIPCHK(hipMemset(b->inv_qfrc, 0, (size_t)n*nv*sizeof(double)));
+    HIPCHK(hipMalloc((void**)&b->inv_cforce, (size_t)n*3*FB_MAXCON_*sizeof(double))); HIPCHK(hipMemset(b->inv_cforce, 0, (size_t)n*3*FB_MAXCON_*sizeof(double)));
+  }
+  // the device copy of the model struct follows the host copy (as in launch())
+  if (!b->dM) { HIPCHK(hipMalloc(&b->dM, sizeof(b->M64))); memset(&b->M64_dev, 0xff, sizeof(b->M64)); }
+  if (memcmp(&b->M64, &b->M64_dev, sizeof(b->M64)) != 0) {
+    HIPCHK(hipMemcpy(b->dM, &b->M64, sizeof(b->M64), hipMemcpyHostToDevice));
+    memcpy(&b->M64_dev, &b->M64, sizeof(b->M64));
+  }
+  InvArgs<double> A;
+  A.qfrc_inverse = b->inv_qfrc; A.contact_force = b->inv_cforce; A.n_env = n;
+  A.flags = (flags & FB_INV_DISCRETE) ? FB_INV_FLAG_DISCRETE : 0;
+  constexpr int EPB = LdsCfg<double>::EPB;
+  hipLaunchKernelGGL((k_inverse<double>), dim3((n + EPB - 1)/EPB), dim3(FB_WAVE*EPB), 0, (hipStream_t)stream, (const DevModel<double>*)b->dM,
+                     (double*)b->rarena, b->iarena, A);
+  HIPCHK(hipGetLastError());
+  return 0;
+  FB_GUARD_END
+}
+
 // ------------------------------------------------------------------ field access
 struct FieldDesc { int kind; /*0 real arena, 1 int arena, 2 f32 array, 3 i32 array, 4 f64 array*/ size_t off, width; void* base; };
 
@@ -1530,6 +1570,8 @@ static int field_desc(fb_batch* b, int field, FieldDesc* f) {
     case FB_SITE_XPOS: *f = {0, o.sxpos, (size_t)3*m->nsite, nullptr}; break;
     case FB_IK_ERR: *f = {4, 0, 2, b->ik_err}; break;
     case FB_IK_STEPS: *f = {3, 0, 2, b->ik_steps}; break;
+    case FB_QFRC_INVERSE: *f = {4, 0, (size_t)m->nv, b->inv_qfrc}; break;
+    case FB_CONTACT_FORCE: *f = {4, 0, (size_t)3*FB_MAXCON_, b->inv_cforce}; break;
     default: return fail("unknown field");
   }
   return 0;
@@ -1574,6 +1616,7 @@ extern "C" int fb_batch_get(fb_batch* b, int field, void* dst, size_t bytes) {
     HIPCHK(hipMemcpy2D(dst, f.width*4, (char*)b->iarena + f.off*4, (size_t)b->off.nint*4, f.width*4, n, hipMemcpyDeviceToHost));
   } else {
     if (!f.base) return fail(field == FB_IK_ERR || field == FB_IK_STEPS ? "fb_batch_get: field not allocated yet (run fb_batch_ik first)"
+                             : field == FB_QFRC_INVERSE || field == FB_CONTACT_FORCE ? "fb_batch_get: field not allocated yet (run fb_batch_inverse first)"
                                                                          : "fb_batch_get: field not allocated yet (set a reference first)");
     if (bytes != (size_t)n*f.width*(f.kind == 4 ? 8 : 4)) return fail("fb_batch_get: size mismatch");
     HIPCHK(hipMemcpy(dst, f.base, bytes, hipMemcpyDeviceToHost));

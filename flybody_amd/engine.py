@@ -30,7 +30,7 @@ FIELDS = dict(QPOS=0, QVEL=1, ACT=2, CTRL=3, QACC=4, XPOS=5, XQUAT=6, SENSORDATA
               DISCOUNT=10, STEP_TYPE=11, NCON=12, NEFC=13, SOLVER_NITER=14, QFRC_BIAS=15, QFRC_PASSIVE=16,
               QACC_SMOOTH=17, QM=18, CONTACT=19, EFC_FORCE=20, QFRC_ACTUATOR=21, QFRC_CONSTRAINT=22,
               STEP_COUNT=23, SUBTREE_COM=24, PROF=25, REWARD_FACTORS=26, GEOM_XPOS=27, GEOM_XMAT=28, CVEL=29, STEP_TICKS=30, LAUNCH_ORDER=31, WARN=32, WARN_EVER=33, SIZE_STATS=34,
-              SITE_XPOS=35, IK_ERR=36, IK_STEPS=37)
+              SITE_XPOS=35, IK_ERR=36, IK_STEPS=37, QFRC_INVERSE=38, CONTACT_FORCE=39)
 _INT_FIELDS = {'STEP_TYPE', 'NCON', 'NEFC', 'SOLVER_NITER', 'STEP_COUNT', 'PROF', 'STEP_TICKS', 'LAUNCH_ORDER', 'WARN', 'WARN_EVER', 'SIZE_STATS', 'IK_STEPS'}
 # bits of WARN / WARN_EVER (include/flybody_engine.h): the caps MuJoCo reports as nconmax / njmax warnings, and iteration limits
 WARN_BITS = dict(CONTACT_CAP=1, EFC_CAP=2, SOLVER_MAXITER=4, CCD_MAXITER=8, SCHED_WAIT=16, SOLVER_FALLBACK=32)
@@ -110,6 +110,8 @@ def load_library(lib_path: Optional[str] = None) -> C.CDLL:
         L.fb_batch_timing_launches.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
     if hasattr(L, 'fb_batch_ik'):           # (A/B builds of older sources lack it)
         L.fb_batch_ik.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    if hasattr(L, 'fb_batch_inverse'):
+        L.fb_batch_inverse.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
     _libs[path] = L
     return L
 
@@ -282,6 +284,13 @@ class Batch:
                         float(beta), float(progress_threshold), int(max_steps))
         _check(self.L, self.L.fb_batch_ik(self.h, C.byref(cfg), t.ctypes.data, stream))
 
+    def inverse(self, discrete: bool = False, stream=None):
+        """Inverse dynamics for every environment (fb_batch_inverse, MuJoCo's mj_inverse): the generalised force that gives the
+        environment's QPOS / QVEL the acceleration QACC (set by the caller), in QFRC_INVERSE; per-contact forces in CONTACT_FORCE
+        ([n_env][MAXCON][3], contact frame); EFC_FORCE / QFRC_CONSTRAINT hold the inverse's values.  discrete: QACC is (qvel+ - qvel) / h
+        of the engine's Euler substep (FB_INV_DISCRETE).  Noslip is not inverted.  FP64 batches only.  Asynchronous after its checks."""
+        _check(self.L, self.L.fb_batch_inverse(self.h, 1 if discrete else 0, stream))
+
     def synchronize(self, stream=None):
         _check(self.L, self.L.fb_batch_synchronize(self.h, stream))
 
@@ -306,7 +315,7 @@ class Batch:
                     EFC_FORCE=MAXEFC, QFRC_ACTUATOR=m.dim('nv'), QFRC_CONSTRAINT=m.dim('nv'), STEP_COUNT=1,
                     SUBTREE_COM=3, PROF=112, REWARD_FACTORS=5, GEOM_XPOS=3*m.dim('ngeom'),
                     GEOM_XMAT=9*m.dim('ngeom'), CVEL=6*m.dim('nbody'), STEP_TICKS=1, LAUNCH_ORDER=1, WARN=1, WARN_EVER=1, SIZE_STATS=4,
-                    SITE_XPOS=3*m.dim('nsite'), IK_ERR=2, IK_STEPS=2)[name]
+                    SITE_XPOS=3*m.dim('nsite'), IK_ERR=2, IK_STEPS=2, QFRC_INVERSE=m.dim('nv'), CONTACT_FORCE=3*MAXCON)[name]
 
     def get(self, name: str) -> np.ndarray:
         w = self._width(name)

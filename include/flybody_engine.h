@@ -73,6 +73,9 @@ enum {
   FB_SITE_XPOS = 35,  /* [n_env][nsite][3] site positions (position stage) */
   FB_IK_ERR = 36,     /* [n_env][2] FP64: err_norm, err_norm_first_term of the last fb_batch_ik (read-only; allocated by the first call) */
   FB_IK_STEPS = 37,   /* [n_env][2] int32: steps, success of the last fb_batch_ik (read-only; allocated by the first call) */
+  FB_QFRC_INVERSE = 38,  /* [n_env][nv] FP64: qfrc_inverse of the last fb_batch_inverse (read-only; allocated by the first call) */
+  FB_CONTACT_FORCE = 39, /* [n_env][FB_MAXCON][3] FP64: force of contact c of the last fb_batch_inverse in its contact frame (normal,
+                            tangent 1, tangent 2; zero beyond the contact's condim and for c >= FB_NCON), rows as FB_CONTACT (read-only) */
   FB_NFIELD
 };
 
@@ -231,6 +234,21 @@ typedef struct fb_ik_config {
   int32_t max_steps;
 } fb_ik_config;
 int fb_batch_ik(fb_batch* b, const fb_ik_config* cfg, const double* target_xpos, void* stream);
+
+/* Inverse dynamics, MuJoCo's mj_inverse for every environment at once (FP64 batches only): from the environment's FB_QPOS, FB_QVEL and a
+ * caller-set FB_QACC,
+ *     FB_QFRC_INVERSE = M qacc + qfrc_bias - qfrc_passive - qfrc_constraint
+ * with M including armature, qfrc_passive = springs, dampers and the fluid forces, and qfrc_constraint = J' f(J qacc - aref), f the
+ * soft-constraint primal map (no solver runs).  Per-contact forces in FB_CONTACT_FORCE; FB_EFC_FORCE and FB_QFRC_CONSTRAINT hold the
+ * inverse's values afterwards, and the position / velocity stage outputs (FB_XPOS, FB_CONTACT, FB_QM, FB_QFRC_BIAS, ...) are refreshed
+ * from qpos / qvel as fb_batch_forward refreshes them.  FB_QACC is read, not written; nothing a later control step reads changes.
+ * Noslip is not inverted (neither does mj_inverse): for a model with noslip_iterations > 0 (fruitfly.xml sets 3) the inverse of a
+ * forward pass's qacc differs from its qfrc_actuator by what the noslip passes changed.
+ * flags: FB_INV_DISCRETE (MuJoCo's mjENBL_INVDISCRETE for the engine's semi-implicit Euler with implicit joint damping): FB_QACC is
+ * read as (qvel+ - qvel) / h and converted to M^-1 (M + h D) qacc first.  Fails on an FP32 batch, unknown flags and a non-finite
+ * FB_QACC (checked on the host: the call synchronises the device before it launches).  Asynchronous on `stream` after that. */
+enum { FB_INV_DISCRETE = 1 };
+int fb_batch_inverse(fb_batch* b, int flags, void* stream);
 
 const char* fb_last_error(void);
 
