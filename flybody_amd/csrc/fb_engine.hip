@@ -39,6 +39,7 @@ struct fb_model {
   std::map<std::string, const BlobEntry*> idx;
   // host-side derived tables
   int nq, nv, nbody, njnt, ngeom, nsite, nu, na, ntendon, npair, nM, nsubstep, nobsjnt, napp, nforce, ntouch;
+  int task_id;                           // 0 walk_imitation, 1 flight_imitation, 2 walk_on_ball
   std::vector<int> body_nsub, body_depth, body_chlen, body_chain, body_common, dof_depth, dof_ndesc, lvl_dof, lvl_start, adh_act;
   std::vector<int> wrap_qadr, act_wn, act_wdof, act_lenadr; std::vector<double> act_wcoef;
   std::vector<int> pair_word, pair_body, plane_geoms;
@@ -175,6 +176,7 @@ static int model_load_impl(fb_model* m, size_t n) {
   m->i("sensor_touch_sites", &c); m->ntouch = (int)c;
   if (m->nq <= 0 || m->nv <= 0 || m->nbody <= 1 || m->njnt <= 0) return fail("fb_model_load: empty model");
   check_model_arrays(m);
+  m->task_id = m->i("task_id")[0];
   m->nM = m->i("dof_Madr")[m->nv];
   if (!(m->d("opt_timestep")[0] > 0) || !(m->d("opt_control_timestep")[0] >= m->d("opt_timestep")[0])) return fail("fb_model_load: bad timestep / control timestep");
   m->nsubstep = (int)floor(m->d("opt_control_timestep")[0] / m->d("opt_timestep")[0] + 0.5);
@@ -503,15 +505,20 @@ static int model_load_impl(fb_model* m, size_t n) {
 
 extern "C" void fb_model_destroy(fb_model* m) { delete m; }
 
+// Width of the observation vector (engine.observation_layout; fb_step.hpp writes it): the walker's own observables, 7 per reference frame
+// of the imitation tasks (nref = future_steps + 1 of them) and, for walk_on_ball, the ball's velocity
+static int obs_width(const fb_model* m, int nref, bool ball) {
+  return 3 + m->na + 3*m->napp + (ball ? 3 : 0) + 3*m->nforce + 3 + 2*m->nobsjnt + 7*nref + m->ntouch + 3 + 3;
+}
+
 extern "C" int fb_model_dim(const fb_model* m, const char* name) {
   if (!m || !name) return -1;
 #define X(f) if (!strcmp(name, #f)) return m->f
   X(nq); X(nv); X(nbody); X(njnt); X(ngeom); X(nsite); X(nu); X(na); X(ntendon); X(npair); X(nM); X(nsubstep);
-  X(nobsjnt); X(napp); X(nforce); X(ntouch);
+  X(nobsjnt); X(napp); X(nforce); X(ntouch); X(task_id);
 #undef X
   if (!strcmp(name, "nact")) return m->nu + (m->i("user_action_idx")[0] >= 0 ? 1 : 0);
-  if (!strcmp(name, "task_id")) return m->i("task_id")[0];
-  if (!strcmp(name, "nobs_base")) return 3 + m->na + 3*m->napp + 3*m->nforce + 3 + 2*m->nobsjnt + m->ntouch + 3 + 3;
+  if (!strcmp(name, "nobs_base")) return obs_width(m, 0, false);
   return -1;
 }
 
@@ -883,9 +890,9 @@ struct fb_batch {
   unsigned xcc_mask = 0; std::vector<void*> probed_streams; unsigned* probe_word = nullptr;  // ... the streams it was validated on, the probe's device word
   void* park = nullptr;               // MODE_STAGE: LDS pools between single-stage launches (allocated on first use)
   std::vector<void*> allocs;          // model tables on the device
-  DevModel<double> M64; DevModel<float> M32;
-  DevModel<double> M64_dev; DevModel<float> M32_dev;   // what the device copy currently holds
+  DevModel<double> M64; DevModel<float> M32;   // the model at the batch's precision (with_model: only that one is built)
   void* dM = nullptr;                 // the model struct in device memory (the kernels read it through the constant path)
+  std::vector<char> dM_copy;          // ... what it currently holds (sync_model)
   void *ref_qpos = nullptr, *ref_qvel = nullptr;
   bool have_ref = false, have_wbpg = false;
   hipEvent_t ev0 = nullptr, ev1 = nullptr; int timed_launches = 0; bool timing = false;
@@ -915,6 +922,43 @@ static int upload_i(fb_batch* b, const int* src, size_t n, P* dst) {
                                                     // (flight_imitation has no force sensors: a garbage site id from here indexed site_bodyid wildly)
   b->allocs.push_back(p);
   *dst = (const int*)p;
+  return 0;
+}
+
+// f(M) on the batch's model at its precision: M64 for an FP64 batch, M32 for an FP32 one (the other one is never built or read).
+// Inside f, `using real = decltype(M.timestep);` names the precision.
+template <typename F>
+static auto with_model(fb_batch* b, F&& f) { return b->precision == 64 ? f(b->M64) : f(b->M32); }
+static size_t real_size(fb_batch* b) { return with_model(b, [](auto& M) { return sizeof(M.timestep); }); }
+
+// The device copy of the model struct follows the host copy (the setters only touch the host copy); a changed model is rare,
+// so the refresh simply waits for the device to be idle
+static int sync_model(fb_batch* b) {
+  return with_model(b, [&](auto& M) {
+    if (!b->dM) HIPCHK(hipMalloc(&b->dM, sizeof(M)));
+    const char* h = (const char*)&M;
+    if (b->dM_copy.empty() || memcmp(h, b->dM_copy.data(), sizeof(M)) != 0) {
+      HIPCHK(hipDeviceSynchronize());
+      HIPCHK(hipMemcpy(b->dM, h, sizeof(M), hipMemcpyHostToDevice));
+      b->dM_copy.assign(h, h + sizeof(M));
+    }
+    return 0;
+  });
+}
+
+// a zeroed device buffer, allocated on the first call that needs it
+template <typename T>
+static int alloc_zeroed_once(T** p, size_t bytes) {
+  if (!*p) { HIPCHK(hipMalloc((void**)p, bytes)); HIPCHK(hipMemset(*p, 0, bytes)); }
+  return 0;
+}
+
+// a new, zeroed observation buffer of nobs floats per environment
+static int alloc_obs(fb_batch* b, int nobs) {
+  (void)hipFree(b->obs); b->obs = nullptr;
+  HIPCHK(hipMalloc((void**)&b->obs, (size_t)b->n_env*nobs*sizeof(float)));
+  HIPCHK(hipMemset(b->obs, 0, (size_t)b->n_env*nobs*sizeof(float)));
+  b->nobs = nobs;
   return 0;
 }
 
@@ -974,7 +1018,7 @@ static int build_devmodel(fb_batch* b, DevModel<real>& M) {
   // leg joints (optional array: models compiled before the flight-with-legs variant do not carry it)
   if (m->has("leg_joints", 1)) { UI(leg_jnt, "leg_joints") M.nlegjnt = (int)c; for (size_t k = 0; k < c; k++) if (m->i("leg_joints")[k] < 0 || m->i("leg_joints")[k] >= m->njnt) return fail("fb_batch_create: leg_joints out of range"); }
   else { UV(leg_jnt, adh_act) M.nlegjnt = 0; }
-  M.task = m->i("task_id")[0]; M.user_idx = m->i("user_action_idx")[0]; M.nact = m->nu + (M.user_idx >= 0 ? 1 : 0);
+  M.task = m->task_id; M.user_idx = m->i("user_action_idx")[0]; M.nact = m->nu + (M.user_idx >= 0 ? 1 : 0);
   for (int k = 0; k < 3; k++) M.com_offset[k] = (real)m->d("com_offset")[k];
   M.nlevel = m->nlevel;
   UI(geom_type, "geom_type") UI(geom_bodyid, "geom_bodyid") UI(site_bodyid, "site_bodyid") UI(site_type, "site_type")
@@ -1043,10 +1087,9 @@ extern "C" int fb_batch_create(const fb_model* m, int n_env, int device, int pre
 }
 
 static int batch_create_impl(fb_batch* b) {
-  const fb_model* m = b->m; const int n_env = b->n_env, precision = b->precision;
-  if (precision == 64) { if (build_devmodel<double>(b, b->M64)) return -1; compute_offsets(b->M64, b->off); b->M64.off = b->off; }
-  else { if (build_devmodel<float>(b, b->M32)) return -1; compute_offsets(b->M32, b->off); b->M32.off = b->off; }
-  size_t rs = precision == 64 ? 8 : 4;
+  const fb_model* m = b->m; const int n_env = b->n_env;
+  if (with_model(b, [&](auto& M) { if (build_devmodel(b, M)) return -1; compute_offsets(M, b->off); M.off = b->off; return 0; })) return -1;
+  const size_t rs = real_size(b);
   HIPCHK(hipMalloc(&b->rarena, (size_t)n_env*b->off.nreal*rs));
   HIPCHK(hipMemset(b->rarena, 0, (size_t)n_env*b->off.nreal*rs));
   HIPCHK(hipMalloc((void**)&b->iarena, (size_t)n_env*b->off.nint*sizeof(int)));
@@ -1065,10 +1108,12 @@ static int batch_create_impl(fb_batch* b) {
 #ifdef FB_EMULATE
     b->nq = 1; b->slots = 2;                                   // (host emulation: tiny, so that the test batches take the ticket path)
 #else
-    int nb = 0;
     hipDeviceProp_t prop; HIPCHK(hipGetDeviceProperties(&prop, b->device));
-    if (precision == 64) { HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_fly<double>, FB_WAVE*LdsCfg<double>::EPB, 0)); b->slots = nb*prop.multiProcessorCount*LdsCfg<double>::EPB; }
-    else { HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_fly<float>, FB_WAVE*LdsCfg<float>::EPB, 0)); b->slots = nb*prop.multiProcessorCount*LdsCfg<float>::EPB; }
+    if (with_model(b, [&](auto& M) {
+          using real = decltype(M.timestep);
+          int nb = 0;
+          HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_fly<real>, FB_WAVE*LdsCfg<real>::EPB, 0)); b->slots = nb*prop.multiProcessorCount*LdsCfg<real>::EPB;
+          return 0; })) return -1;
     unsigned* dmask; unsigned hmask = 0;
     HIPCHK(hipMalloc((void**)&dmask, sizeof(unsigned))); HIPCHK(hipMemset(dmask, 0, sizeof(unsigned)));
     hipLaunchKernelGGL(k_probe_xcc, dim3(4096), dim3(FB_WAVE), 0, 0, dmask);
@@ -1097,15 +1142,12 @@ static int batch_create_impl(fb_batch* b) {
   HIPCHK(hipMemset(b->discount, 0, n_env*sizeof(float)));
   HIPCHK(hipMemset(b->step_type, 0, n_env*sizeof(int)));
   // initial state: qpos0 everywhere (fb_batch_reset overrides it once a reference is set)
-  {
-    std::vector<char> rows((size_t)n_env*m->nq*rs);
-    const double* q0 = m->d("qpos0");
-    for (int e = 0; e < n_env; e++)
-      for (int k = 0; k < m->nq; k++) {
-        if (rs == 8) ((double*)rows.data())[(size_t)e*m->nq + k] = q0[k]; else ((float*)rows.data())[(size_t)e*m->nq + k] = (float)q0[k];
-      }
-    HIPCHK(hipMemcpy2D((char*)b->rarena + (size_t)b->off.qpos*rs, (size_t)b->off.nreal*rs, rows.data(), (size_t)m->nq*rs, (size_t)m->nq*rs, n_env, hipMemcpyHostToDevice));
-  }
+  if (with_model(b, [&](auto& M) {
+        std::vector<decltype(M.timestep)> rows((size_t)n_env*m->nq);
+        const double* q0 = m->d("qpos0");
+        for (int e = 0; e < n_env; e++) std::copy_n(q0, m->nq, rows.data() + (size_t)e*m->nq);
+        HIPCHK(hipMemcpy2D((char*)b->rarena + (size_t)b->off.qpos*rs, (size_t)b->off.nreal*rs, rows.data(), (size_t)m->nq*rs, (size_t)m->nq*rs, n_env, hipMemcpyHostToDevice));
+        return 0; })) return -1;
   b->nobs = 0;
   return 0;
 }
@@ -1128,58 +1170,45 @@ extern "C" int fb_batch_set_reference(fb_batch* b, const double* ref_qpos, const
   if (!b || !ref_qpos || !ref_qvel || T < 2) return fail("fb_batch_set_reference: bad arguments");
   if (T - future_steps - 1 < 1) return fail("fb_batch_set_reference: trajectory shorter than future_steps + 2");
   HIPCHK(hipSetDevice(b->device));
-  (void)hipFree(b->ref_qpos); (void)hipFree(b->ref_qvel); (void)hipFree(b->obs);
-  b->ref_qpos = b->ref_qvel = nullptr; b->obs = nullptr; b->have_ref = false;     // (a failed allocation below must not leave dangling pointers)
+  (void)hipFree(b->ref_qpos); (void)hipFree(b->ref_qvel);
+  b->ref_qpos = b->ref_qvel = nullptr; b->have_ref = false;     // (a failed allocation below must not leave dangling pointers)
   const fb_model* m = b->m;
-  int nobs = 3 + m->na + 3*m->napp + 3*m->nforce + 3 + 2*m->nobsjnt + 7*(future_steps + 1) + m->ntouch + 3 + 3;
   int max_steps = (int)floor(time_limit / m->d("opt_control_timestep")[0] + 0.5) + 1;
   int snippet = T - future_steps - 1;
   int episode_steps = max_steps < snippet ? max_steps : snippet;
-  if (m->i("task_id")[0] == 1) {          // flight_imitation.py:101-105
+  if (m->task_id == 1) {          // flight_imitation.py:101-105
     int lim = max_steps - 1;
     episode_steps = (T < lim ? T : lim) - (future_steps + 1);
   }
-  size_t rs = b->precision == 64 ? 8 : 4;
-  HIPCHK(hipMalloc(&b->ref_qpos, (size_t)T*7*rs));
-  HIPCHK(hipMalloc(&b->ref_qvel, (size_t)T*6*rs));
-  if (rs == 8) {
-    HIPCHK(hipMemcpy(b->ref_qpos, ref_qpos, (size_t)T*7*8, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(b->ref_qvel, ref_qvel, (size_t)T*6*8, hipMemcpyHostToDevice));
-  } else {
-    std::vector<float> a((size_t)T*7), v((size_t)T*6);
-    for (size_t k = 0; k < a.size(); k++) a[k] = (float)ref_qpos[k];
-    for (size_t k = 0; k < v.size(); k++) v[k] = (float)ref_qvel[k];
-    HIPCHK(hipMemcpy(b->ref_qpos, a.data(), a.size()*4, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(b->ref_qvel, v.data(), v.size()*4, hipMemcpyHostToDevice));
-  }
-  HIPCHK(hipMalloc((void**)&b->obs, (size_t)b->n_env*nobs*sizeof(float)));
-  HIPCHK(hipMemset(b->obs, 0, (size_t)b->n_env*nobs*sizeof(float)));
-  b->nobs = nobs;
-#define SETREF(M) M.ref_qpos = (decltype(M.timestep)*)b->ref_qpos; M.ref_qvel = (decltype(M.timestep)*)b->ref_qvel; M.T = T; \
-  M.future_steps = future_steps; M.episode_steps = episode_steps; M.nobs = nobs; \
-  M.terminal_com_dist = (decltype(M.terminal_com_dist))terminal_com_dist; M.time_limit = (decltype(M.time_limit))time_limit;
-  SETREF(b->M64) SETREF(b->M32)
-#undef SETREF
-  b->have_ref = true;
-  return 0;
+  return with_model(b, [&](auto& M) {
+    using real = decltype(M.timestep);
+    const std::vector<real> q(ref_qpos, ref_qpos + (size_t)T*7), v(ref_qvel, ref_qvel + (size_t)T*6);
+    HIPCHK(hipMalloc(&b->ref_qpos, q.size()*sizeof(real)));
+    HIPCHK(hipMalloc(&b->ref_qvel, v.size()*sizeof(real)));
+    HIPCHK(hipMemcpy(b->ref_qpos, q.data(), q.size()*sizeof(real), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(b->ref_qvel, v.data(), v.size()*sizeof(real), hipMemcpyHostToDevice));
+    if (alloc_obs(b, obs_width(m, future_steps + 1, false))) return -1;
+    M.ref_qpos = (const real*)b->ref_qpos; M.ref_qvel = (const real*)b->ref_qvel; M.T = T;
+    M.future_steps = future_steps; M.episode_steps = episode_steps; M.nobs = b->nobs;
+    M.terminal_com_dist = (real)terminal_com_dist; M.time_limit = (real)time_limit;
+    b->have_ref = true;
+    return 0;
+  });
 }
 
 extern "C" int fb_batch_set_time_limit(fb_batch* b, double time_limit) {
   if (!b || !(time_limit > 0)) return fail("fb_batch_set_time_limit: bad arguments");
   const fb_model* m = b->m;
-  if (m->i("task_id")[0] != 2) return fail("fb_batch_set_time_limit: only the walk_on_ball task has no reference trajectory");
+  if (m->task_id != 2) return fail("fb_batch_set_time_limit: only the walk_on_ball task has no reference trajectory");
   HIPCHK(hipSetDevice(b->device));
-  int nobs = 3 + m->na + 3*m->napp + 3 + 3*m->nforce + 3 + 2*m->nobsjnt + m->ntouch + 3 + 3;
-  (void)hipFree(b->obs); b->obs = nullptr;
-  HIPCHK(hipMalloc((void**)&b->obs, (size_t)b->n_env*nobs*sizeof(float)));
-  HIPCHK(hipMemset(b->obs, 0, (size_t)b->n_env*nobs*sizeof(float)));
-  b->nobs = nobs;
-#define SETTL(M) M.nobs = nobs; M.T = 0; M.future_steps = 0; M.episode_steps = 0; M.time_limit = (decltype(M.time_limit))time_limit; \
-  M.terminal_com_dist = (decltype(M.terminal_com_dist))1e30;
-  SETTL(b->M64) SETTL(b->M32)
-#undef SETTL
-  b->have_ref = true;
-  return 0;
+  if (alloc_obs(b, obs_width(m, 0, true))) return -1;
+  return with_model(b, [&](auto& M) {
+    using real = decltype(M.timestep);
+    M.nobs = b->nobs; M.T = 0; M.future_steps = 0; M.episode_steps = 0; M.time_limit = (real)time_limit;
+    M.terminal_com_dist = (real)1e30;
+    b->have_ref = true;
+    return 0;
+  });
 }
 
 extern "C" int fb_batch_set_wbpg(fb_batch* b, const double* traj, const double* phase, const int32_t* offset, const double* freqs,
@@ -1187,15 +1216,16 @@ extern "C" int fb_batch_set_wbpg(fb_batch* b, const double* traj, const double* 
   if (!b || !traj || !phase || !offset || !freqs || nfreq <= 0) return fail("fb_batch_set_wbpg: bad arguments");
   HIPCHK(hipSetDevice(b->device));
   int rows = offset[nfreq];
-#define SETWB(M, real) { const real *t_, *p_, *f_; const int* o_; \
-    if (upload<real>(b, traj, (size_t)rows*6, &t_) || upload<real>(b, phase, (size_t)rows, &p_) || upload<real>(b, freqs, (size_t)nfreq, &f_) || \
-        upload_i(b, offset, (size_t)nfreq + 1, &o_)) return -1; \
-    M.wb_traj = t_; M.wb_phase = p_; M.wb_freqs = f_; M.wb_offset = o_; M.wb_nfreq = nfreq; M.wb_base_freq = (real)base_freq; \
-    M.wb_rel_range = (real)rel_range; M.wb_rate = (real)rate; M.seed = seed; }
-  if (b->precision == 64) SETWB(b->M64, double) else SETWB(b->M32, float)
-#undef SETWB
-  b->have_wbpg = true;
-  return 0;
+  return with_model(b, [&](auto& M) {
+    using real = decltype(M.timestep);
+    const real *t_, *p_, *f_; const int* o_;
+    if (upload<real>(b, traj, (size_t)rows*6, &t_) || upload<real>(b, phase, (size_t)rows, &p_) || upload<real>(b, freqs, (size_t)nfreq, &f_) ||
+        upload_i(b, offset, (size_t)nfreq + 1, &o_)) return -1;
+    M.wb_traj = t_; M.wb_phase = p_; M.wb_freqs = f_; M.wb_offset = o_; M.wb_nfreq = nfreq; M.wb_base_freq = (real)base_freq;
+    M.wb_rel_range = (real)rel_range; M.wb_rate = (real)rate; M.seed = seed;
+    b->have_wbpg = true;
+    return 0;
+  });
 }
 
 extern "C" int fb_batch_set_walk_dataset(fb_batch* b, const fb_walk_dataset* ds) {
@@ -1203,7 +1233,7 @@ extern "C" int fb_batch_set_walk_dataset(fb_batch* b, const fb_walk_dataset* ds)
     return fail("fb_batch_set_walk_dataset: null argument");
   if (ds->n_traj <= 0 || ds->n_select <= 0 || ds->n_joints < 0 || ds->n_sites < 0) return fail("fb_batch_set_walk_dataset: bad sizes");
   const fb_model* m = b->m;
-  if (m->i("task_id")[0] != 0) return fail("fb_batch_set_walk_dataset: not a walk_imitation model");
+  if (m->task_id != 0) return fail("fb_batch_set_walk_dataset: not a walk_imitation model");
   for (int k = 0; k < ds->n_joints; k++) if (ds->joint_ids[k] < 0 || ds->joint_ids[k] >= m->njnt) return fail("fb_batch_set_walk_dataset: joint id out of range");
   for (int k = 0; k < ds->n_sites; k++) if (ds->site_ids[k] < 0 || ds->site_ids[k] >= m->nsite) return fail("fb_batch_set_walk_dataset: site id out of range");
   for (int k = 0; k < ds->n_select; k++) {
@@ -1214,31 +1244,28 @@ extern "C" int fb_batch_set_walk_dataset(fb_batch* b, const fb_walk_dataset* ds)
   HIPCHK(hipSetDevice(b->device));
   size_t rows = (size_t)ds->traj_offset[ds->n_traj];
   int nj = ds->n_joints, ns = ds->n_sites, future_steps = ds->future_steps;
-  int nobs = 3 + m->na + 3*m->napp + 3*m->nforce + 3 + 2*m->nobsjnt + 7*(future_steps + 1) + m->ntouch + 3 + 3;
   int max_steps = (int)floor(ds->time_limit / m->d("opt_control_timestep")[0] + 0.5) + 1;
-  (void)hipFree(b->obs); b->obs = nullptr;
-  HIPCHK(hipMalloc((void**)&b->obs, (size_t)b->n_env*nobs*sizeof(float)));
-  HIPCHK(hipMemset(b->obs, 0, (size_t)b->n_env*nobs*sizeof(float)));
-  b->nobs = nobs;
-#define SETDS(M, real) { const real *q_, *v_, *r_, *j_; const int *o_, *ji_, *si_, *se_; \
-    if (upload<real>(b, ds->qpos, rows*(7 + nj), &q_) || upload<real>(b, ds->qvel, rows*(6 + nj), &v_) || upload<real>(b, ds->root2site, rows*3*ns, &r_) || \
-        upload<real>(b, ds->joint_quat, rows*4*nj, &j_) || upload_i(b, ds->traj_offset, (size_t)ds->n_traj + 1, &o_) || upload_i(b, ds->joint_ids, nj, &ji_) || \
-        upload_i(b, ds->site_ids, ns, &si_) || upload_i(b, ds->select, ds->n_select, &se_)) return -1; \
-    M.ds_qpos = q_; M.ds_qvel = v_; M.ds_r2s = r_; M.ds_jq = j_; M.ds_offset = o_; M.ds_jid = ji_; M.ds_sid = si_; M.ds_select = se_; \
-    M.ds_nj = nj; M.ds_ns = ns; M.ds_ntraj = ds->n_traj; M.ds_nselect = ds->n_select; M.ds_env_base = ds->env_id_base; M.max_episode_steps = max_steps; \
-    M.seed = ds->seed; M.future_steps = future_steps; M.nobs = nobs; M.T = 0; M.episode_steps = 0; \
-    M.terminal_com_dist = (real)ds->terminal_com_dist; M.time_limit = (real)ds->time_limit; }
-  if (b->precision == 64) SETDS(b->M64, double) else SETDS(b->M32, float)
-#undef SETDS
-  b->have_ref = true;
-  return 0;
+  if (alloc_obs(b, obs_width(m, future_steps + 1, false))) return -1;
+  return with_model(b, [&](auto& M) {
+    using real = decltype(M.timestep);
+    const real *q_, *v_, *r_, *j_; const int *o_, *ji_, *si_, *se_;
+    if (upload<real>(b, ds->qpos, rows*(7 + nj), &q_) || upload<real>(b, ds->qvel, rows*(6 + nj), &v_) || upload<real>(b, ds->root2site, rows*3*ns, &r_) ||
+        upload<real>(b, ds->joint_quat, rows*4*nj, &j_) || upload_i(b, ds->traj_offset, (size_t)ds->n_traj + 1, &o_) || upload_i(b, ds->joint_ids, nj, &ji_) ||
+        upload_i(b, ds->site_ids, ns, &si_) || upload_i(b, ds->select, ds->n_select, &se_)) return -1;
+    M.ds_qpos = q_; M.ds_qvel = v_; M.ds_r2s = r_; M.ds_jq = j_; M.ds_offset = o_; M.ds_jid = ji_; M.ds_sid = si_; M.ds_select = se_;
+    M.ds_nj = nj; M.ds_ns = ns; M.ds_ntraj = ds->n_traj; M.ds_nselect = ds->n_select; M.ds_env_base = ds->env_id_base; M.max_episode_steps = max_steps;
+    M.seed = ds->seed; M.future_steps = future_steps; M.nobs = b->nobs; M.T = 0; M.episode_steps = 0;
+    M.terminal_com_dist = (real)ds->terminal_com_dist; M.time_limit = (real)ds->time_limit;
+    b->have_ref = true;
+    return 0;
+  });
 }
 
 extern "C" int fb_batch_set_flight_dataset(fb_batch* b, const fb_flight_dataset* ds) {
   if (!b || !ds || !ds->traj_offset || !ds->qpos || !ds->qvel || !ds->select) return fail("fb_batch_set_flight_dataset: null argument");
   if (ds->n_traj <= 0 || ds->n_select <= 0 || ds->future_steps < 0) return fail("fb_batch_set_flight_dataset: bad sizes");
   const fb_model* m = b->m;
-  if (m->i("task_id")[0] != 1) return fail("fb_batch_set_flight_dataset: not a flight_imitation model");
+  if (m->task_id != 1) return fail("fb_batch_set_flight_dataset: not a flight_imitation model");
   for (int k = 0; k < ds->n_select; k++) {
     int t = ds->select[k];
     if (t < 0 || t >= ds->n_traj) return fail("fb_batch_set_flight_dataset: selected trajectory out of range");
@@ -1249,37 +1276,35 @@ extern "C" int fb_batch_set_flight_dataset(fb_batch* b, const fb_flight_dataset*
   HIPCHK(hipSetDevice(b->device));
   size_t rows = (size_t)ds->traj_offset[ds->n_traj];
   int future_steps = ds->future_steps;
-  int nobs = 3 + m->na + 3*m->napp + 3*m->nforce + 3 + 2*m->nobsjnt + 7*(future_steps + 1) + m->ntouch + 3 + 3;
-  (void)hipFree(b->obs); b->obs = nullptr;
-  HIPCHK(hipMalloc((void**)&b->obs, (size_t)b->n_env*nobs*sizeof(float)));
-  HIPCHK(hipMemset(b->obs, 0, (size_t)b->n_env*nobs*sizeof(float)));
-  b->nobs = nobs;
-#define SETFD(M, real) { const real *q_, *v_; const int *o_, *se_; \
-    if (upload<real>(b, ds->qpos, rows*7, &q_) || upload<real>(b, ds->qvel, rows*6, &v_) || \
-        upload_i(b, ds->traj_offset, (size_t)ds->n_traj + 1, &o_) || upload_i(b, ds->select, ds->n_select, &se_)) return -1; \
-    M.ds_qpos = q_; M.ds_qvel = v_; M.ds_offset = o_; M.ds_select = se_; M.ds_nj = 0; M.ds_ns = 0; M.ds_ntraj = ds->n_traj; \
-    M.ds_nselect = ds->n_select; M.ds_env_base = ds->env_id_base; M.ds_random_start = ds->randomize_start_step ? 1 : 0; \
-    M.seed = ds->seed; M.future_steps = future_steps; M.nobs = nobs; M.T = 0; M.episode_steps = 0; \
-    M.terminal_com_dist = (real)ds->terminal_com_dist; M.time_limit = (real)ds->time_limit; }
-  if (b->precision == 64) SETFD(b->M64, double) else SETFD(b->M32, float)
-#undef SETFD
-  b->have_ref = true;
-  return 0;
+  if (alloc_obs(b, obs_width(m, future_steps + 1, false))) return -1;
+  return with_model(b, [&](auto& M) {
+    using real = decltype(M.timestep);
+    const real *q_, *v_; const int *o_, *se_;
+    if (upload<real>(b, ds->qpos, rows*7, &q_) || upload<real>(b, ds->qvel, rows*6, &v_) ||
+        upload_i(b, ds->traj_offset, (size_t)ds->n_traj + 1, &o_) || upload_i(b, ds->select, ds->n_select, &se_)) return -1;
+    M.ds_qpos = q_; M.ds_qvel = v_; M.ds_offset = o_; M.ds_select = se_; M.ds_nj = 0; M.ds_ns = 0; M.ds_ntraj = ds->n_traj;
+    M.ds_nselect = ds->n_select; M.ds_env_base = ds->env_id_base; M.ds_random_start = ds->randomize_start_step ? 1 : 0;
+    M.seed = ds->seed; M.future_steps = future_steps; M.nobs = b->nobs; M.T = 0; M.episode_steps = 0;
+    M.terminal_com_dist = (real)ds->terminal_com_dist; M.time_limit = (real)ds->time_limit;
+    b->have_ref = true;
+    return 0;
+  });
+}
+
+// the k_fly / k_fly_reset launch of launch()
+template <typename real>
+static void launch_fly(fb_batch* b, int mode, const float* action, const int* ids, int n, int nsub, hipStream_t st, bool tickets, const int* tord) {
+  constexpr int EPB = LdsCfg<real>::EPB;
+  const DevModel<real>* dM = (const DevModel<real>*)b->dM;
+  Batch<real> B = {(real*)b->rarena, b->iarena, b->obs, b->reward, b->discount, b->step_type, b->n_env, b->nobs, b->use_prio ? b->sched : nullptr, b->cost,
+                   tickets ? b->tick : nullptr, b->done, b->nq, b->sched_err, tord, (real*)b->park};
+  if (mode == MODE_RESET) hipLaunchKernelGGL((k_fly_reset<real>), dim3((n + EPB - 1)/EPB), dim3(FB_WAVE*EPB), 0, st, dM, B, ids, nsub, n);
+  else hipLaunchKernelGGL((k_fly<real>), dim3((n + EPB - 1)/EPB), dim3(FB_WAVE*EPB), 0, st, dM, B, action, ids, mode, nsub, n);
 }
 
 static int launch(fb_batch* b, int mode, const float* action, const int* ids, int n, int nsub, void* stream) {
   hipStream_t st = (hipStream_t)stream;
-  // the device copy of the model struct follows the host copy (setters only touch the host copy); a changed model is rare,
-  // so the refresh simply waits for the device to be idle
-  const void* hM = b->precision == 64 ? (const void*)&b->M64 : (const void*)&b->M32;
-  void* hD = b->precision == 64 ? (void*)&b->M64_dev : (void*)&b->M32_dev;
-  size_t nM = b->precision == 64 ? sizeof(b->M64) : sizeof(b->M32);
-  if (!b->dM) { HIPCHK(hipMalloc(&b->dM, nM)); memset(hD, 0xff, nM); }
-  if (memcmp(hM, hD, nM) != 0) {
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(b->dM, hM, nM, hipMemcpyHostToDevice));
-    memcpy(hD, hM, nM);
-  }
+  if (sync_model(b)) return -1;
   HIPCHK(hipMemsetAsync(b->sched, 0, FB_NSCHED*sizeof(int), st));
   // a control step of the whole batch: substep scheduler when the batch exceeds the resident slots, otherwise one environment per
   // wave in longest-first order
@@ -1319,17 +1344,7 @@ static int launch(fb_batch* b, int mode, const float* action, const int* ids, in
     while ((int)b->lev.size() < 2*(b->timed_launches + 1)) { hipEvent_t nev; HIPCHK(hipEventCreate(&nev)); b->lev.push_back(nev); }
     HIPCHK(hipEventRecord(b->lev[2*b->timed_launches], st));
   }
-  if (b->precision == 64) {
-    Batch<double> B = {(double*)b->rarena, b->iarena, b->obs, b->reward, b->discount, b->step_type, b->n_env, b->nobs, b->use_prio ? b->sched : nullptr, b->cost,
-                       tickets ? b->tick : nullptr, b->done, b->nq, b->sched_err, tord, (double*)b->park};
-    if (mode == MODE_RESET) hipLaunchKernelGGL((k_fly_reset<double>), dim3((n + LdsCfg<double>::EPB - 1)/LdsCfg<double>::EPB), dim3(FB_WAVE*LdsCfg<double>::EPB), 0, st, (const DevModel<double>*)b->dM, B, ids, nsub, n);
-    else hipLaunchKernelGGL((k_fly<double>), dim3((n + LdsCfg<double>::EPB - 1)/LdsCfg<double>::EPB), dim3(FB_WAVE*LdsCfg<double>::EPB), 0, st, (const DevModel<double>*)b->dM, B, action, ids, mode, nsub, n);
-  } else {
-    Batch<float> B = {(float*)b->rarena, b->iarena, b->obs, b->reward, b->discount, b->step_type, b->n_env, b->nobs, b->use_prio ? b->sched : nullptr, b->cost,
-                      tickets ? b->tick : nullptr, b->done, b->nq, b->sched_err, tord, (float*)b->park};
-    if (mode == MODE_RESET) hipLaunchKernelGGL((k_fly_reset<float>), dim3((n + LdsCfg<float>::EPB - 1)/LdsCfg<float>::EPB), dim3(FB_WAVE*LdsCfg<float>::EPB), 0, st, (const DevModel<float>*)b->dM, B, ids, nsub, n);
-    else hipLaunchKernelGGL((k_fly<float>), dim3((n + LdsCfg<float>::EPB - 1)/LdsCfg<float>::EPB), dim3(FB_WAVE*LdsCfg<float>::EPB), 0, st, (const DevModel<float>*)b->dM, B, action, ids, mode, nsub, n);
-  }
+  with_model(b, [&](auto& M) { launch_fly<decltype(M.timestep)>(b, mode, action, ids, n, nsub, st, tickets, tord); });
   if (per_launch) HIPCHK(hipEventRecord(b->lev[2*b->timed_launches + 1], st));
   if (full_step) { hipLaunchKernelGGL(k_order, dim3(1), dim3(FB_ORDER_THREADS), 0, st, b->cost, b->order, n); b->order_valid = true; }
   HIPCHK(hipGetLastError());
@@ -1337,10 +1352,16 @@ static int launch(fb_batch* b, int mode, const float* action, const int* ids, in
   return 0;
 }
 
+// the tables a control step reads are set: a reference (or dataset / time limit) and, with `wbpg`, flight's pattern generator
+static int check_ready(const fb_batch* b, const char* fn, bool wbpg) {
+  if (!b->have_ref) return fail(std::string(fn) + ": call fb_batch_set_reference first");
+  if (wbpg && b->m->task_id == 1 && !b->have_wbpg) return fail(std::string(fn) + ": flight task needs fb_batch_set_wbpg first");
+  return 0;
+}
+
 extern "C" int fb_batch_reset(fb_batch* b, const int32_t* env_ids, int n, void* stream) {
   if (!b) return fail("fb_batch_reset: null batch");
-  if (!b->have_ref) return fail("fb_batch_reset: call fb_batch_set_reference first");
-  if (b->m->i("task_id")[0] == 1 && !b->have_wbpg) return fail("fb_batch_reset: flight task needs fb_batch_set_wbpg first");
+  if (check_ready(b, "fb_batch_reset", true)) return -1;
   HIPCHK(hipSetDevice(b->device));
   if (env_ids) {
     if (n <= 0 || n > b->n_env) return fail("fb_batch_reset: bad n");
@@ -1353,8 +1374,7 @@ extern "C" int fb_batch_reset(fb_batch* b, const int32_t* env_ids, int n, void* 
 
 extern "C" int fb_batch_step(fb_batch* b, const float* action, void* stream) {
   if (!b || !action) return fail("fb_batch_step: null argument");
-  if (!b->have_ref) return fail("fb_batch_step: call fb_batch_set_reference first");
-  if (b->m->i("task_id")[0] == 1 && !b->have_wbpg) return fail("fb_batch_step: flight task needs fb_batch_set_wbpg first");
+  if (check_ready(b, "fb_batch_step", true)) return -1;
   HIPCHK(hipSetDevice(b->device));
   return launch(b, MODE_STEP, action, nullptr, b->n_env, 0, stream);
 }
@@ -1400,13 +1420,10 @@ extern "C" int fb_batch_synchronize(fb_batch* b, void* stream) {
 // of a control step itself (tools/stage_profile.py); results equal fb_batch_step's as long as no environment ends its episode.
 extern "C" int fb_batch_stage(fb_batch* b, int stage_word, const float* action, void* stream) {
   if (!b || stage_word < 0) return fail("fb_batch_stage: bad arguments");
-  if (!b->have_ref) return fail("fb_batch_stage: call fb_batch_set_reference first");
+  if (check_ready(b, "fb_batch_stage", false)) return -1;
   HIPCHK(hipSetDevice(b->device));
-  if (!b->park) {
-    const size_t pool = b->precision == 64 ? (size_t)LdsCfg<double>::POOL*8 : (size_t)LdsCfg<float>::POOL*4;
-    HIPCHK(hipMalloc(&b->park, (size_t)b->n_env*pool));
-    HIPCHK(hipMemset(b->park, 0, (size_t)b->n_env*pool));
-  }
+  const size_t pool = with_model(b, [](auto& M) { return sizeof(M.timestep)*LdsCfg<decltype(M.timestep)>::POOL; });
+  if (alloc_zeroed_once(&b->park, (size_t)b->n_env*pool)) return -1;
   return launch(b, MODE_STAGE, action, nullptr, b->n_env, stage_word, stream);
 }
 
@@ -1461,22 +1478,14 @@ extern "C" int fb_batch_ik(fb_batch* b, const fb_ik_config* cfg, const double* t
   const size_t tgt_off = ((it.size()*sizeof(int) + 255) & ~(size_t)255), bytes = tgt_off + (size_t)n*3*ns*sizeof(double);
   HIPCHK(hipSetDevice(b->device));
   HIPCHK(hipDeviceSynchronize());                      // (a previous IK launch may still read the buffer)
-  if (!b->ik_err) {
-    HIPCHK(hipMalloc((void**)&b->ik_err, (size_t)n*2*sizeof(double))); HIPCHK(hipMemset(b->ik_err, 0, (size_t)n*2*sizeof(double)));
-    HIPCHK(hipMalloc((void**)&b->ik_steps, (size_t)n*2*sizeof(int))); HIPCHK(hipMemset(b->ik_steps, 0, (size_t)n*2*sizeof(int)));
-  }
+  if (alloc_zeroed_once(&b->ik_err, (size_t)n*2*sizeof(double)) || alloc_zeroed_once(&b->ik_steps, (size_t)n*2*sizeof(int))) return -1;
   if (b->ik_buf_bytes < bytes) {
     (void)hipFree(b->ik_buf); b->ik_buf = nullptr; b->ik_buf_bytes = 0;
     HIPCHK(hipMalloc(&b->ik_buf, bytes)); b->ik_buf_bytes = bytes;
   }
   HIPCHK(hipMemcpy(b->ik_buf, it.data(), it.size()*sizeof(int), hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy((char*)b->ik_buf + tgt_off, target_xpos, (size_t)n*3*ns*sizeof(double), hipMemcpyHostToDevice));
-  // the device copy of the model struct follows the host copy (as in launch())
-  if (!b->dM) { HIPCHK(hipMalloc(&b->dM, sizeof(b->M64))); memset(&b->M64_dev, 0xff, sizeof(b->M64)); }
-  if (memcmp(&b->M64, &b->M64_dev, sizeof(b->M64)) != 0) {
-    HIPCHK(hipMemcpy(b->dM, &b->M64, sizeof(b->M64), hipMemcpyHostToDevice));
-    memcpy(&b->M64_dev, &b->M64, sizeof(b->M64));
-  }
+  if (sync_model(b)) return -1;
   const int* ib = (const int*)b->ik_buf;
   IKArgs<double> A;
   A.site = ib + o_site; A.bsite_off = ib + o_boff; A.bsite = ib + o_bsite; A.include = ib + o_inc; A.dof = ib + o_dof; A.dof_hq = ib + o_hq;
@@ -1506,16 +1515,8 @@ extern "C" int fb_batch_inverse(fb_batch* b, int flags, void* stream) {
     for (size_t k = 0; k < qacc.size(); k++)
       if (!std::isfinite(qacc[k])) return fail("fb_batch_inverse: FB_QACC of environment " + std::to_string(k/nv) + " is not finite");
   }
-  if (!b->inv_qfrc) {
-    HIPCHK(hipMalloc((void**)&b->inv_qfrc, (size_t)n*nv*sizeof(double))); HIPCHK(hipMemset(b->inv_qfrc, 0, (size_t)n*nv*sizeof(double)));
-    HIPCHK(hipMalloc((void**)&b->inv_cforce, (size_t)n*3*FB_MAXCON_*sizeof(double))); HIPCHK(hipMemset(b->inv_cforce, 0, (size_t)n*3*FB_MAXCON_*sizeof(double)));
-  }
-  // the device copy of the model struct follows the host copy (as in launch())
-  if (!b->dM) { HIPCHK(hipMalloc(&b->dM, sizeof(b->M64))); memset(&b->M64_dev, 0xff, sizeof(b->M64)); }
-  if (memcmp(&b->M64, &b->M64_dev, sizeof(b->M64)) != 0) {
-    HIPCHK(hipMemcpy(b->dM, &b->M64, sizeof(b->M64), hipMemcpyHostToDevice));
-    memcpy(&b->M64_dev, &b->M64, sizeof(b->M64));
-  }
+  if (alloc_zeroed_once(&b->inv_qfrc, (size_t)n*nv*sizeof(double)) || alloc_zeroed_once(&b->inv_cforce, (size_t)n*3*FB_MAXCON_*sizeof(double))) return -1;
+  if (sync_model(b)) return -1;
   InvArgs<double> A;
   A.qfrc_inverse = b->inv_qfrc; A.contact_force = b->inv_cforce; A.n_env = n;
   A.flags = (flags & FB_INV_DISCRETE) ? FB_INV_FLAG_DISCRETE : 0;
@@ -1528,53 +1529,74 @@ extern "C" int fb_batch_inverse(fb_batch* b, int flags, void* stream) {
 }
 
 // ------------------------------------------------------------------ field access
-struct FieldDesc { int kind; /*0 real arena, 1 int arena, 2 f32 array, 3 i32 array, 4 f64 array*/ size_t off, width; void* base; };
+enum FieldKind { REAL_ARENA, INT_ARENA, F32_ARRAY, I32_ARRAY, F64_ARRAY };
+// rows of `width` at offset `off` of an arena row, or an array [n_env][width] of its own at `base`; `unset`: why such an array is not
+// allocated yet (the ones allocated with the batch need none)
+struct FieldDesc { FieldKind kind; size_t off, width; void* base = nullptr; const char* unset = nullptr; };
 
 static int field_desc(fb_batch* b, int field, FieldDesc* f) {
   const fb_model* m = b->m; const WSOff& o = b->off;
+  const char* no_ref = "fb_batch_get: field not allocated yet (set a reference first)";
+  const char* no_ik = "fb_batch_get: field not allocated yet (run fb_batch_ik first)";
+  const char* no_inv = "fb_batch_get: field not allocated yet (run fb_batch_inverse first)";
   switch (field) {
-    case FB_QPOS: *f = {0, o.qpos, (size_t)m->nq, nullptr}; break;
-    case FB_QVEL: *f = {0, o.qvel, (size_t)m->nv, nullptr}; break;
-    case FB_ACT: *f = {0, o.act, (size_t)m->na, nullptr}; break;
-    case FB_CTRL: *f = {0, o.ctrl, (size_t)m->nu, nullptr}; break;
-    case FB_QACC: *f = {0, o.qacc, (size_t)m->nv, nullptr}; break;
-    case FB_XPOS: *f = {0, o.xpos, (size_t)3*m->nbody, nullptr}; break;
-    case FB_XQUAT: *f = {0, o.xquat, (size_t)4*m->nbody, nullptr}; break;
-    case FB_SENSORDATA: *f = {0, o.sens, FB_NSENS, nullptr}; break;
-    case FB_QFRC_BIAS: *f = {0, o.qfrc_bias, (size_t)m->nv, nullptr}; break;
-    case FB_QFRC_PASSIVE: *f = {0, o.qfrc_passive, (size_t)m->nv, nullptr}; break;
-    case FB_QACC_SMOOTH: *f = {0, o.qacc_smooth, (size_t)m->nv, nullptr}; break;
-    case FB_QM: *f = {0, o.qM, (size_t)m->nM, nullptr}; break;
-    case FB_EFC_FORCE: *f = {0, o.efc_force, FB_MAXEFC_, nullptr}; break;
-    case FB_QFRC_ACTUATOR: *f = {0, o.qfrc_actuator, (size_t)m->nv, nullptr}; break;
-    case FB_QFRC_CONSTRAINT: *f = {0, o.qfrc_constraint, (size_t)m->nv, nullptr}; break;
-    case FB_SUBTREE_COM: *f = {0, o.com, 3, nullptr}; break;
-    case FB_NCON: *f = {1, o.istate + IS_NCON, 1, nullptr}; break;
-    case FB_NEFC: *f = {1, o.istate + IS_NEFC, 1, nullptr}; break;
-    case FB_SOLVER_NITER: *f = {1, o.istate + IS_NITER, 1, nullptr}; break;
-    case FB_STEP_COUNT: *f = {1, o.istate + IS_STEP, 1, nullptr}; break;
-    case FB_PROF: *f = {1, o.prof, 2*FB_NPROF, nullptr}; break;
-    case FB_REWARD_FACTORS: *f = {0, o.rfac, 5, nullptr}; break;
-    case FB_GEOM_XPOS: *f = {0, o.gxpos, (size_t)3*m->ngeom, nullptr}; break;
-    case FB_GEOM_XMAT: *f = {0, o.gxmat, (size_t)9*m->ngeom, nullptr}; break;
-    case FB_CVEL: *f = {0, o.cvel, (size_t)6*m->nbody, nullptr}; break;
-    case FB_OBS: *f = {2, 0, (size_t)b->nobs, b->obs}; break;
-    case FB_REWARD: *f = {2, 0, 1, b->reward}; break;
-    case FB_DISCOUNT: *f = {2, 0, 1, b->discount}; break;
-    case FB_STEP_TYPE: *f = {3, 0, 1, b->step_type}; break;
-    case FB_WARN: *f = {1, o.istate + IS_WARN, 1, nullptr}; break;
-    case FB_WARN_EVER: *f = {1, o.istate + IS_WARN_EVER, 1, nullptr}; break;
-    case FB_SIZE_STATS: *f = {1, o.istate + IS_MAX_NCON, 4, nullptr}; break;
-    case FB_STEP_TICKS: *f = {3, 0, 1, b->cost}; break;
-    case FB_LAUNCH_ORDER: *f = {3, 0, 1, b->order}; break;
-    case FB_SITE_XPOS: *f = {0, o.sxpos, (size_t)3*m->nsite, nullptr}; break;
-    case FB_IK_ERR: *f = {4, 0, 2, b->ik_err}; break;
-    case FB_IK_STEPS: *f = {3, 0, 2, b->ik_steps}; break;
-    case FB_QFRC_INVERSE: *f = {4, 0, (size_t)m->nv, b->inv_qfrc}; break;
-    case FB_CONTACT_FORCE: *f = {4, 0, (size_t)3*FB_MAXCON_, b->inv_cforce}; break;
+    case FB_QPOS: *f = {REAL_ARENA, o.qpos, (size_t)m->nq}; break;
+    case FB_QVEL: *f = {REAL_ARENA, o.qvel, (size_t)m->nv}; break;
+    case FB_ACT: *f = {REAL_ARENA, o.act, (size_t)m->na}; break;
+    case FB_CTRL: *f = {REAL_ARENA, o.ctrl, (size_t)m->nu}; break;
+    case FB_QACC: *f = {REAL_ARENA, o.qacc, (size_t)m->nv}; break;
+    case FB_XPOS: *f = {REAL_ARENA, o.xpos, (size_t)3*m->nbody}; break;
+    case FB_XQUAT: *f = {REAL_ARENA, o.xquat, (size_t)4*m->nbody}; break;
+    case FB_SENSORDATA: *f = {REAL_ARENA, o.sens, FB_NSENS}; break;
+    case FB_QFRC_BIAS: *f = {REAL_ARENA, o.qfrc_bias, (size_t)m->nv}; break;
+    case FB_QFRC_PASSIVE: *f = {REAL_ARENA, o.qfrc_passive, (size_t)m->nv}; break;
+    case FB_QACC_SMOOTH: *f = {REAL_ARENA, o.qacc_smooth, (size_t)m->nv}; break;
+    case FB_QM: *f = {REAL_ARENA, o.qM, (size_t)m->nM}; break;
+    case FB_EFC_FORCE: *f = {REAL_ARENA, o.efc_force, FB_MAXEFC_}; break;
+    case FB_QFRC_ACTUATOR: *f = {REAL_ARENA, o.qfrc_actuator, (size_t)m->nv}; break;
+    case FB_QFRC_CONSTRAINT: *f = {REAL_ARENA, o.qfrc_constraint, (size_t)m->nv}; break;
+    case FB_SUBTREE_COM: *f = {REAL_ARENA, o.com, 3}; break;
+    case FB_NCON: *f = {INT_ARENA, o.istate + IS_NCON, 1}; break;
+    case FB_NEFC: *f = {INT_ARENA, o.istate + IS_NEFC, 1}; break;
+    case FB_SOLVER_NITER: *f = {INT_ARENA, o.istate + IS_NITER, 1}; break;
+    case FB_STEP_COUNT: *f = {INT_ARENA, o.istate + IS_STEP, 1}; break;
+    case FB_PROF: *f = {INT_ARENA, o.prof, 2*FB_NPROF}; break;
+    case FB_REWARD_FACTORS: *f = {REAL_ARENA, o.rfac, 5}; break;
+    case FB_GEOM_XPOS: *f = {REAL_ARENA, o.gxpos, (size_t)3*m->ngeom}; break;
+    case FB_GEOM_XMAT: *f = {REAL_ARENA, o.gxmat, (size_t)9*m->ngeom}; break;
+    case FB_CVEL: *f = {REAL_ARENA, o.cvel, (size_t)6*m->nbody}; break;
+    case FB_OBS: *f = {F32_ARRAY, 0, (size_t)b->nobs, b->obs, no_ref}; break;
+    case FB_REWARD: *f = {F32_ARRAY, 0, 1, b->reward}; break;
+    case FB_DISCOUNT: *f = {F32_ARRAY, 0, 1, b->discount}; break;
+    case FB_STEP_TYPE: *f = {I32_ARRAY, 0, 1, b->step_type}; break;
+    case FB_WARN: *f = {INT_ARENA, o.istate + IS_WARN, 1}; break;
+    case FB_WARN_EVER: *f = {INT_ARENA, o.istate + IS_WARN_EVER, 1}; break;
+    case FB_SIZE_STATS: *f = {INT_ARENA, o.istate + IS_MAX_NCON, 4}; break;
+    case FB_STEP_TICKS: *f = {I32_ARRAY, 0, 1, b->cost}; break;
+    case FB_LAUNCH_ORDER: *f = {I32_ARRAY, 0, 1, b->order}; break;
+    case FB_SITE_XPOS: *f = {REAL_ARENA, o.sxpos, (size_t)3*m->nsite}; break;
+    case FB_IK_ERR: *f = {F64_ARRAY, 0, 2, b->ik_err, no_ik}; break;
+    case FB_IK_STEPS: *f = {I32_ARRAY, 0, 2, b->ik_steps, no_ik}; break;
+    case FB_QFRC_INVERSE: *f = {F64_ARRAY, 0, (size_t)m->nv, b->inv_qfrc, no_inv}; break;
+    case FB_CONTACT_FORCE: *f = {F64_ARRAY, 0, (size_t)3*FB_MAXCON_, b->inv_cforce, no_inv}; break;
     default: return fail("unknown field");
   }
   return 0;
+}
+
+// a REAL_ARENA field of every environment, between the arena (the batch's precision) and FP64 rows [n_env][width] on the host
+static int real_rows(fb_batch* b, const FieldDesc& f, double* host, bool to_device) {
+  return with_model(b, [&](auto& M) {
+    using real = decltype(M.timestep);
+    const size_t row = f.width*sizeof(real), pitch = (size_t)b->off.nreal*sizeof(real);
+    char* dev = (char*)b->rarena + f.off*sizeof(real);
+    std::vector<real> tmp((size_t)b->n_env*f.width);
+    if (to_device) std::copy(host, host + tmp.size(), tmp.begin());
+    HIPCHK(to_device ? hipMemcpy2D(dev, pitch, tmp.data(), row, row, b->n_env, hipMemcpyHostToDevice)
+                     : hipMemcpy2D(tmp.data(), row, dev, pitch, row, b->n_env, hipMemcpyDeviceToHost));
+    if (!to_device) std::copy(tmp.begin(), tmp.end(), host);
+    return 0;
+  });
 }
 
 extern "C" int fb_batch_get(fb_batch* b, int field, void* dst, size_t bytes) {
@@ -1586,39 +1608,33 @@ extern "C" int fb_batch_get(fb_batch* b, int field, void* dst, size_t bytes) {
   if (field == FB_CONTACT) {
     // [n_env][64][8]: dist, pos3, normal3, pair id  (FP64)
     if (bytes != (size_t)n*FB_MAXCON_*8*sizeof(double)) return fail("fb_batch_get: size mismatch");
-    size_t rs = b->precision == 64 ? 8 : 4;
-    std::vector<char> rr((size_t)n*b->off.nreal*rs);
-    std::vector<int> ii((size_t)n*b->off.nint);
-    HIPCHK(hipMemcpy(rr.data(), b->rarena, rr.size(), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(ii.data(), b->iarena, ii.size()*sizeof(int), hipMemcpyDeviceToHost));
-    double* out = (double*)dst;
-    auto rd = [&](size_t env, size_t off) { return rs == 8 ? ((double*)rr.data())[env*b->off.nreal + off] : (double)((float*)rr.data())[env*b->off.nreal + off]; };
-    for (int e = 0; e < n; e++) for (int c = 0; c < FB_MAXCON_; c++) {
-      double* o = out + ((size_t)e*FB_MAXCON_ + c)*8;
-      o[0] = rd(e, b->off.con_dist + c);
-      for (int k = 0; k < 3; k++) { o[1+k] = rd(e, b->off.con_pos + 3*c + k); o[4+k] = rd(e, b->off.con_frame + 9*c + k); }
-      o[7] = ii[(size_t)e*b->off.nint + b->off.con_pair + c];
-    }
-    return 0;
+    return with_model(b, [&](auto& M) {
+      std::vector<decltype(M.timestep)> rr((size_t)n*b->off.nreal);
+      std::vector<int> ii((size_t)n*b->off.nint);
+      HIPCHK(hipMemcpy(rr.data(), b->rarena, rr.size()*sizeof(rr[0]), hipMemcpyDeviceToHost));
+      HIPCHK(hipMemcpy(ii.data(), b->iarena, ii.size()*sizeof(int), hipMemcpyDeviceToHost));
+      double* out = (double*)dst;
+      for (int e = 0; e < n; e++) for (int c = 0; c < FB_MAXCON_; c++) {
+        double* o = out + ((size_t)e*FB_MAXCON_ + c)*8;
+        const auto* r = rr.data() + (size_t)e*b->off.nreal;
+        o[0] = r[b->off.con_dist + c];
+        for (int k = 0; k < 3; k++) { o[1+k] = r[b->off.con_pos + 3*c + k]; o[4+k] = r[b->off.con_frame + 9*c + k]; }
+        o[7] = ii[(size_t)e*b->off.nint + b->off.con_pair + c];
+      }
+      return 0;
+    });
   }
   FieldDesc f;
   if (field_desc(b, field, &f)) return -1;
-  if (f.kind == 0) {
+  if (f.kind == REAL_ARENA) {
     if (bytes != (size_t)n*f.width*sizeof(double)) return fail("fb_batch_get: size mismatch (physics fields are returned as FP64)");
-    size_t rs = b->precision == 64 ? 8 : 4;
-    std::vector<char> tmp((size_t)n*f.width*rs);
-    HIPCHK(hipMemcpy2D(tmp.data(), f.width*rs, (char*)b->rarena + f.off*rs, (size_t)b->off.nreal*rs, f.width*rs, n, hipMemcpyDeviceToHost));
-    double* out = (double*)dst;
-    if (rs == 8) memcpy(out, tmp.data(), tmp.size());
-    else for (size_t k = 0; k < (size_t)n*f.width; k++) out[k] = ((float*)tmp.data())[k];
-  } else if (f.kind == 1) {
+    return real_rows(b, f, (double*)dst, false);
+  } else if (f.kind == INT_ARENA) {
     if (bytes != (size_t)n*f.width*sizeof(int)) return fail("fb_batch_get: size mismatch");
     HIPCHK(hipMemcpy2D(dst, f.width*4, (char*)b->iarena + f.off*4, (size_t)b->off.nint*4, f.width*4, n, hipMemcpyDeviceToHost));
   } else {
-    if (!f.base) return fail(field == FB_IK_ERR || field == FB_IK_STEPS ? "fb_batch_get: field not allocated yet (run fb_batch_ik first)"
-                             : field == FB_QFRC_INVERSE || field == FB_CONTACT_FORCE ? "fb_batch_get: field not allocated yet (run fb_batch_inverse first)"
-                                                                         : "fb_batch_get: field not allocated yet (set a reference first)");
-    if (bytes != (size_t)n*f.width*(f.kind == 4 ? 8 : 4)) return fail("fb_batch_get: size mismatch");
+    if (!f.base) return fail(f.unset);
+    if (bytes != (size_t)n*f.width*(f.kind == F64_ARRAY ? 8 : 4)) return fail("fb_batch_get: size mismatch");
     HIPCHK(hipMemcpy(dst, f.base, bytes, hipMemcpyDeviceToHost));
   }
   return 0;
@@ -1631,15 +1647,10 @@ extern "C" int fb_batch_set(fb_batch* b, int field, const void* src, size_t byte
   FieldDesc f;
   if (field_desc(b, field, &f)) return -1;
   int n = b->n_env;
-  if (f.kind == 0) {
+  if (f.kind == REAL_ARENA) {
     if (bytes != (size_t)n*f.width*sizeof(double)) return fail("fb_batch_set: size mismatch (physics fields are passed as FP64)");
-    size_t rs = b->precision == 64 ? 8 : 4;
-    std::vector<char> tmp((size_t)n*f.width*rs);
-    const double* in = (const double*)src;
-    if (rs == 8) memcpy(tmp.data(), in, tmp.size());
-    else for (size_t k = 0; k < (size_t)n*f.width; k++) ((float*)tmp.data())[k] = (float)in[k];
-    HIPCHK(hipMemcpy2D((char*)b->rarena + f.off*rs, (size_t)b->off.nreal*rs, tmp.data(), f.width*rs, f.width*rs, n, hipMemcpyHostToDevice));
-  } else if (f.kind == 1) {
+    return real_rows(b, f, (double*)src, true);
+  } else if (f.kind == INT_ARENA) {
     if (bytes != (size_t)n*f.width*sizeof(int)) return fail("fb_batch_set: size mismatch");
     HIPCHK(hipMemcpy2D((char*)b->iarena + f.off*4, (size_t)b->off.nint*4, src, f.width*4, f.width*4, n, hipMemcpyHostToDevice));
   } else return fail("fb_batch_set: field is read-only");
@@ -1659,7 +1670,7 @@ extern "C" void* fb_batch_device_ptr(fb_batch* b, int field) {
 
 extern "C" int fb_batch_row(fb_batch* b, int which, int env, void* host, size_t bytes, int write, size_t* row_bytes) {
   if (!b || which < 0 || which > 1 || env < 0 || env >= b->n_env) return fail("fb_batch_row: bad argument");
-  const size_t rs = which == 0 ? (b->precision == 64 ? 8 : 4) : 4;
+  const size_t rs = which == 0 ? real_size(b) : 4;
   const size_t rb = (which == 0 ? (size_t)b->off.nreal : (size_t)b->off.nint)*rs;
   if (row_bytes) *row_bytes = rb;
   if (bytes == 0) return 0;

@@ -7,6 +7,7 @@ tests/_emu; nothing in the package does that.)
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
 import os
 from typing import Dict, Optional
@@ -25,17 +26,23 @@ HIP_LIB = os.path.join(_HERE, 'libflybody_hip.so')
 HIP_LIB_DENSE = os.path.join(_HERE, 'libflybody_hip_dense.so')
 ASSETS = os.path.join(_HERE, 'assets')
 
-# field ids (include/flybody_engine.h)
-FIELDS = dict(QPOS=0, QVEL=1, ACT=2, CTRL=3, QACC=4, XPOS=5, XQUAT=6, SENSORDATA=7, OBS=8, REWARD=9,
-              DISCOUNT=10, STEP_TYPE=11, NCON=12, NEFC=13, SOLVER_NITER=14, QFRC_BIAS=15, QFRC_PASSIVE=16,
-              QACC_SMOOTH=17, QM=18, CONTACT=19, EFC_FORCE=20, QFRC_ACTUATOR=21, QFRC_CONSTRAINT=22,
-              STEP_COUNT=23, SUBTREE_COM=24, PROF=25, REWARD_FACTORS=26, GEOM_XPOS=27, GEOM_XMAT=28, CVEL=29, STEP_TICKS=30, LAUNCH_ORDER=31, WARN=32, WARN_EVER=33, SIZE_STATS=34,
-              SITE_XPOS=35, IK_ERR=36, IK_STEPS=37, QFRC_INVERSE=38, CONTACT_FORCE=39)
-_INT_FIELDS = {'STEP_TYPE', 'NCON', 'NEFC', 'SOLVER_NITER', 'STEP_COUNT', 'PROF', 'STEP_TICKS', 'LAUNCH_ORDER', 'WARN', 'WARN_EVER', 'SIZE_STATS', 'IK_STEPS'}
+MAXCON, MAXEFC, NSENSOR = 64, 192, 33
+# fields (include/flybody_engine.h): name -> (id, dtype, width of an environment's row).  A width is a number, a model dimension
+# (Model.dim; 'nobs': Batch.nobs) or a (factor, dimension) pair.  fb_batch_get returns physics fields as FP64 at either precision.
+_F64, _F32, _I32 = np.float64, np.float32, np.int32
+FIELDS = dict(
+    QPOS=(0, _F64, 'nq'), QVEL=(1, _F64, 'nv'), ACT=(2, _F64, 'na'), CTRL=(3, _F64, 'nu'), QACC=(4, _F64, 'nv'),
+    XPOS=(5, _F64, (3, 'nbody')), XQUAT=(6, _F64, (4, 'nbody')), SENSORDATA=(7, _F64, NSENSOR), OBS=(8, _F32, 'nobs'),
+    REWARD=(9, _F32, 1), DISCOUNT=(10, _F32, 1), STEP_TYPE=(11, _I32, 1), NCON=(12, _I32, 1), NEFC=(13, _I32, 1),
+    SOLVER_NITER=(14, _I32, 1), QFRC_BIAS=(15, _F64, 'nv'), QFRC_PASSIVE=(16, _F64, 'nv'), QACC_SMOOTH=(17, _F64, 'nv'),
+    QM=(18, _F64, 'nM'), CONTACT=(19, _F64, MAXCON*8), EFC_FORCE=(20, _F64, MAXEFC), QFRC_ACTUATOR=(21, _F64, 'nv'),
+    QFRC_CONSTRAINT=(22, _F64, 'nv'), STEP_COUNT=(23, _I32, 1), SUBTREE_COM=(24, _F64, 3), PROF=(25, _I32, 112),
+    REWARD_FACTORS=(26, _F64, 5), GEOM_XPOS=(27, _F64, (3, 'ngeom')), GEOM_XMAT=(28, _F64, (9, 'ngeom')), CVEL=(29, _F64, (6, 'nbody')),
+    STEP_TICKS=(30, _I32, 1), LAUNCH_ORDER=(31, _I32, 1), WARN=(32, _I32, 1), WARN_EVER=(33, _I32, 1), SIZE_STATS=(34, _I32, 4),
+    SITE_XPOS=(35, _F64, (3, 'nsite')), IK_ERR=(36, _F64, 2), IK_STEPS=(37, _I32, 2), QFRC_INVERSE=(38, _F64, 'nv'),
+    CONTACT_FORCE=(39, _F64, 3*MAXCON))
 # bits of WARN / WARN_EVER (include/flybody_engine.h): the caps MuJoCo reports as nconmax / njmax warnings, and iteration limits
 WARN_BITS = dict(CONTACT_CAP=1, EFC_CAP=2, SOLVER_MAXITER=4, CCD_MAXITER=8, SCHED_WAIT=16, SOLVER_FALLBACK=32)
-_F32_FIELDS = {'OBS', 'REWARD', 'DISCOUNT'}
-MAXCON, MAXEFC, NSENSOR = 64, 192, 33
 
 # fb_step.hpp stage ids (ST_*) and the stage sequence of one control step as d_run walks it (profiling: fb_batch_stage)
 ST = dict(ACT=0, ACC_PRE=1, SOLVE=2, ACC_SOLVE=3, ACC_POST=4, CONSTR_A=5, CONSTR_B=6, SENS=7, EULER_PRE=8, FACTOR=9, EULER_SOLVE=10,
@@ -139,6 +146,22 @@ def _check(L, rc):
         raise EngineError(L.fb_last_error().decode())
 
 
+def observation_layout(model: 'Model', future_steps: int, ball: bool = False):
+    """({observable: (offset, size, shape)}, width) of the packed observation vector (fb_step.hpp writes it).  The buffer is in
+    sorted-key order (tasks/task_utils.py:12); walk_on_ball (ball=True) has no reference observables, its ball's velocity instead."""
+    na, napp, nforce, nobsj, ntouch = (model.dim(k) for k in ('na', 'napp', 'nforce', 'nobsjnt', 'ntouch'))
+    nf = 0 if ball else future_steps + 1
+    sizes = collections.OrderedDict([
+        ('accelerometer', (3,)), ('actuator_activation', (na,)), ('appendages_pos', (3*napp,)), ('ball_qvel', (3 if ball else 0,)),
+        ('force', (3*nforce,)),
+        ('gyro', (3,)), ('joints_pos', (nobsj,)), ('joints_vel', (nobsj,)), ('ref_displacement', (nf, 3)),
+        ('ref_root_quat', (nf, 4)), ('touch', (ntouch,)), ('velocimeter', (3,)), ('world_zaxis', (3,))])
+    layout = collections.OrderedDict(); off = 0
+    for k, shp in sizes.items():
+        n = int(np.prod(shp)); layout[k] = (off, n, shp); off += n
+    return layout, off
+
+
 class _IKConfig(C.Structure):
     """fb_ik_config (include/flybody_engine.h)."""
     _fields_ = [('n_site', C.c_int32), ('n_joint', C.c_int32), ('site_ids', C.c_void_p), ('joint_ids', C.c_void_p), ('include', C.c_void_p),
@@ -187,9 +210,7 @@ class Batch:
         assert rq.ndim == 2 and rq.shape[1] == 7 and rv.shape == (rq.shape[0], 6)
         _check(self.L, self.L.fb_batch_set_reference(self.h, rq.ctypes.data, rv.ctypes.data, rq.shape[0],
                                                      int(future_steps), float(terminal_com_dist), float(time_limit)))
-        m = self.model
-        self.nobs = (3 + m.dim('na') + 3*m.dim('napp') + 3*m.dim('nforce') + 3 + 2*m.dim('nobsjnt') +
-                     7*(future_steps + 1) + m.dim('ntouch') + 3 + 3)
+        self.nobs = observation_layout(self.model, future_steps)[1]
 
     def set_walk_dataset(self, ds, joint_ids, site_ids, select=None, future_steps=64, terminal_com_dist=0.3, time_limit=10.0,
                          seed: int = 0, env_id_base: int = 0):
@@ -208,9 +229,7 @@ class Batch:
         d = _DS(ds.n_traj, len(keep[5]), len(keep[6]), len(sel), *(a.ctypes.data for a in keep), int(future_steps), float(terminal_com_dist),
                 float(time_limit), int(seed), int(env_id_base))
         _check(self.L, self.L.fb_batch_set_walk_dataset(self.h, C.byref(d)))
-        m = self.model
-        self.nobs = (3 + m.dim('na') + 3*m.dim('napp') + 3*m.dim('nforce') + 3 + 2*m.dim('nobsjnt') +
-                     7*(future_steps + 1) + m.dim('ntouch') + 3 + 3)
+        self.nobs = observation_layout(self.model, future_steps)[1]
 
     def set_flight_dataset(self, offsets, root_qpos, qvel, select=None, future_steps=5, terminal_com_dist=2.0, time_limit=0.6,
                            randomize_start_step=True, seed: int = 0, env_id_base: int = 0):
@@ -226,15 +245,12 @@ class Batch:
         d = _FD(n_traj, len(sel), keep[0].ctypes.data, keep[1].ctypes.data, keep[2].ctypes.data, sel.ctypes.data, int(future_steps),
                 int(bool(randomize_start_step)), float(terminal_com_dist), float(time_limit), int(seed), int(env_id_base))
         _check(self.L, self.L.fb_batch_set_flight_dataset(self.h, C.byref(d)))
-        m = self.model
-        self.nobs = (3 + m.dim('na') + 3*m.dim('napp') + 3*m.dim('nforce') + 3 + 2*m.dim('nobsjnt') +
-                     7*(future_steps + 1) + m.dim('ntouch') + 3 + 3)
+        self.nobs = observation_layout(self.model, future_steps)[1]
 
     def set_time_limit(self, time_limit: float = 2.0):
         """walk_on_ball: no reference trajectory, only the episode time limit."""
         _check(self.L, self.L.fb_batch_set_time_limit(self.h, float(time_limit)))
-        m = self.model
-        self.nobs = 3 + m.dim('na') + 3*m.dim('napp') + 3 + 3*m.dim('nforce') + 3 + 2*m.dim('nobsjnt') + m.dim('ntouch') + 3 + 3
+        self.nobs = observation_layout(self.model, 0, ball=True)[1]
 
     def set_wbpg(self, tables, seed: int = 0):
         t = np.ascontiguousarray(tables['traj'], np.float64); p = np.ascontiguousarray(tables['phase'], np.float64)
@@ -306,32 +322,27 @@ class Batch:
         _check(self.L, self.L.fb_batch_row(self.h, which, env, buf.ctypes.data, n.value, 0, None))
         return buf
 
-    def _width(self, name):
-        m = self.model
-        return dict(QPOS=m.dim('nq'), QVEL=m.dim('nv'), ACT=m.dim('na'), CTRL=m.dim('nu'), QACC=m.dim('nv'),
-                    XPOS=3*m.dim('nbody'), XQUAT=4*m.dim('nbody'), SENSORDATA=NSENSOR, OBS=self.nobs, REWARD=1,
-                    DISCOUNT=1, STEP_TYPE=1, NCON=1, NEFC=1, SOLVER_NITER=1, QFRC_BIAS=m.dim('nv'),
-                    QFRC_PASSIVE=m.dim('nv'), QACC_SMOOTH=m.dim('nv'), QM=m.dim('nM'), CONTACT=MAXCON*8,
-                    EFC_FORCE=MAXEFC, QFRC_ACTUATOR=m.dim('nv'), QFRC_CONSTRAINT=m.dim('nv'), STEP_COUNT=1,
-                    SUBTREE_COM=3, PROF=112, REWARD_FACTORS=5, GEOM_XPOS=3*m.dim('ngeom'),
-                    GEOM_XMAT=9*m.dim('ngeom'), CVEL=6*m.dim('nbody'), STEP_TICKS=1, LAUNCH_ORDER=1, WARN=1, WARN_EVER=1, SIZE_STATS=4,
-                    SITE_XPOS=3*m.dim('nsite'), IK_ERR=2, IK_STEPS=2, QFRC_INVERSE=m.dim('nv'), CONTACT_FORCE=3*MAXCON)[name]
+    def _field(self, name):
+        """(id, dtype, width) of a field of this batch (FIELDS)."""
+        fid, dt, w = FIELDS[name]
+        k, dim = w if isinstance(w, tuple) else (1, w)
+        if isinstance(dim, str):
+            dim = self.nobs if dim == 'nobs' else self.model.dim(dim)
+        return fid, dt, k*dim
 
     def get(self, name: str) -> np.ndarray:
-        w = self._width(name)
-        dt = np.int32 if name in _INT_FIELDS else (np.float32 if name in _F32_FIELDS else np.float64)
+        fid, dt, w = self._field(name)
         out = np.zeros((self.n_env, w), dt)
-        _check(self.L, self.L.fb_batch_get(self.h, FIELDS[name], out.ctypes.data, out.nbytes))
+        _check(self.L, self.L.fb_batch_get(self.h, fid, out.ctypes.data, out.nbytes))
         return out
 
     def set(self, name: str, value):
-        w = self._width(name)
-        dt = np.int32 if name in _INT_FIELDS else np.float64
+        fid, dt, w = self._field(name)
         v = np.ascontiguousarray(np.broadcast_to(np.asarray(value, dt), (self.n_env, w)))
-        _check(self.L, self.L.fb_batch_set(self.h, FIELDS[name], v.ctypes.data, v.nbytes))
+        _check(self.L, self.L.fb_batch_set(self.h, fid, v.ctypes.data, v.nbytes))
 
     def device_ptr(self, name: str) -> int:
-        p = self.L.fb_batch_device_ptr(self.h, FIELDS[name])
+        p = self.L.fb_batch_device_ptr(self.h, FIELDS[name][0])
         if not p:
             raise EngineError(f'no device pointer for {name}')
         return p

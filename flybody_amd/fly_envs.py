@@ -20,6 +20,7 @@ from typing import Optional, Sequence
 import numpy as np
 
 from . import engine
+from .engine import observation_layout
 from .reference import constant_speed_trajectory, default_walking_reference
 
 
@@ -48,25 +49,11 @@ class BoundedArray(Array):
         self.minimum = np.asarray(minimum, dtype); self.maximum = np.asarray(maximum, dtype)
 
 
-# observation layout: packed buffer is in sorted-key order (tasks/task_utils.py:12); the dict the
+# observation layout (engine.observation_layout): the packed buffer is in sorted-key order (tasks/task_utils.py:12); the dict the
 # reference returns lists the walker observables first and the two task observables last
 # (tests/test_walking_env.py:11-23)
 _DICT_ORDER = ['accelerometer', 'actuator_activation', 'appendages_pos', 'force', 'gyro', 'joints_pos', 'joints_vel',
                'touch', 'velocimeter', 'world_zaxis', 'ref_displacement', 'ref_root_quat', 'ball_qvel']
-
-
-def observation_layout(model: engine.Model, future_steps: int, ball: bool = False):
-    na, napp, nforce, nobsj, ntouch = (model.dim(k) for k in ('na', 'napp', 'nforce', 'nobsjnt', 'ntouch'))
-    nf = 0 if ball else future_steps + 1                      # walk_on_ball: no reference observables, ball_qvel instead
-    sizes = collections.OrderedDict([
-        ('accelerometer', (3,)), ('actuator_activation', (na,)), ('appendages_pos', (3*napp,)), ('ball_qvel', (3 if ball else 0,)),
-        ('force', (3*nforce,)),
-        ('gyro', (3,)), ('joints_pos', (nobsj,)), ('joints_vel', (nobsj,)), ('ref_displacement', (nf, 3)),
-        ('ref_root_quat', (nf, 4)), ('touch', (ntouch,)), ('velocimeter', (3,)), ('world_zaxis', (3,))])
-    layout = collections.OrderedDict(); off = 0
-    for k, shp in sizes.items():
-        n = int(np.prod(shp)); layout[k] = (off, n, shp); off += n
-    return layout, off
 
 
 def action_spec_from_arrays(a) -> BoundedArray:

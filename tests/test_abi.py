@@ -104,3 +104,14 @@ def test_no_cpu_fallback(walk_arrays):
             if f.endswith('.py'):
                 src = open(os.path.join(root, f)).read()
                 assert 'from oracle' not in src and 'import oracle' not in src and 'libflybody_emu' not in src, f
+
+
+def test_python_field_table_matches_header():
+    """engine.FIELDS names every field of the header's field enum (FB_QPOS ... ) with the header's id, and no other."""
+    from flybody_amd import engine
+    hdr = open(os.path.join(ROOT, 'include', 'flybody_engine.h')).read()
+    hdr = re.sub(r'/\*.*?\*/', '', hdr, flags=re.S)
+    block = next(b for b in re.findall(r'enum\s*\{(.*?)\}', hdr, flags=re.S) if 'FB_QPOS' in b)
+    ids = {name: int(v) for name, v in re.findall(r'\bFB_([A-Z0-9_]+)\s*=\s*(\d+)', block)}
+    assert len(ids) >= 40 and ids['QPOS'] == 0 and ids['CONTACT_FORCE'] == 39
+    assert {name: f[0] for name, f in engine.FIELDS.items()} == ids
