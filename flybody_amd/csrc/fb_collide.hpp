@@ -14,14 +14,10 @@
 template <typename real>
 struct CGeom { real pos[3], mat[9], size[3]; int type; real margin; };     // by value: pointers to the caller's arrays pin those arrays in scratch memory
 
-#ifndef FB_SUPPORT_SELECT
-#define FB_SUPPORT_SELECT 1
-#endif
 template <typename real>
 FBD void support(const CGeom<real>& g, const real* dir, real* out) {
   real l[3], p[3];
   mulmatT3(l, g.mat, dir);
-#if FB_SUPPORT_SELECT
   // Round 5: all four shapes by SELECTS.  The lanes of a narrow-phase pass hold different geom types, so a branch per type made the
   // wave run every branch anyway -- plus a saveexec / branch / restore around each, twice per support pair and ~25 times per pass.
   // Same arithmetic per shape (the unused shapes' square roots are computed and dropped).
@@ -37,23 +33,6 @@ FBD void support(const CGeom<real>& g, const real* dir, real* out) {
   if (cyl) { px = nc < FB_MINV ? (real)0 : g.size[0]*l[0]*nic; py = nc < FB_MINV ? (real)0 : g.size[0]*l[1]*nic; pz = hz; }
   if (!(caps || ell || cyl || sph)) { px = 0; py = 0; pz = 0; }
   p[0] = px; p[1] = py; p[2] = pz;
-#else
-  if (g.type == GEOM_SPHERE) { scl3(p, l, g.size[0]); }
-  else if (g.type == GEOM_CAPSULE) {
-    scl3(p, l, g.size[0]);
-    p[2] += (l[2] >= 0 ? g.size[1] : -g.size[1]);
-  } else if (g.type == GEOM_ELLIPSOID) {
-    real s[3] = {g.size[0]*l[0], g.size[1]*l[1], g.size[2]*l[2]};
-    real n = norm3(s);
-    if (n < FB_MINV) { p[0] = g.size[0]; p[1] = 0; p[2] = 0; }
-    else { real ni = fb_inv(n); p[0] = g.size[0]*s[0]*ni; p[1] = g.size[1]*s[1]*ni; p[2] = g.size[2]*s[2]*ni; }
-  } else if (g.type == GEOM_CYLINDER) {
-    real n = fb_sqrt(l[0]*l[0] + l[1]*l[1]);
-    if (n < FB_MINV) { p[0] = 0; p[1] = 0; }
-    else { real ni = fb_inv(n); p[0] = g.size[0]*l[0]*ni; p[1] = g.size[0]*l[1]*ni; }
-    p[2] = (l[2] >= 0 ? g.size[1] : -g.size[1]);
-  } else { p[0] = p[1] = p[2] = 0; }
-#endif
   addscl3(p, l, (real)0.5*g.margin);
   mulmat3(out, g.mat, p);
   add3(out, out, g.pos);
@@ -73,13 +52,11 @@ FBD void support(const CGeom<real>& g, const real* dir, real* out) {
 //     maps are ~2/3 of an iteration's arithmetic: the instructions a wave issues per pass drop by about a third, the mean number of
 //     enabled lanes doubles, and the per-lane state shrinks by one shape (15 reals) and one witness array (12 reals) -- the 168-register
 //     budget no longer spills the portal (d_collision hands the convex pairs of a pass out to lane pairs).
-#ifndef FB_MPR_PAIRED
 #ifdef FB_EMULATE
 #define FB_MPR_PAIRED 0            // (the fibers of the host emulation exchange values at wave-uniform yield points only: the pair exchange sits inside the
                                    //  divergent refinement loops, so the emulation build runs the one-lane policy -- same portal code, same arithmetic)
 #else
 #define FB_MPR_PAIRED 1
-#endif
 #endif
 template <typename real, int NW> struct MprPt { real v[3], w[NW][3]; };
 template <typename real, int NW> struct Portal { real v[4][3], w[NW][4][3]; };
@@ -547,6 +524,9 @@ FB_STAGE_B int narrow_phase(const DevModel<real>& M_, const WS<real>& w_, int p,
 }
 
 #if FB_MPR_PAIRED
+// the paired pass's LDS area inside the factor's row (d_collision): 6 nv reals, the lanes' first contacts (7 x FB_WAVE reals), then the jobs
+// of one trip (2 x 32 ints, each at most one real wide)
+static_assert(6*FB_MAXNV + 7*FB_WAVE + 2*32 <= FB_LDS_SCRATCH, "the paired-MPR jobs area must fit in the LDS row of the factor");
 // One side of a convex pair (lane pair 2j, 2j+1: shape A on the even lane, B on the odd one).  Both lanes compute the same depth, normal
 // and position; the even lane stores the contact in the LDS slot of the lane that owns the candidate.  Returns contacts | cap << 8.
 template <typename real>
@@ -615,9 +595,7 @@ __device__ __forceinline__ void d_collision(const DevModel<real>& M, const WS<re
   // jumped fails the displacement test like one that drifted.  A list that would not fit FB_VLMAX pairs is not kept.
   // A list that does not survive ONE substep (flight: the wings move by more than the slack every substep) is not worth building: after such a
   // rebuild the next FB_VL_BACKOFF substeps run the plain loop without list construction.
-#ifndef FB_VL_BACKOFF
 #define FB_VL_BACKOFF 15
-#endif
   bool use_list = false;
   int nlist = 0, okf = 0;
   const int vskip = (vld > 0) ? uniform_int(w.istate()[IS_VL_SKIP]) : 0;

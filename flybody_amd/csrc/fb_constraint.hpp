@@ -12,17 +12,10 @@
 #include "fb_smooth.hpp"
 #include "fb_newton.hpp"
 
-#ifndef FB_J_ROWMAJOR
-#define FB_J_ROWMAJOR 1
-#endif
-#if FB_J_ROWMAJOR
 // row-major (round 5): the 2 x FB_MAXCH chain entries of a constraint row are contiguous (320 B in FP64), so the ~12 rows of a typical system
 // occupy ~4 KB of the environment's row instead of 40 x 2 pieces of 96 B at a stride of 1536 B -- and J^T f, which walks the rows
 // one by one with lane == dof, reads two cache lines per row instead of one per lane
 #define JIDX(side, s, r) (((r)*2 + (side))*FB_MAXCH + (s))
-#else
-#define JIDX(side, s, r) (((side)*FB_MAXCH + (s))*FB_MAXEFC_ + (r))
-#endif
 #define MINIMP ((real)0.0001)
 #define MAXIMP ((real)0.9999)
 
@@ -216,22 +209,17 @@ FBD void project_row(const DevModel<real>& M, const WS<real>& w, int side, int r
   // L[chain[s], chain[t]] lives in row chain[s] (depth s) at offset s - t.  The bound is the wave-uniform longest chain: a slot beyond
   // the lane's own chain carries y[s] = 0 and reads a trunk row (chain[] is padded with dof 0: finite factor entries), so it subtracts
   // exact zeros -- cheaper than an exec-mask round trip per slot for the lane-varying `s < len`
-  // (Round 6, FB_PROJ_STRAIGHT 1: no bound at all -- by the argument above a slot beyond the longest chain is as harmless as one beyond the lane's own,
-  //  and the fruit fly's longest chain IS FB_MAXCH -- makes the triangular solve ONE basic block.  Measured -0.6 % env-steps/s
-  //  (profiles/r6/ab_factor_straight.txt): left off.)
-#ifndef FB_PROJ_STRAIGHT
-#define FB_PROJ_STRAIGHT 0
-#endif
+  // (Round 6: dropping the bound as well -- one basic block for the whole triangular solve -- measured -0.6 % env-steps/s,
+  //  profiles/r6/ab_factor_straight.txt.)
   const int chmax = M.chmax;
 #pragma unroll
   for (int s = FB_MAXCH - 1; s >= 1; s--) {
-    if (FB_PROJ_STRAIGHT || s < chmax) {
+    if (s < chmax) {
       const FB_LDS real* row = w.lLD + rowadr[s];
 #pragma unroll
       for (int t = 0; t < s; t++) y[t] -= row[-t] * y[s];
     }
   }
-  (void)chmax;
 #pragma unroll
   for (int s = 0; s < FB_MAXCH; s++) y[s] = (s < len) ? y[s]*sd[chain[s]] : (real)0;
 }
@@ -242,9 +230,6 @@ FBD void project_row(const DevModel<real>& M, const WS<real>& w, int side, int r
 // are common to any two chains by construction: their contribution is (yA + yB)_r (yA + yB)_c, ONE v_readlane pair and ONE multiply-add
 // per slot and row instead of two pairs and four products each behind a lane-varying prefix test (~20 instructions per slot and row;
 // the masked form remains for the slots below the trunk, and for models without a trunk -- a forest of dof trees: TRUNK = 0).
-#ifndef FB_AR_TRUNK
-#define FB_AR_TRUNK 1
-#endif
 template <int TRUNK, typename real, typename ARP>
 FBD void ar_from_registers_t(const DevModel<real>& M, const WS<real>& w, ARP AR, int nefc, int lane, const real* yA, const real* yB, int bA, int bB, int lA, int lB) {
   const bool valid = lane < nefc;
@@ -290,10 +275,8 @@ FBD void ar_from_registers_t(const DevModel<real>& M, const WS<real>& w, ARP AR,
 }
 template <typename real, typename ARP>
 FBD void ar_from_registers(const DevModel<real>& M, const WS<real>& w, ARP AR, int nefc, int lane, const real* yA, const real* yB, int bA, int bB, int lA, int lB) {
-#if FB_AR_TRUNK
   if (uniform_int(M.ntrunk) == FB_MAXTRUNK) ar_from_registers_t<FB_MAXTRUNK>(M, w, AR, nefc, lane, yA, yB, bA, bB, lA, lB);
   else
-#endif
   ar_from_registers_t<0>(M, w, AR, nefc, lane, yA, yB, bA, bB, lA, lB);
 }
 
@@ -607,11 +590,6 @@ template <bool S, typename real, typename ARP> FBD void res_axpy3(R3<double>& re
   }
 }
 
-#ifdef FB_PGS_NOINLINE
-#define FB_PGS_ATTR __device__ FB_NOINLINE
-#else
-#define FB_PGS_ATTR FB_STAGE_A
-#endif
 // PGS + noslip sweeps; ARP is an LDS (address_space(3)) or a global pointer to the Delassus matrix.
 // Residual-maintaining Gauss-Seidel: the vector res = b + AR f lives in registers (lane k owns rows k, k+64,
 // k+128); a row update reads its residual with v_readlane and, if the force changed by delta, adds
@@ -619,7 +597,7 @@ template <bool S, typename real, typename ARP> FBD void res_axpy3(R3<double>& re
 // critical path.  Mathematically identical to recomputing each row's dot product.
 // `sweeps` false: the forces in efc_force are final (the Newton solver produced them) and only the noslip passes run.
 template <typename real, typename ARP, bool S>
-FB_PGS_ATTR int d_pgs(const DevModel<real>& M, const WS<real>& w, ARP AR, int nefc, int lane, bool sweeps = true) {
+FB_STAGE_A int d_pgs(const DevModel<real>& M, const WS<real>& w, ARP AR, int nefc, int lane, bool sweeps = true) {
   int nv = M.nv;
   PROF_BEGIN();
   R3<real> f, rb, rR, rfr0, rfr1, rla, rdiag;
@@ -709,7 +687,6 @@ FB_PGS_ATTR int d_pgs(const DevModel<real>& M, const WS<real>& w, ARP AR, int ne
   const int max_it = sweeps ? M.iterations : 0, max_noslip = M.noslip_iterations;
   const real tol_scaled = M.tolerance, noslip_tol = M.noslip_tolerance;
   int niter = 0;
-#ifndef FB_PGS_BRANCHY
   if (S) {
   // ---- branch-lean sweep for systems of <= 64 rows (every row lives in lane == row).
   // Measured on MI355X (tools/microbench/lat.hip, one wave): a dependent FP64 FMA costs ~6 cycles, but a wave-uniform branch
@@ -831,9 +808,7 @@ FB_PGS_ATTR int d_pgs(const DevModel<real>& M, const WS<real>& w, ARP AR, int ne
     if (improvement*scale < tol_scaled) break;
     if (it == 0) FB_SETPRIO(3);
   }
-  } else
-#endif
-  {
+  } else {
     for (int it = 0; it < max_it; it++) {
       real improvement = 0;
       for (int i = 0; i < nefc;) {
@@ -1096,12 +1071,8 @@ __device__ __forceinline__ bool d_constraint_a(const DevModel<real>& M, const WS
     if (newton) {
       const WS<real> wc = w;               // (the callee is not inlined: hand it a copy, the caller's descriptor stays in registers)
       // (two instantiations by system size: <= FB_NEWTON_NT rows -- 93 % of the solves -- runs the register-tile code alone, the rest the
-      //  lane == row code alone; FB_NW_SPLIT = 0: one function that decides at run time)
-#if FB_NW_SPLIT
+      //  lane == row code alone)
       constexpr int MT = 1, MR = 2;
-#else
-      constexpr int MT = 0, MR = 0;
-#endif
       if (k_in_slot && nefc <= FB_NEWTON_NT) niter = d_newton<real, const FB_LDS real*, FB_LDS real*, MT>(M, wc, arp, w.lAR() + tri, nefc, lane);
       else if (k_in_slot) niter = d_newton<real, const FB_LDS real*, FB_LDS real*, MR>(M, wc, arp, w.lAR() + tri, nefc, lane);
       else if (!wide) niter = d_newton<real, const FB_LDS real*, FB_LDS real*, MR>(M, wc, arp, w.lLD, nefc, lane);
@@ -1120,11 +1091,7 @@ __device__ __forceinline__ bool d_constraint_a(const DevModel<real>& M, const WS
   else if (nefc <= 64) {
     if (newton) {
       const WS<real> wc = w;
-#if FB_NW_SPLIT
       niter = d_newton<real, const real*, real*, 2>(M, wc, (const real*)w.AR(), w.AR() + tri, nefc, lane);       // (beyond the LDS slot: > 16 rows)
-#else
-      niter = d_newton<real, const real*, real*>(M, wc, (const real*)w.AR(), w.AR() + tri, nefc, lane);
-#endif
       SYNC();
     }
     if (!newton || M.noslip_iterations > 0) { const int it2 = d_pgs<real, const real*, true>(M, w, (const real*)w.AR(), nefc, lane, !newton); if (!newton) niter = it2; }

@@ -542,15 +542,6 @@ struct Batch {
 #ifndef FB_TICKET_SPLIT
 #define FB_TICKET_SPLIT 0                 // final substeps of a control step handed out as two half tickets (0: whole substeps only; measured: profiles/r6/ab_tickets.txt)
 #endif
-#ifndef FB_HEAVY_PRIO_ROWS
-#define FB_HEAVY_PRIO_ROWS 0              // constraint rows (previous substep) from which a ticket runs at issue priority FB_HEAVY_PRIO (0: off)
-#endif
-#ifndef FB_HEAVY_PRIO
-#define FB_HEAVY_PRIO 2
-#endif
-#ifndef FB_TICKET_ORDER
-#define FB_TICKET_ORDER 1                 // hand an XCD's environments out by decreasing size of their last constraint system (k_ticket_order)
-#endif
 #ifndef FB_SCHED_SPIN_CAP
 #define FB_SCHED_SPIN_CAP (1 << 22)       // x s_sleep(32): seconds.  (Test builds lower it to provoke the abandon path.)
 #endif
@@ -572,11 +563,6 @@ __device__ __forceinline__ void fly_kernel(const DevModel<real>* Mp, const Batch
   // per-wave (per-environment) hot arrays
   constexpr int EPB = LdsCfg<real>::EPB;
   __shared__ real s_pool[EPB][LdsCfg<real>::POOL];          // [factor row | Delassus matrix | solve vector] of each environment
-#ifdef FB_LDS_PAD
-  // experiment: extra LDS per workgroup lowers the number of resident environments (is a phase latency- or issue-bound?)
-  __shared__ real s_pad[FB_LDS_PAD];
-  if (threadIdx.x == 0 && mode == 12345) s_pad[blockIdx.x % FB_LDS_PAD] = 1;
-#endif
   // elimination-tree tables shared by the workgroup's environments ("joint tree staged in LDS")
   __shared__ LdsTab s_tab;
   // the model lives in constant memory: its fields (sizes, table pointers, workspace offsets) are scalar loads
@@ -669,21 +655,13 @@ __device__ __forceinline__ void fly_kernel(const DevModel<real>* Mp, const Batch
 #ifndef FB_EMULATE
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
 #endif
-      WS<real> w;
-      w.o = (const FB_CONST WSOff*)&M.off;
-      w.rb = (FB_GLOBAL real*)(B.rarena + (size_t)env*M.off.nreal); w.ib = (FB_GLOBAL int*)(B.iarena + (size_t)env*M.off.nint);
-      w.lLD = (FB_LDS real*)s_pool[wave]; w.lt = (const FB_LDS LdsTab*)&s_tab;
+      const WS<real> w = ws_env(M, B.rarena, B.iarena, env, s_pool, wave, &s_tab);
       float* obs = B.obs ? B.obs + (size_t)env*B.nobs : nullptr;
 #ifdef FB_EMULATE
       // (host emulation, test infrastructure: every ticket starts from a POISONED LDS pool -- whatever a stage left there for a later ticket,
       //  against the claim that nothing LDS-resident crosses a ticket boundary, turns the state into NaN and fails the parity tests)
       for (int i = lane; i < LdsCfg<real>::POOL; i += FB_WAVE) w.lLD[i] = (real)NAN;
       SYNC();
-#endif
-#if FB_HEAVY_PRIO_ROWS > 0
-      // an environment whose last constraint system was large is the likely end of the launch (its ten substeps are a serial chain:
-      // profiles/r5/launch_times.txt): issue priority from its first ticket, not only once it has fallen a round behind
-      if (late < FB_HEAVY_PRIO && uniform_int(w.istate()[IS_NEFC]) >= FB_HEAVY_PRIO_ROWS) late = FB_HEAVY_PRIO;
 #endif
       if (lane == 0) { w.istate()[IS_PRIO] = late; if (round == 0) w.istate()[IS_WARN] = 0; }
       FB_SETPRIO(late);
@@ -717,10 +695,7 @@ __device__ __forceinline__ void fly_kernel(const DevModel<real>* Mp, const Batch
     return;
   }
   int env = uniform_int(env_ids ? env_ids[slot] : slot);
-  WS<real> w;
-  w.o = (const FB_CONST WSOff*)&M.off;
-  w.rb = (FB_GLOBAL real*)(B.rarena + (size_t)env*M.off.nreal); w.ib = (FB_GLOBAL int*)(B.iarena + (size_t)env*M.off.nint);
-  w.lLD = (FB_LDS real*)s_pool[wave]; w.lt = (const FB_LDS LdsTab*)&s_tab;
+  const WS<real> w = ws_env(M, B.rarena, B.iarena, env, s_pool, wave, &s_tab);
   float* obs = B.obs ? B.obs + (size_t)env*B.nobs : nullptr;
 #if defined(FB_PROFILE) && !defined(FB_EMULATE)
   long long t0_ = clock64(), r0_ = wall_clock64();
@@ -1053,10 +1028,7 @@ static int build_devmodel(fb_batch* b, DevModel<real>& M) {
 template <typename real>
 static void compute_offsets(const DevModel<real>& M, WSOff& o) {
   uint32_t r = 0, i = 0;
-#ifndef FB_WS_ALIGN
-#define FB_WS_ALIGN 16
-#endif
-  auto al = [](uint32_t v) { return (v + (uint32_t)(FB_WS_ALIGN - 1)) & ~(uint32_t)(FB_WS_ALIGN - 1); };   // 4: every array 16/32-byte aligned; 16: on a cache line of its own
+  auto al = [](uint32_t v) { return (v + 15u) & ~15u; };   // every array on a cache line of its own
 #define X(name, n) o.name = r; r = al(r + (uint32_t)(n));
   FB_WS_REAL(X)
 #undef X
@@ -1333,11 +1305,9 @@ static int launch(fb_batch* b, int mode, const float* action, const int* ids, in
   if (full_step && b->order_valid) ids = b->order;       // slowest environments of the previous step first
   if (tickets) {
     HIPCHK(hipMemsetAsync(b->tick, 0, 16*16*sizeof(int), st)); HIPCHK(hipMemsetAsync(b->done, 0, (size_t)n*sizeof(int), st));
-#if FB_TICKET_ORDER
     if (b->ticket_order) hipLaunchKernelGGL(k_ticket_order, dim3(b->nq), dim3(FB_ORDER_THREADS), 0, st, (const int*)b->iarena, (int)b->off.nint, (int)(b->off.istate + IS_NEFC), b->torder, n, b->nq);
-#endif
   }
-  const int* tord = (tickets && FB_TICKET_ORDER && b->ticket_order) ? b->torder : nullptr;
+  const int* tord = (tickets && b->ticket_order) ? b->torder : nullptr;
   const int FB_TIMED_MAX = 2048;
   const bool per_launch = b->timing && mode == MODE_STEP && b->timed_launches < FB_TIMED_MAX;
   if (per_launch) {

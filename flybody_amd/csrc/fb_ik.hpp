@@ -30,9 +30,7 @@
 #include "fb_smooth.hpp"
 
 #define FB_IK_POOL 1536
-#ifndef FB_IK_WAVES_PER_SIMD
 #define FB_IK_WAVES_PER_SIMD 2
-#endif
 #define FB_IK_CHECK 100             // the reference evaluates the objective every 100 steps (inverse_kinematics.py:122)
 
 template <typename real>
@@ -81,15 +79,12 @@ FBD real ik_site_err(const IKArgs<real>& A, const WS<real>& w, const real* tgt, 
 
 template <typename real>
 __device__ __forceinline__ void ik_kernel(const DevModel<real>* Mp, real* rarena, int* iarena, const IKArgs<real>& A) {
-  __shared__ real s_ik[FB_IK_POOL];
+  __shared__ real s_ik[1][FB_IK_POOL];                          // (one wave per workgroup)
   const DevModel<real>& M = as_constant(*Mp);
   const int lane = threadIdx.x % FB_WAVE;
   const int env = uniform_int(blockIdx.x);
   if (env >= A.n_env) return;
-  WS<real> w;
-  w.o = (const FB_CONST WSOff*)&M.off;
-  w.rb = (FB_GLOBAL real*)(rarena + (size_t)env*M.off.nreal); w.ib = (FB_GLOBAL int*)(iarena + (size_t)env*M.off.nint);
-  w.lLD = (FB_LDS real*)s_ik; w.lt = nullptr;                  // (the position stages use the pool only, not the elimination-tree tables)
+  const WS<real> w = ws_env(M, rarena, iarena, env, s_ik, 0, (const LdsTab*)nullptr);      // (the position stages use the pool only, not the elimination-tree tables)
   const real* tgt = A.target + (size_t)env*3*A.n_site;
   const int nv = M.nv, nbody = M.nbody;
   // LDS after the position stages: cdof [6 nv] (d_com_pos mirrors it at the pool's start) | body wrenches [6 nbody] | qpos update [nv]

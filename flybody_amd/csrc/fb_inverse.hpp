@@ -52,10 +52,7 @@ __device__ __forceinline__ void inverse_kernel(const DevModel<real>* Mp, real* r
   const int wave = uniform_int(tid / FB_WAVE), lane = tid % FB_WAVE;
   const int env = uniform_int(blockIdx.x*EPB + wave);
   if (env >= A.n_env) return;
-  WS<real> w;
-  w.o = (const FB_CONST WSOff*)&M.off;
-  w.rb = (FB_GLOBAL real*)(rarena + (size_t)env*M.off.nreal); w.ib = (FB_GLOBAL int*)(iarena + (size_t)env*M.off.nint);
-  w.lLD = (FB_LDS real*)s_pool[wave]; w.lt = (const FB_LDS LdsTab*)&s_tab;
+  const WS<real> w = ws_env(M, rarena, iarena, env, s_pool, wave, &s_tab);
   const WS<real> wc = w;
   // ---- mj_invPosition + mj_invVelocity: the forward pass's stages, unchanged
   s_kinematics(M, wc, lane);

@@ -15,40 +15,19 @@
 #else
 #define FB_NOINLINE __attribute__((noinline))
 #endif
-#ifndef FB_INL_A
-#define FB_INL_A 0      // (1,1) trips an AMDGPU back-end assertion in ROCm 7.2 (private-base compare); (0,1) measured equal
-#endif
-#ifndef FB_INL_B
-#define FB_INL_B 1
-#endif
-#if FB_INL_A
-#define FB_STAGE_A __device__ FB_NOINLINE
-#else
-#define FB_STAGE_A __device__ __forceinline__
-#endif
-#ifndef FB_INL_FS
-#define FB_INL_FS 1
-#endif
-#if FB_INL_FS
-#define FB_STAGE_FS __device__ FB_NOINLINE
-#else
-#define FB_STAGE_FS __device__ __forceinline__
-#endif
-#if FB_INL_B
+#define FB_STAGE_A __device__ __forceinline__   // (noinline here trips an AMDGPU back-end assertion in ROCm 7.2: private-base compare)
 #define FB_STAGE_B __device__ FB_NOINLINE
-#else
-#define FB_STAGE_B __device__ __forceinline__
-#endif
+#define FB_STAGE_FS __device__ FB_NOINLINE
 #define FB_MINV ((real)1e-15)
 
 // division on solver hot paths: exact in FP64 (bit-faithful to the oracle), v_rcp_f32 (1 ulp) in FP32
 // FP64: IEEE division costs ~25 dependent instructions (v_div_scale x2, v_rcp_f64, 5 FMAs, v_div_fmas, v_div_fixup) in the
-// middle of the solver's serial chain.  Unless FB_EXACT_DIV64 is defined the quotient is v_rcp_f64 + two Newton steps + one residual
-// correction (<= 1 ulp for the normal-range operands the solver produces, no denormal / overflow handling).
-#if !defined(FB_EXACT_DIV64) && !defined(FB_EMULATE)
-#ifndef FB_DIV_STEPS
+// middle of the solver's serial chain.  On the device the quotient is v_rcp_f64 + two Newton steps + one residual correction (<= 1 ulp for
+// the normal-range operands the solver produces, no denormal / overflow handling).
+#ifndef FB_EMULATE
 #define FB_DIV_STEPS 2
-#endif
+#define FB_RSQ_STEPS 1
+#define FB_INV_STEPS 2
 FBD double fb_div(double a, double b) {
   double r = __builtin_amdgcn_rcp(b);
 #pragma unroll
@@ -56,51 +35,23 @@ FBD double fb_div(double a, double b) {
   double q = a*r;
   return __builtin_fma(__builtin_fma(-b, q, a), r, q);
 }
-#else
-FBD double fb_div(double a, double b) { return a / b; }
-#endif
-#ifdef FB_EMULATE
-FBD float fb_div(float a, float b) { return a / b; }
-#else
 FBD float fb_div(float a, float b) { return a * __builtin_amdgcn_rcpf(b); }
-#endif
-#if !defined(FB_EXACT_DIV64) && !defined(FB_EMULATE)
 // (round 6: ONE Newton step behind v_rsq_f64 -- a few ulp instead of <= 1 -- measured +0.5 % env-steps/s with the 100-control-step divergence from the
-//  oracle unchanged at 7e-15 / 4e-14 on qpos / qvel, profiles/r6/ab_reciprocals.txt; FB_RSQ_STEPS 2 restores the second)
-#ifndef FB_RSQ_STEPS
-#define FB_RSQ_STEPS 1
-#endif
+//  oracle unchanged at 7e-15 / 4e-14 on qpos / qvel, profiles/r6/ab_reciprocals.txt)
 FBD double fb_rsqrt(double a) {
   double y = __builtin_amdgcn_rsq(a);
 #pragma unroll
   for (int k = 0; k < FB_RSQ_STEPS; k++) y = y*__builtin_fma(-0.5*a*y, y, 1.5);
   return y;
 }
-#else
-FBD double fb_rsqrt(double a) { return 1.0 / sqrt(a); }
-#endif
-#ifdef FB_EMULATE
-FBD float fb_rsqrt(float a) { return 1.0f / sqrtf(a); }
-#else
 FBD float fb_rsqrt(float a) { return __builtin_amdgcn_rsqf(a); }
-#endif
 // sqrt / reciprocal on the same footing: v_rsq_f64 / v_rcp_f64 + Newton steps (<= 1 ulp) instead of the IEEE sequences (~30 dependent
 // instructions each) -- used by the vector normalisations and the iterative collision query, which sit on serial chains.
-// The host emulation and FB_EXACT_DIV64 builds keep the exact operations.
-#if !defined(FB_EXACT_DIV64) && !defined(FB_EMULATE)
 FBD double fb_sqrt(double a) { return a > 0 ? a*fb_rsqrt(a) : 0.0; }
 FBD float fb_sqrt(float a) { return a > 0 ? a*fb_rsqrt(a) : 0.0f; }
-#else
-FBD double fb_sqrt(double a) { return sqrt(a); }
-FBD float fb_sqrt(float a) { return sqrtf(a); }
-#endif
-// 1 / a: v_rcp_f64 + Newton steps.  fb_div(1, a) is rcp + THREE steps (its residual correction of q = 1 * r is a third one): the second already
-// leaves the rounding of the last fma as the only error, and a reciprocal sits on the serial chain of every pivot (Gauss-Jordan on the
-// Newton tiles) and of every level of the factorisations.  FB_INV_STEPS 3 restores the old sequence.
-#ifndef FB_INV_STEPS
-#define FB_INV_STEPS 2
-#endif
-#if !defined(FB_EXACT_DIV64) && !defined(FB_EMULATE) && FB_INV_STEPS < 3
+// 1 / a: v_rcp_f64 + FB_INV_STEPS Newton steps.  fb_div(1, a) would be rcp + THREE steps (its residual correction of q = 1 * r is a third one): the
+// second already leaves the rounding of the last fma as the only error, and a reciprocal sits on the serial chain of every pivot
+// (Gauss-Jordan on the Newton tiles) and of every level of the factorisations.
 FBD double fb_inv(double a) {
   double r = __builtin_amdgcn_rcp(a);
 #pragma unroll
@@ -108,6 +59,13 @@ FBD double fb_inv(double a) {
   return r;
 }
 #else
+// the host emulation keeps the exact operations
+FBD double fb_div(double a, double b) { return a / b; }
+FBD float fb_div(float a, float b) { return a / b; }
+FBD double fb_rsqrt(double a) { return 1.0 / sqrt(a); }
+FBD float fb_rsqrt(float a) { return 1.0f / sqrtf(a); }
+FBD double fb_sqrt(double a) { return sqrt(a); }
+FBD float fb_sqrt(float a) { return sqrtf(a); }
 FBD double fb_inv(double a) { return fb_div(1.0, a); }
 #endif
 FBD float fb_inv(float a) { return fb_div(1.0f, a); }
@@ -123,12 +81,9 @@ template <typename real> FBD void add3(real* r, const real* a, const real* b) { 
 template <typename real> FBD void scl3(real* r, const real* a, real s) { r[0] = a[0]*s; r[1] = a[1]*s; r[2] = a[2]*s; }
 template <typename real> FBD void addscl3(real* r, const real* a, real s) { r[0] += a[0]*s; r[1] += a[1]*s; r[2] += a[2]*s; }
 template <typename real> FBD real norm3(const real* a) { return fb_sqrt(dot3(a, a)); }
-#ifndef FB_RSQ_NORM
-#define FB_RSQ_NORM 1
-#endif
 // norm and its reciprocal from ONE reciprocal square root (device builds: fb_sqrt is a * rsqrt(a) there anyway; the division that
 // followed it was 8 more instructions on the chain of every normalisation and support-function call)
-#if FB_RSQ_NORM && !defined(FB_EXACT_DIV64) && !defined(FB_EMULATE)
+#ifndef FB_EMULATE
 template <typename real> FBD real norm_rnorm(real n2, real& rn) { rn = n2 > 0 ? fb_rsqrt(n2) : (real)0; return n2*rn; }
 #else
 template <typename real> FBD real norm_rnorm(real n2, real& rn) { const real n = fb_sqrt(n2); rn = fb_inv(n > 0 ? n : (real)1); return n; }
@@ -229,11 +184,6 @@ template <typename real> FBD real clampr(real x, real lo, real hi) { return x < 
 #define FB_OPAQUE(x) asm volatile("" : "+v"(x))
 #define FB_SETPRIO(p) do { int p_ = (p); if (p_ <= 0) __builtin_amdgcn_s_setprio(0); else if (p_ == 1) __builtin_amdgcn_s_setprio(1); else if (p_ == 2) __builtin_amdgcn_s_setprio(2); else __builtin_amdgcn_s_setprio(3); } while (0)
 #define FB_LDS_AS __attribute__((address_space(3)))
-#endif
-
-// issue priority of the latency-bound stage class (fb_step.hpp: d_run; 0 = no stage classes)
-#ifndef FB_LAT_PRIO
-#define FB_LAT_PRIO 2
 #endif
 
 // Arguments of a non-inlined device function arrive in VGPRs even when they are wave-uniform.  Moving a uniform

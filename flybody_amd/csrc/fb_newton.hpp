@@ -35,29 +35,11 @@
 #define FB_NEWTON_LS_MAX 20
 #define FB_NEWTON_MAXROWS 64
 #define FB_NEWTON_NT 16     // rows up to which a system is solved in the 16 x 16 tile layout (4 entries per lane)
-#ifndef FB_NEWTON_F32_FLOOR
 #define FB_NEWTON_F32_FLOOR 1e-10
-#endif
 enum { FB_SOLVER_PGS = 0, FB_SOLVER_CG = 1, FB_SOLVER_NEWTON = 2 };      // mjtSolver numbering
 
-#ifndef FB_NEWTON_INLINE
 #define FB_NEWTON_ATTR __device__ FB_NOINLINE
-#else
-#define FB_NEWTON_ATTR __device__ __forceinline__
-#endif
 
-#ifndef FB_NW_REUSE
-#define FB_NW_REUSE 1
-#endif
-#ifndef FB_NW_HOIST
-#define FB_NW_HOIST 1
-#endif
-#ifndef FB_NW_SPLIT
-#define FB_NW_SPLIT 1
-#endif
-#ifndef FB_NW_RSQ
-#define FB_NW_RSQ 1
-#endif
 // constants of a row (lane): position inside its contact block, scaling of the block's three rows, regulariser
 template <typename real> struct NwConst { int k; bool ell; real D, sqD, s0, s1, s2, mu, Dm, g1; };
 // force, cost share, and this lane's row / column of the block factor F (H = F F')
@@ -69,7 +51,7 @@ template <typename real>
 FBD void nw_update(const NwConst<real>& c, real jb0, real jb1, real jb2, NwRow<real>& o) {
   const real jo = c.k == 0 ? jb0 : (c.k == 1 ? jb1 : jb2);
   const real U0 = jb0*c.s0, U1 = jb1*c.s1, U2 = jb2*c.s2;
-#if FB_NW_RSQ && !defined(FB_EMULATE) && !defined(FB_EXACT_DIV64)
+#ifndef FB_EMULATE
   // |tangential part| and its reciprocal from ONE reciprocal square root (fb_sqrt is a * rsqrt(a) anyway): no division on the chain
   const real TT = U1*U1 + U2*U2;
   const real Tr = TT > 0 ? fb_rsqrt(TT) : (real)0;
@@ -82,7 +64,7 @@ FBD void nw_update(const NwConst<real>& c, real jb0, real jb1, real jb2, NwRow<r
   const bool bot = !top & ((c.mu*N + T <= 0) | ((T <= 0) & (N < 0)));
   const bool mid = c.ell & !top & !bot;
   const bool quad = c.ell ? bot : (jo < 0);
-#if FB_NW_RSQ && !defined(FB_EMULATE) && !defined(FB_EXACT_DIV64)
+#ifndef FB_EMULATE
   const real Ti = mid ? Tr : (real)1;
 #else
   const real Ti = fb_div((real)1, mid ? T : (real)1);
@@ -432,59 +414,17 @@ FB_NEWTON_ATTR int d_newton_wide(const DevModel<real>& M_, const WS<real>& w_, i
   return niter;
 }
 
-// One elimination step of the 16 x 16 register tile (lane (ti, tc) holds K[ti][4 tc + 0..3]): trailing update, the scaled pivot ROW kept
-// in place (the back substitution reads U[ti][p] from it), forward substitution.  Round 5: two masks and one multiply-add per register
-// instead of a three-way choice per register -- the scaled pivot COLUMN is not written back (nothing reads a finished column: the next
-// pivots read trailing entries, the back substitution the row images), and the rows above the pivot pass through the multiply-add with a
-// zero multiplier.
-#ifndef FB_NW_CHOLMASK
-#define FB_NW_CHOLMASK 1
-#endif
-#if FB_NW_CHOLMASK
-#define NW_ELIM(pv, Kr, Lip, Lpj, inv, invd, yp, yv)                                        \
-  do {                                                                                      \
-    const bool prow_ = ti == (pv);                                                          \
-    const real Lm_ = ti > (pv) ? (Lip) : (real)0;                                           \
-    _Pragma("unroll") for (int s = 0; s < 4; s++) {                                         \
-      const bool right_ = 4*tc + s > (pv);                                                  \
-      const real l_ = right_ ? Lpj[s] : (real)0;                                            \
-      const real t_ = Kr[s] - Lm_*l_;                                                       \
-      Kr[s] = (prow_ && right_) ? l_ : t_;                                                  \
-    }                                                                                       \
-    invd = prow_ ? (inv) : invd;                                                            \
-    yv = prow_ ? (yp) : yv - Lm_*(yp);                                                      \
-  } while (0)
-#else
-#define NW_ELIM(pv, Kr, Lip, Lpj, inv, invd, yp, yv)                                        \
-  do {                                                                                      \
-    _Pragma("unroll") for (int s = 0; s < 4; s++) {                                         \
-      const int tj = 4*tc + s;                                                              \
-      if (ti > (pv) && tj > (pv)) Kr[s] -= (Lip)*Lpj[s];                                    \
-      else if (ti == (pv) && tj > (pv)) Kr[s] = Lpj[s];                                     \
-      else if (tj == (pv) && ti > (pv)) Kr[s] = (Lip);                                      \
-    }                                                                                       \
-    if (ti == (pv)) { invd = (inv); yv = (yp); }                                            \
-    else if (ti > (pv)) yv -= (Lip)*(yp);                                                   \
-  } while (0)
-#endif
 // Gauss-Jordan step on the register tile (round 5): the pivot row is scaled by 1 / K[p][p] and EVERY other row -- above and below --
 // eliminates its entry of the pivot column, the right-hand side riding along: after the last pivot the right-hand side IS the solution,
 // there is no back substitution (a second serial chain of one LDS-crossbar round trip per pivot), no triangular mask (a finished column
 // of the pivot row holds exact zeros or rounding residue that nothing reads), no square root.  In the tile layout the whole matrix is
 // one multiply-add per register anyway, so touching the rows above the pivot is free.  K = I + F'AF is symmetric positive definite with
 // pivots >= 1: elimination without pivoting is stable; the direction it yields differs from the Cholesky one (oracle) by rounding.
-#ifndef FB_NW_GJ
-#define FB_NW_GJ 1
-#endif
-// Round 6 (FB_NW_GJ_RAW): the pivot row is NOT scaled in place -- every other row subtracts (K[i][p] / K[p][p]) times the raw pivot row,
+// Round 6: the pivot row is NOT scaled in place -- every other row subtracts (K[i][p] / K[p][p]) times the raw pivot row,
 // the pivot row passes through with a zero multiplier, its reciprocal pivot is kept in `invd` and the solution is yv * invd at the end
 // (a finished row's diagonal is never touched again: its entries in later pivot columns are what those pivots eliminate, column p of a
 // later pivot row is zero).  One multiply and one select per step and lane instead of five multiplies and ten selects; plain Gaussian
 // elimination to both sides, same pivots, rounding-level difference in the direction.
-#ifndef FB_NW_GJ_RAW
-#define FB_NW_GJ_RAW 1
-#endif
-#if FB_NW_GJ_RAW
 #define NW_GJ_STEP(pv, P, q, Kr, yv)                                                        \
   do {                                                                                      \
     const real invp_ = fb_inv(rdlane(Kr[q], 4*(pv) + (P)));                                 \
@@ -495,29 +435,7 @@ FB_NEWTON_ATTR int d_newton_wide(const DevModel<real>& M_, const WS<real>& w_, i
     yv -= Lm_*rdlane(yv, 4*(pv));                                                           \
     invd = prow_ ? invp_ : invd;                                                            \
   } while (0)
-#define NW_GJ_SOL(yv) ((yv)*invd)
-#else
-#define NW_GJ_STEP(pv, P, q, Kr, yv)                                                        \
-  do {                                                                                      \
-    const real invp_ = fb_inv(rdlane(Kr[q], 4*(pv) + (P)));                                 \
-    const real Lip_ = nw_lane(Kr[q], 4*ti + (P));                                           \
-    real rp_[4];                                                                            \
-    _Pragma("unroll") for (int s = 0; s < 4; s++) rp_[s] = nw_lane(Kr[s], 4*(pv) + tc)*invp_; \
-    const real yp_ = rdlane(yv, 4*(pv))*invp_;                                              \
-    const bool prow_ = ti == (pv);                                                          \
-    _Pragma("unroll") for (int s = 0; s < 4; s++) Kr[s] = prow_ ? rp_[s] : Kr[s] - Lip_*rp_[s]; \
-    yv = prow_ ? yp_ : yv - Lip_*yp_;                                                       \
-  } while (0)
-#define NW_GJ_SOL(yv) (yv)
-#endif
-#ifndef FB_NW_ROWSUM
-#define FB_NW_ROWSUM 1
-#endif
-#if FB_NW_ROWSUM
 #define NW_SUM(x) wave_sum_lo((x), tile)          // tile systems (<= 16 rows): every summand is zero outside lanes 0-15
-#else
-#define NW_SUM(x) wave_sum(x)
-#endif
 // ------------------------------------------------------------------ 17 ... 32 ACTIVE columns: Gauss-Jordan on a 32 x 32 register tile
 // Round 6.  The systems a lock-step launch ENDS on (tools/launch_times.py: steps whose largest system has 34-39 rows last 6 % longer than
 // steps without one, >= 40 rows 17 %) spend most of their solve in the right-looking factorisation on LDS rows below: ~75 k cycles per
@@ -528,10 +446,8 @@ FB_NEWTON_ATTR int d_newton_wide(const DevModel<real>& M_, const WS<real>& w_, i
 // shuffles, one multiply-add per live register.  The pivots of the second block row leave the finished first block column alone.
 // No back substitution, nothing of the factor returns to memory.  Round 5's attempt (2 x 2 blocked Cholesky INSIDE d_newton) spilled
 // the small-system path; this is a function of its own with its own register allocation, called on the rare path only.
-#ifndef FB_NW_TILE32
-#define FB_NW_TILE32 3      // 0: rows-in-LDS factorisation for every system with more than 16 active columns; 1-2: register tiles up to 32 active columns; 3: up to 48; 4: up to 64 (the LDS path is not compiled in)
-#endif
-// NB block rows of 16: n_act <= 16 NB (NB = 2: 32 columns, 16 matrix registers per lane; 3: 48 / 36; 4: 64 / 64 -- every system of one row per lane).
+// NB block rows of 16: n_act <= 16 NB (NB = 2: 32 columns, 16 matrix registers per lane; 3: 48 / 36).  Systems with more than 48 active
+// columns take the rows-in-LDS factorisation of d_newton.
 template <int NB, typename real, typename KP>
 FB_NEWTON_ATTR real nw_gj32(KP K, int n_act_, unsigned long long m_act, real dg, real y, int lane, bool on) {
   const int n_act = uniform_int(n_act_);
@@ -668,16 +584,13 @@ FB_NEWTON_ATTR int d_newton(const DevModel<real>& M_, const WS<real>& w_, ARP AR
   const int ti = lane >> 2, tc = lane & 3;
   const int tir = min(ti, n - 1);                   // (rows beyond the system: clamped addresses, zero factors)
   real At[4] = {0, 0, 0, 0};
-#if FB_NW_HOIST
   // Round 5: what the K build of EVERY iteration needs from the matrix is iteration-invariant -- for this lane's four tile columns
   // tj = 4 tc + s the packed-triangle positions of A[tir][base(tj) + 0..2] (three 8-bit indices per register: a 16-row triangle has 136
   // entries) -- and the regulariser leaves the diagonal ONCE: the solve works on A = AR - diag R in place (the owner lane keeps the
   // original diagonal entry and puts it back, bit for bit, behind the last iteration: the noslip pass reads AR).
   typename NwMut<ARP>::type ARw = (typename NwMut<ARP>::type)AR;
   real ar_diag = 0; unsigned kadr[4] = {0, 0, 0, 0};
-#endif
   if (tile) {
-#if FB_NW_HOIST
     if (on) { const int dd = lane*(lane + 1)/2 + lane; ar_diag = ARw[dd]; ARw[dd] = ar_diag - R; }
     SYNC_LDS();
 #pragma unroll
@@ -691,15 +604,6 @@ FB_NEWTON_ATTR int d_newton(const DevModel<real>& M_, const WS<real>& w_, ARP AR
       const int a2 = tir >= c2 ? tir*(tir + 1)/2 + c2 : c2*(c2 + 1)/2 + tir;
       kadr[s] = (unsigned)a0 | ((unsigned)a1 << 8) | ((unsigned)a2 << 16);
     }
-#else
-    const real Rt = nw_lane(R, tir);
-#pragma unroll
-    for (int s = 0; s < 4; s++) {
-      const int tj = 4*tc + s, tjr = min(tj, n - 1);
-      const real e = AR[tir >= tjr ? tir*(tir + 1)/2 + tjr : tjr*(tjr + 1)/2 + tir];
-      At[s] = (ti < n && tj < n) ? (ti == tj ? e - Rt : e) : (real)0;
-    }
-#endif
   }
   // y = A x  (A = AR - diag R).  lane == row: column k of the packed triangle per step, x_k by v_readlane
   auto amul = [&](real x) -> real {
@@ -745,14 +649,9 @@ FB_NEWTON_ATTR int d_newton(const DevModel<real>& M_, const WS<real>& w_, ARP AR
   }
   int niter = 0;
   NW_PROF(0);
-#if FB_NW_REUSE
   nw_update(c, jb0, jb1, jb2, o);
-#endif
   for (int it = 0; it < max_it; it++) {
-#if !FB_NW_REUSE
-    nw_update(c, jb0, jb1, jb2, o);
-#endif
-    // (FB_NW_REUSE: `o` is the constraint update at the current iterate on entry -- the line search's last evaluation is AT the accepted
+    // (`o` is the constraint update at the current iterate on entry -- the line search's last evaluation is AT the accepted
     //  step, so the update it computed is handed over instead of being recomputed here and once more behind the loop)
     const real r = o.f - lam;
     const real q = amul(r);
@@ -790,36 +689,21 @@ FB_NEWTON_ATTR int d_newton(const DevModel<real>& M_, const WS<real>& w_, ARP AR
         for (int s = 0; s < 4; s++) {
           const int tj = 4*tc + s;
           const real fj0 = nw_lane(o.fc0, tj), fj1 = nw_lane(o.fc1, tj), fj2 = nw_lane(o.fc2, tj);
-#if FB_NW_HOIST
           // (rows beyond the system compute garbage here that nothing reads: the second pass below addresses rows base_i + a < n only,
           //  and an off row's own factors are zero)
           const unsigned pk = kadr[s];
           G[s] = fj0*AR[pk & 255u] + fj1*AR[(pk >> 8) & 255u] + fj2*AR[(pk >> 16) & 255u];
-          continue;
-#endif
-          const int bj = nw_lane_i(base, tj);
-          const int c0 = min(bj, n - 1), c1 = min(bj + 1, n - 1), c2 = min(bj + 2, n - 1);
-          real e0 = AR[tir >= c0 ? tir*(tir + 1)/2 + c0 : c0*(c0 + 1)/2 + tir];
-          real e1 = AR[tir >= c1 ? tir*(tir + 1)/2 + c1 : c1*(c1 + 1)/2 + tir];
-          real e2 = AR[tir >= c2 ? tir*(tir + 1)/2 + c2 : c2*(c2 + 1)/2 + tir];
-          const real Rt = nw_lane(R, tir);
-          e0 -= (tir == c0) ? Rt : (real)0; e1 -= (tir == c1) ? Rt : (real)0; e2 -= (tir == c2) ? Rt : (real)0;
-          G[s] = (ti < n) ? fj0*e0 + fj1*e1 + fj2*e2 : (real)0;
         }
 #pragma unroll
         for (int s = 0; s < 4; s++)
           Kr[s] = ((ti == 4*tc + s) ? (real)1 : (real)0) + fi0*nw_lane(G[s], g0) + fi1*nw_lane(G[s], g1) + fi2*nw_lane(G[s], g2);
       }
       NW_PROF(2);
-      // ---- factorisation of the tile (right-looking, symmetric scaling: K = L~ U~ with U~ = L~' up to rounding), forward substitution
-      // folded in.  One elimination step is ONE multiply-add per register for the whole trailing matrix: the pivot row reaches a lane as
-      // K[p][4 tc + s] = lane (p, tc)'s own register s, the pivot column as K[ti][p] = lane (ti, p >> 2)'s register p & 3 (static: the
-      // pivot loop is unrolled by four).  Both images of a finished column are scaled in place, which lets the back substitution read
-      // U[ti][p] from a lane of its own row.
+      // ---- Gauss-Jordan elimination of the tile (NW_GJ_STEP), the right-hand side riding along.  One elimination step is ONE multiply-add
+      // per register for the whole matrix: the pivot row reaches a lane as K[p][4 tc + s] = lane (p, tc)'s own register s, the pivot column
+      // as K[ti][p] = lane (ti, p >> 2)'s register p & 3 (static: the pivot loop is unrolled by four).
       real yv = nw_lane(y, ti), invd = 1;
       const int PN = (n - 1) >> 2;
-#if FB_NW_GJ
-      (void)invd;
       for (int P = 0; P <= PN; P++) {
 #pragma unroll
         for (int q = 0; q < 4; q++) {
@@ -828,42 +712,7 @@ FB_NEWTON_ATTR int d_newton(const DevModel<real>& M_, const WS<real>& w_, ARP AR
         }
       }
       NW_PROF(3);
-#else
-      for (int P = 0; P <= PN; P++) {
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-          const int pv = 4*P + q;
-          if ((m_act >> pv) & 1ull) {
-            const real inv = fb_rsqrt(rdlane(Kr[q], 4*pv + P));
-            const real Lip = nw_lane(Kr[q], 4*ti + P)*inv;
-            real Lpj[4];
-#pragma unroll
-            for (int s = 0; s < 4; s++) Lpj[s] = nw_lane(Kr[s], 4*pv + tc)*inv;
-            const real yp = rdlane(yv, 4*pv)*inv;
-            NW_ELIM(pv, Kr, Lip, Lpj, inv, invd, yp, yv);
-          }
-        }
-      }
-      NW_PROF(3);
-      // ---- back substitution, last column first
-      for (int P = PN; P >= 0; P--) {
-#pragma unroll
-        for (int q = 3; q >= 0; q--) {
-          const int pv = 4*P + q;
-          if ((m_act >> pv) & 1ull) {
-            const real zp = rdlane(yv, 4*pv)*rdlane(invd, 4*pv);
-            const real Upi = nw_lane(Kr[q], 4*ti + P);
-            if (ti == pv) yv = zp;
-            else if (ti < pv) yv -= Upi*zp;
-          }
-        }
-      }
-#endif
-#if FB_NW_GJ
-      const real zr = nw_lane(NW_GJ_SOL(yv), 4*(lane & 15));
-#else
-      const real zr = nw_lane(yv, 4*(lane & 15));
-#endif
+      const real zr = nw_lane(yv*invd, 4*(lane & 15));
       z = (on && ((m_act >> lane) & 1ull)) ? zr : (real)0;
       NW_PROF(4);
     } else {
@@ -906,12 +755,11 @@ FB_NEWTON_ATTR int d_newton(const DevModel<real>& M_, const WS<real>& w_, ARP AR
       NW_PROF(2);
       if (n_act <= FB_NEWTON_NT) {
         FB_STAT(41);
-        // ---- tile factorisation (98.5 % of the iterations of the bench workload have <= 16 ACTIVE columns): the compacted K as a full
+        // ---- tile elimination (98.5 % of the iterations of the bench workload have <= 16 ACTIVE columns): the compacted K as a full
         // symmetric 16 x 16 tile over the wave -- lane (ti, tc) = (lane >> 2, lane & 3) holds K[ti][4 tc + 0..3] -- so that one elimination
-        // step is ONE multiply-add per register for the whole trailing matrix instead of a v_readlane per remaining column: the pivot row
+        // step is ONE multiply-add per register for the whole matrix instead of a v_readlane per remaining column: the pivot row
         // reaches a lane as K[p][4 tc + s] = lane (p, tc)'s own register s, the pivot column as K[ti][p] = lane (ti, p >> 2)'s register p & 3
-        // (static: the pivot loop is unrolled by four).  Both mirror images of a finished column are scaled in place (the tile ends as
-        // L + L' - diag), which lets the back substitution read L[p][ti] from a lane of its own row.  Nothing of L returns to LDS.
+        // (static: the pivot loop is unrolled by four).  Nothing of the factor returns to LDS.
         const bool mine = on && ((m_act >> lane) & 1ull);
         if (mine) K[my_ci*(my_ci + 1)/2 + my_ci] = (real)lane;     // row of compact index my_ci, parked in the diagonal slot of packed row my_ci (unused: the diagonals live in registers)
         SYNC();
@@ -930,8 +778,6 @@ FB_NEWTON_ATTR int d_newton(const DevModel<real>& M_, const WS<real>& w_, ARP AR
         }
         if (!iv) yv = 0;
         real invd = 1;
-#if FB_NW_GJ
-        (void)invd;
         for (int P = 0; 4*P < n_act; P++) {
 #pragma unroll
           for (int q = 0; q < 4; q++) {
@@ -940,69 +786,23 @@ FB_NEWTON_ATTR int d_newton(const DevModel<real>& M_, const WS<real>& w_, ARP AR
           }
         }
         NW_PROF(3);
-#else
-        for (int P = 0; 4*P < n_act; P++) {
-#pragma unroll
-          for (int q = 0; q < 4; q++) {
-            const int pv = 4*P + q;
-            if (pv < n_act) {
-              const real inv = fb_rsqrt(rdlane(Kr[q], 4*pv + P));
-              const real Lip = nw_lane(Kr[q], 4*ti + P)*inv;
-              real Lpj[4];
-#pragma unroll
-              for (int s = 0; s < 4; s++) Lpj[s] = nw_lane(Kr[s], 4*pv + tc)*inv;
-              const real yp = rdlane(yv, 4*pv)*inv;
-              NW_ELIM(pv, Kr, Lip, Lpj, inv, invd, yp, yv);
-            }
-          }
-        }
-        NW_PROF(3);
-        // ---- back substitution L' z = y, last column first: row ti < p reads L[p][ti] from the mirror image in its own row
-        for (int P = (n_act - 1) >> 2; P >= 0; P--) {
-#pragma unroll
-          for (int q = 3; q >= 0; q--) {
-            const int pv = 4*P + q;
-            if (pv < n_act) {
-              const real zp = rdlane(yv, 4*pv)*rdlane(invd, 4*pv);
-              const real Lpi = nw_lane(Kr[q], 4*ti + P);
-              if (ti == pv) yv = zp;
-              else if (ti < pv) yv -= Lpi*zp;
-            }
-          }
-        }
-#endif
-#if FB_NW_GJ
-        const real zr = nw_lane(NW_GJ_SOL(yv), mine ? 4*my_ci : 0);
-#else
-        const real zr = nw_lane(yv, mine ? 4*my_ci : 0);
-#endif
+        const real zr = nw_lane(yv*invd, mine ? 4*my_ci : 0);
         z = mine ? zr : (real)0;
         SYNC();                                       // (K is rewritten by the next iteration)
         NW_PROF(4);
       }
-#if FB_NW_TILE32
       else if (n_act <= 32) {
         FB_STAT(46);
         z = nw_gj32<2, real, KP>(K, n_act, m_act, dg, y, lane, on);
         NW_PROF(3); NW_PROF(4);
       }
-#if FB_NW_TILE32 >= 3
       else if (n_act <= 48) {
         FB_STAT(46);
         z = nw_gj32<3, real, KP>(K, n_act, m_act, dg, y, lane, on);
         NW_PROF(3); NW_PROF(4);
       }
-#endif
-#if FB_NW_TILE32 >= 4
       else {
-        FB_STAT(46);
-        z = nw_gj32<4, real, KP>(K, n_act, m_act, dg, y, lane, on);
-        NW_PROF(3); NW_PROF(4);
-      }
-#endif
-#endif
-#if FB_NW_TILE32 < 4
-      else {
+      // Larger systems      else {
       // Larger systems: right-looking factorisation on the rows in LDS.  These are the environments a lock-step launch WAITS for
       // (tools/ticket_trace.py: the last environments of a launch spent 5-20 x the mean here), so the loop is built for instruction count:
       //  * the ACTIVE rows are re-mapped onto the first n_act lanes (lane c = compact row c; the inactive rows of K are identity rows and
@@ -1087,7 +887,6 @@ FB_NEWTON_ATTR int d_newton(const DevModel<real>& M_, const WS<real>& w_, ARP AR
       SYNC();                                         // (K is rewritten by the next iteration)
       NW_PROF(4);
       }
-#endif
     }
     real dl;
     {
@@ -1119,9 +918,7 @@ FB_NEWTON_ATTR int d_newton(const DevModel<real>& M_, const WS<real>& w_, ARP AR
     NW_PROF(6); NW_COUNT(0);
     if (!(alpha > 0)) break;
     lam += alpha*dl; jb0 = tb0; jb1 = tb1; jb2 = tb2;
-#if FB_NW_REUSE
     o = o2;
-#endif
     niter = it + 1;
     // MuJoCo's own stopping test: the IMPROVEMENT of the iteration, scaled, below opt.tolerance.  phi is convex with phi'(0) = g0 < 0, so
     // the cost fell by at most -g0 alpha: when even that bound is under the tolerance the solver is done.  (The decrement bound at the
@@ -1130,13 +927,8 @@ FB_NEWTON_ATTR int d_newton(const DevModel<real>& M_, const WS<real>& w_, ARP AR
     // seen once in 160 environment-steps of the wing-collision variant, FB_WARN_SOLVER_MAXITER.)
     if (-g0*alpha*scale < tol) break;
   }
-#if !FB_NW_REUSE
-  nw_update(c, jb0, jb1, jb2, o);
-#endif
   if (on) w.efc_force()[lane] = o.f;
-#if FB_NW_HOIST
   if (tile) { if (on) ARw[lane*(lane + 1)/2 + lane] = ar_diag; SYNC_LDS(); }
-#endif
   if (n > FB_NEWTON_NT) FB_SETPRIO(uniform_int(w.istate()[IS_PRIO]));
 #if defined(FB_PROFILE) && !defined(FB_EMULATE)
   if (lane == 0) { long long* pp_ = (long long*)w.prof(); for (int k_ = 0; k_ < 7; k_++) pp_[32 + k_] += nwp_[k_]; pp_[39] += nwc_[0]; pp_[40] += nwc_[1]; pp_[41] += 1; }

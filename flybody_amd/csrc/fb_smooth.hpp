@@ -18,8 +18,6 @@
 // s_barrier, which would couple unrelated environments.
 #ifdef FB_EMULATE
 #define SYNC() __syncthreads()
-#elif defined(FB_SYNC_WORKGROUP)
-#define SYNC() do { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup"); __builtin_amdgcn_wave_barrier(); } while (0)
 #else
 #define SYNC() do { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); __builtin_amdgcn_wave_barrier(); } while (0)
 #endif
@@ -52,6 +50,18 @@ __device__ __forceinline__ WS<real> ws_uniform(const WS<real>& w_, const DevMode
   w.rb = uniform_p(w_.rb); w.ib = uniform_p(w_.ib);
   w.lLD = uniform_p(w_.lLD); w.lt = uniform_p(w_.lt);
   w.o = (const FB_CONST WSOff*)&M.off;              // (the offset table is part of the model, which every stage has in SGPRs: not fetched from the descriptor)
+  return w;
+}
+
+// ------------------------------------------------------------------ kernel prologue
+// The workspace descriptor of environment `env` run by wave `wave` of its workgroup: the environment's rows of the two arenas, the wave's
+// LDS pool pools[wave] and the workgroup's elimination-tree tables (null for a kernel that stages none).
+template <typename real, typename Pools>
+__device__ __forceinline__ WS<real> ws_env(const DevModel<real>& M, real* rarena, int* iarena, int env, Pools& pools, int wave, const LdsTab* tab) {
+  WS<real> w;
+  w.o = (const FB_CONST WSOff*)&M.off;
+  w.rb = (FB_GLOBAL real*)(rarena + (size_t)env*M.off.nreal); w.ib = (FB_GLOBAL int*)(iarena + (size_t)env*M.off.nint);
+  w.lLD = (FB_LDS real*)pools[wave]; w.lt = (const FB_LDS LdsTab*)tab;      // (indexed here, behind the rows: indexed by the caller, ahead of them, it reorders the kernels' prologue code)
   return w;
 }
 
@@ -555,11 +565,9 @@ __device__ __forceinline__ void d_crb(const DevModel<real>& M, const WS<real>& w
       // (no early exit: the loop must unroll completely, ch[] lives in registers; the row is collected in registers and stored in
       // one go -- a store between two slots makes the next slot's wait for its operands a wait for that store)
       real val[FB_MAXCH];
-      // (round 6, FB_CRB_GROUP: the wave-uniform bound is tested once per FB_CRB_GROUP slots -- a slot beyond it reads dof 0's axis like one beyond the
+      // (round 6: the wave-uniform bound is tested once per FB_CRB_GROUP slots -- a slot beyond it reads dof 0's axis like one beyond the
       //  dof's own depth and is not stored -- so that a group's 6 x FB_CRB_GROUP LDS reads are in flight together instead of one exposed round trip per slot)
-#ifndef FB_CRB_GROUP
 #define FB_CRB_GROUP 4
-#endif
 #pragma unroll
       for (int sl0 = 0; sl0 < FB_MAXCH; sl0 += FB_CRB_GROUP) {
 #pragma unroll
@@ -617,23 +625,14 @@ __device__ __forceinline__ void d_crb(const DevModel<real>& M, const WS<real>& w
 // (the loads are unconditional so that all of them are in flight together; an absent entry reads row `ms`,
 // which always exists, and its product is discarded)
 // Which dof is the lane's q-th row in the factorisation and the solves (-1: none).  Rounds 1-5: dof lane + 64 q, i.e. both row sets held dofs
-// of EVERY depth, and every level of the level loops ran the publish and the pull code of both.  Round 6 (FB_FAC_REMAP): the rows are dealt by
+// of EVERY depth, and every level of the level loops ran the publish and the pull code of both.  Round 6: the rows are dealt by
 // DEPTH -- the 64 shallowest dofs outside the trunk are the first rows, the rest (fruit fly: depth >= 12) the second -- so the second set's
 // code only runs on the deep levels and the first set's publish code only on the shallow ones: a level executes one publish and (mostly)
 // one pull block instead of two each.  The table is staged in LDS behind the branching-dof table (fb_engine.hip: s_gen[FB_MAXNV ..]).
-#ifndef FB_FAC_REMAP
-#define FB_FAC_REMAP 1
-#endif
 template <typename real>
-FBD int fac_dof(const WS<real>& w, int nv, int nT, int lane, int q) {
-#if FB_FAC_REMAP
+FBD int fac_dof(const WS<real>& w, int lane, int q) {
   const int j = w.lgen()[FB_MAXNV + lane + q*FB_WAVE];
-  (void)nv; (void)nT;
   return j == 255 ? -1 : j;
-#else
-  const int j = lane + q*FB_WAVE;
-  return (j < nv && j >= nT) ? j : -1;
-#endif
 }
 
 template <typename real>
@@ -650,17 +649,11 @@ FBD real gen_pull3(const FB_LDS real* RM, unsigned m01, unsigned m23, int oi, in
   return (p[0] + p[1]) + (p[2] + p[3]);
 }
 
-// Round 6 (FB_FAC_STRAIGHT): the wave-uniform row bounds of the level loop as a BINARY DESCENT on d into straight-line code instead of one
+// Round 6: the wave-uniform row bounds of the level loop as a BINARY DESCENT on d into straight-line code instead of one
 // compare-and-branch per entry (publish: 19 per row and level) or per group of four (pull: 5 per row and level, each group's LDS reads
 // waited for on their own because a basic block ends behind it).  profiles/r5/icache_counters.txt: 50 k branches per environment-step and
 // 16 % of the wave cycles waiting for the instruction buffer behind them; a third of the branches were these.
-#ifndef FB_FAC_STRAIGHT
-#define FB_FAC_STRAIGHT 1
-#endif
-#ifndef FB_FAC_VOLATILE
-#define FB_FAC_VOLATILE 1
-#endif
-#if FB_FAC_VOLATILE && !defined(FB_EMULATE)
+#ifndef FB_EMULATE
 #define FB_FAC_LD(p) ((const volatile FB_LDS real*)(p))       // keeps the backend from pairing the reads into ds_read2_b64 (half the LDS rate per byte: MI355X_MICROARCH.md, LDS table; +0.15 %)
 #else
 #define FB_FAC_LD(p) (p)
@@ -683,9 +676,7 @@ FBD void fac_publish(FB_LDS real* p, const real* row, int d) {
 // unconditionally in ONE block (every LDS read in flight before the first is consumed; what lands beyond a row's end is never read back, and the
 // reads stay inside the pool), the rest behind one test.  (An exclusive five-way dispatch on ceil(d / 4) was tail-merged by the compiler into
 // multiply + add pairs: more vector instructions than the branches it saved.)
-#ifndef FB_FAC_HEAD
 #define FB_FAC_HEAD 12
-#endif
 template <typename real>
 FBD real fac_pull(real* row, const FB_LDS real* pc, const FB_LDS real* pd, const FB_LDS real* p, int d) {
   const real c = pc[0]*pd[0];
@@ -739,7 +730,7 @@ FB_STAGE_FS void d_factor(const DevModel<real>& M_, const WS<real>& w_, const FB
   real row[2][FB_MAXCH], xa[2];
 #pragma unroll
   for (int q = 0; q < 2; q++) {
-    const int j = fac_dof(w, nv, nT, lane, q);       // (round 6: the lane's q-th row is NOT dof lane + 64 q any more -- the shallow dofs are the first rows, the deep ones the second: fac_dof)
+    const int j = fac_dof(w, lane, q);       // (round 6: the lane's q-th row is NOT dof lane + 64 q any more -- the shallow dofs are the first rows, the deep ones the second: fac_dof)
     jq[q] = j < 0 ? 0 : j;
     has[q] = j >= 0;
     dep[q] = has[q] ? w.ldepth()[j] : 31; mj[q] = has[q] ? w.lmadr()[j] : 0; cl[q] = has[q] ? w.lcl()[j] : 0;
@@ -772,12 +763,7 @@ FB_STAGE_FS void d_factor(const DevModel<real>& M_, const WS<real>& w_, const FB
       if (dep[q] == d) {
         const real di = fb_inv(row[q][0]);
         RM[mj[q]] = di; x[jq[q]] = xa[q];
-#if FB_FAC_STRAIGHT
         fac_publish<1, FB_MAXCH - 1>(RM + mj[q], row[q], d);                             // (exactly the row: the next row in memory belongs to a DEEPER dof, published earlier and still needed)
-#else
-#pragma unroll
-        for (int t = 1; t < FB_MAXCH; t++) if (t <= d) RM[mj[q] + t] = row[q][t];
-#endif
       }
     }
     F_PROF(0);
@@ -792,23 +778,9 @@ FB_STAGE_FS void d_factor(const DevModel<real>& M_, const WS<real>& w_, const FB
       if (tr < cl[q]) {
         // unbranched chain below the dof: the descendant's row starts at base + T(d) (rows of a chain grow by one entry per level)
         const int rk = base[q] + Td, o = d - dep[q];
-#if FB_FAC_STRAIGHT
-        const real xk_ = x[jq[q] + tr + 1];
-        const real c_ = fac_pull(row[q], RM + rk + o, RM + rk, RM + rk + o, d);
-        xa[q] -= c_*xk_;
-        continue;
-#endif
-        const real c = RM[rk + o]*RM[rk];            // M~[k, i] / D[k] = L[k, i] as the normalisation will round it
-        xa[q] -= c*x[jq[q] + tr + 1];
-#pragma unroll
-        for (int t0 = 0; t0 < FB_MAXCH; t0 += 4) {
-          // (t <= depth(i) <= d - 1 is what matters.  The bound is wave-uniform and tested once per four entries: a lane-varying
-          //  bound costs an exec-mask round trip per entry, and what lands beyond a row's end is never read back)
-          if (t0 < d) {
-#pragma unroll
-            for (int t = t0; t < t0 + 4; t++) row[q][t] -= c*RM[rk + o + t];
-          }
-        }
+        const real xk = x[jq[q] + tr + 1];
+        const real c = fac_pull(row[q], RM + rk + o, RM + rk, RM + rk + o, d);
+        xa[q] -= c*xk;
       } else if (gen[q] >= 0) {
         // branching dof: <= 4 listed descendant rows on this level
         const int oo = 2*(gen[q]*FB_MAXCH + d), o = d - dep[q];
@@ -817,21 +789,9 @@ FB_STAGE_FS void d_factor(const DevModel<real>& M_, const WS<real>& w_, const FB
         for (int c4 = 0; c4 < 4; c4++) {
           const int mk = ((c4 < 2 ? m01 : m23) >> (16*(c4 & 1))) & 0xffff, k = (pk >> (8*c4)) & 255;
           if (mk != 0xffff) {
-#if FB_FAC_STRAIGHT
-            const real xk_ = x[k];
-            const real c_ = fac_pull(row[q], RM + mk + o, RM + mk, RM + mk + o, d);
-            xa[q] -= c_*xk_;
-            continue;
-#endif
-            const real c = RM[mk + o]*RM[mk];
-            xa[q] -= c*x[k];
-#pragma unroll
-            for (int t0 = 0; t0 < FB_MAXCH; t0 += 4) {
-              if (t0 < d) {
-#pragma unroll
-                for (int t = t0; t < t0 + 4; t++) row[q][t] -= c*RM[mk + o + t];
-              }
-            }
+            const real xk = x[k];
+            const real c = fac_pull(row[q], RM + mk + o, RM + mk, RM + mk + o, d);
+            xa[q] -= c*xk;
           }
         }
       }
@@ -861,7 +821,7 @@ FB_STAGE_FS void d_factor_tail(const DevModel<real>& M_, const WS<real>& w_, con
   int fd[2], jt[2];
 #pragma unroll
   for (int q = 0; q < 2; q++) {
-    const int j = fac_dof(w, nv, nT, lane, q);
+    const int j = fac_dof(w, lane, q);
     bool has = j >= 0;
     jt[q] = has ? j : 0;
     int dp = has ? w.ldepth()[j] : 31, mj = has ? w.lmadr()[j] : 0;
@@ -978,7 +938,7 @@ FB_STAGE_FS void d_solve(const DevModel<real>& M_, const WS<real>& w_, const FB_
   int jd[2], dep[2], cl[2], gen[2], base[2], rowt[2]; real a_[2];
 #pragma unroll
   for (int q = 0; q < 2; q++) {
-    const int j0 = fac_dof(w, nv, nT, lane, q);
+    const int j0 = fac_dof(w, lane, q);
     const bool has = j0 >= 0;
     const int j = has ? j0 : 0;
     int dp = has ? w.ldepth()[j] : 31, mj = has ? lmadr[j] : 0;
@@ -1128,15 +1088,8 @@ FBD void tree_prefix6(const DevModel<real>& M, DofPair<real>& x, int lane) {
   for (int k = 0; k < FB_NJUMP; k++) {
     if (k == FB_NJUMP - 1 && split) break;         // the last round is the one the split saves
     real ga[6], gb[6];
-#ifndef FB_FETCH_LO
-#define FB_FETCH_LO 1
-#endif
-#if FB_FETCH_LO
     // (skipping the second slot altogether for models of <= 64 dofs -- flight_imitation has 42 -- behind a wave-uniform test: +0.9 % flight, -0.3 % walking; not taken)
     dof_fetch6_lo(x, ja[k], ga); dof_fetch6(x, jb[k], gb);
-#else
-    dof_fetch6(x, ja[k], ga); dof_fetch6(x, jb[k], gb);
-#endif
 #pragma unroll
     for (int c = 0; c < 6; c++) { x.a[c] += ga[c]; x.b[c] += gb[c]; }
   }

@@ -785,19 +785,11 @@ enum { ST_PRE = 32, ST_POST = 33 };
 // time instead of on the whole state machine (measured: the fully inlined kernel is ~25% slower).  A stage receives the
 // model (constant memory) and a copy of the workspace descriptor; it moves the descriptor's pointers back to SGPRs.
 // trailing-wave priority thresholds, in 32nds of the launch's environments (see ST_SUBEND)
-#ifndef FB_PRIO_T1
 #define FB_PRIO_T1 16
 #define FB_PRIO_T2 28
 #define FB_PRIO_T3 31
-#endif
-#ifndef FB_INL_C
-#define FB_INL_C 1
-#endif
-#if FB_INL_C
+#define FB_LAT_PRIO 2     // issue priority of the latency-bound stage class (d_run)
 #define FB_STAGE_C __device__ FB_NOINLINE
-#else
-#define FB_STAGE_C __device__ __forceinline__
-#endif
 #define FB_STAGE_WRAP(name, ...) \
   template <typename real> FB_STAGE_C void name(const DevModel<real>& M_, const WS<real>& w_, int lane) { \
     const DevModel<real>& M = as_constant(M_); const WS<real> w = ws_uniform(w_, M); __VA_ARGS__; }
@@ -850,17 +842,12 @@ __device__ __forceinline__ bool d_run(const DevModel<real>& M, const WS<real>& w
   // VGPRs + saved exec masks across every stage call and counts against the register budget of all stages
   mode = uniform_int(mode); nsub_arg = uniform_int(nsub_arg); tk = uniform_int(tk); only = uniform_int(only);
   const bool tk_first = tk < 0 || (tk & 1), tk_last = tk < 0 || (tk & 2), tk_half_a = tk >= 0 && (tk & 4), tk_half_b = tk >= 0 && (tk & 8);
-  // Round 6 (FB_LAT_PRIO; +0.5 %, profiles/r6/ab_stage_priority.txt): issue priority by STAGE CLASS.  The stages that are chains of memory round trips with a few hundred
+  // Round 6 (+0.5 %, profiles/r6/ab_stage_priority.txt): issue priority by STAGE CLASS.  The stages that are chains of memory round trips with a few hundred
   // instructions between them (actuation, factorisations, solves, sensors, integration, kinematics, inertias, constraint rows, velocities) run at
   // max(ticket priority, FB_LAT_PRIO); the three stages that do nothing but issue (projection, solver, collision) at the ticket's own priority.
-#if FB_LAT_PRIO > 0
   const int base_prio_ = uniform_int((tk >= 0 && (tk & 16)) ? 3 : 0);
 #define ST_LAT() FB_SETPRIO(base_prio_ > FB_LAT_PRIO ? base_prio_ : FB_LAT_PRIO)
 #define ST_ISS() FB_SETPRIO(base_prio_)
-#else
-#define ST_LAT() do {} while (0)
-#define ST_ISS() do {} while (0)
-#endif
   int parts = 15;
   bool resetting = (mode == MODE_RESET) || (mode == MODE_STEP && tk_first && uniform_int(w.istate()[IS_RESET_NEXT]) != 0);
   bool env_logic = (mode == MODE_STEP) || (mode == MODE_RESET);
@@ -919,9 +906,6 @@ __device__ __forceinline__ bool d_run(const DevModel<real>& M, const WS<real>& w
         half = true; ret = ST_ACC_POST; pc = ST_SOLVE; break;
       case ST_SOLVE: {
         PROF_BEGIN();
-#ifdef FB_LAT_FACTOR_ISS
-        ST_LAT();
-#endif
         d_solve(M, wc, w.lLD, w.lx(), half, lane);
         PROF(P_ACC);
         half = false;
@@ -960,9 +944,6 @@ __device__ __forceinline__ bool d_run(const DevModel<real>& M, const WS<real>& w
         damp = true; fret = ST_EULER_SOLVE; pc = ST_FACTOR; break; }
       case ST_FACTOR: {
         PROF_BEGIN();
-#ifdef FB_LAT_FACTOR_ISS
-        ST_ISS();
-#endif
         d_factor(M, wc, (const FB_GLOBAL real*)w.qM(), damp ? M.dof_damping.p : (const FB_GLOBAL real*)nullptr, damp ? M.timestep : (real)0, w.lLD, w.lx(), lane);
         PROF(P_FACTOR);
         pc = fret; break; }

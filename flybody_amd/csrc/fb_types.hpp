@@ -52,9 +52,7 @@ enum { IS_STEP = 0, IS_RESET_NEXT = 1, IS_STEP_TYPE = 2, IS_NCON = 3, IS_NEFC = 
        IS_MAX_NCON = 17, IS_MAX_NEFC = 18, IS_N_GT32 = 19, IS_N_GT64 = 20,      // FB_SIZE_STATS: maxima / counts over every substep since the batch was created (or the field was last set)
        IS_VL_OK = 21, IS_VL_N = 22, IS_VL_SKIP = 23,                             // mid-phase neighbour list (fb_collide.hpp): 1 = vl_list / vl_pos are set (2: and were used at least once); number of listed pairs; substeps left without list building
        IS_N = 24 };
-#ifndef FB_VL_SCALE
-#define FB_VL_SCALE 0.5       // neighbour-list slack in median geom bounding radii (0: no list)
-#endif
+#define FB_VL_SCALE 0.5       // neighbour-list slack in median geom bounding radii
 #define FB_VLMAX 448         // capacity of the mid-phase neighbour list (pairs); a list that does not fit is not kept (every substep then tests every pair)
 // IS_WARN bits (include/flybody_engine.h FB_WARN_*): raised during a launch, cleared at the start of the next control step;
 // IS_WARN_EVER accumulates them since the last reset of the environment

@@ -62,3 +62,29 @@ def test_build_flags_are_part_of_the_source_hash():
     for script in ('tools/build_variant.sh', 'tools/build_profile_lib.sh'):
         assert 'fb_build_flags.h' in open(os.path.join(g.ROOT, script)).read()
     assert len(engine.source_hash()) == 12
+
+
+# The engine's kernel sources and the FB_* names their preprocessor conditionals may test: the ones a committed build, test or tool sets
+# (__graft_entry__.py: FB_F64_DENSE, FB_EMULATE, FB_BUILD_ID; tools/build_profile_lib.sh: FB_PROFILE; tools/collision_stats.py: FB_STATS;
+# tests/test_kernel_emulation.py: FB_SCHED_SPIN_CAP), FB_MPR_PAIRED (derived from FB_EMULATE in fb_collide.hpp) and FB_TICKET_SPLIT (0:
+# folding its arithmetic changes k_fly's code).  A new switch lands together with the build, test or tool that sets it.
+ENGINE_KERNEL_SOURCES = ('fb_collide.hpp', 'fb_constraint.hpp', 'fb_math.hpp', 'fb_newton.hpp', 'fb_smooth.hpp', 'fb_step.hpp', 'fb_types.hpp',
+                         'fb_ik.hpp', 'fb_inverse.hpp', 'fb_engine.hip')
+KEPT_SWITCHES = {'FB_EMULATE', 'FB_PROFILE', 'FB_STATS', 'FB_F64_DENSE', 'FB_SCHED_SPIN_CAP', 'FB_BUILD_ID', 'FB_MPR_PAIRED', 'FB_TICKET_SPLIT'}
+
+
+def test_kernel_sources_test_only_switches_a_build_sets():
+    import os
+    import __graft_entry__ as g
+    found = {}
+    for name in ENGINE_KERNEL_SOURCES:
+        for n, line in enumerate(open(os.path.join(g.ROOT, 'flybody_amd', 'csrc', name)), 1):
+            m = re.match(r'\s*#\s*(if|ifdef|ifndef|elif)\b(.*)', line)
+            if m:
+                for sw in re.findall(r'\bFB_\w+', m.group(2)):
+                    found.setdefault(sw, []).append('%s:%d' % (name, n))
+                if m.group(1) == 'ifndef':
+                    assert 'FB_MPR_PAIRED' not in m.group(2), '%s:%d: FB_MPR_PAIRED follows FB_EMULATE, it is not overridable' % (name, n)
+    assert 'FB_EMULATE' in found and 'FB_PROFILE' in found
+    stray = {sw: where for sw, where in found.items() if sw not in KEPT_SWITCHES}
+    assert not stray, 'switches no build, test or tool sets: %s' % stray
