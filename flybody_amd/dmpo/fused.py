@@ -342,7 +342,6 @@ def bias_elu(x, bias):
 # ------------------------------------------------------------------ the B = 256 layers: small MFMA GEMM (+ bias + ELU epilogue)
 SMALL_GEMM_ROWS = 1024          # layers with more rows than this (the [5120 x 512] target-critic products) go to fbl_gemm_nt (LDS-tiled)
 SMALL_GEMM_K = 512              # ... longer reductions (741 / 800 input columns) to fbl_gemm_longk
-_USE_SGEMM = True               # (rounds 3-5 kept an FB_LEARNER_GEMM=blas switch for A/B runs against rocBLAS; removed: no BLAS call on the GPU path)
 
 
 def _sgemm(a, sai, sak, b, sbk, sbj, M, N, K, epilogue=0, bias=None):
@@ -419,7 +418,7 @@ def gemm_nt(x, w, bias=None, epilogue=0):
 
 def can_longk(x) -> bool:
     """The shapes fbl_gemm_longk is meant for: a 2-D float32 GPU batch of at most SMALL_GEMM_ROWS rows with SMALL_GEMM_K < K <= LONGK_MAX."""
-    return _USE_SGEMM and x.is_cuda and x.dim() == 2 and x.dtype == torch.float32 and x.shape[0] <= SMALL_GEMM_ROWS and SMALL_GEMM_K < x.shape[1] <= LONGK_MAX
+    return x.is_cuda and x.dim() == 2 and x.dtype == torch.float32 and x.shape[0] <= SMALL_GEMM_ROWS and SMALL_GEMM_K < x.shape[1] <= LONGK_MAX
 
 
 def gemm_longk(x, w0, w1=None):
@@ -460,7 +459,7 @@ def linear(x, w, bias=None, elu=False):
     fused); longer reductions at the learner's batch (the 741 / 800-column first layers) -> fbl_gemm_longk.  CPU tensors (the test-suite's
     reference) are F.linear + the plain epilogue; a GPU shape none of the kernels covers RAISES -- there is no BLAS fall-through."""
     assert bias is None or elu, 'bias without activation is not used by the networks (the loss kernels add the output biases)'
-    if _USE_SGEMM and x.is_cuda and x.dtype == torch.float32 and w.stride(1) == 1:
+    if x.is_cuda and x.dtype == torch.float32 and w.stride(1) == 1:
         need = torch.is_grad_enabled() and (x.requires_grad or w.requires_grad or (bias is not None and bias.requires_grad))
         rows = x.numel() // x.shape[-1]
         if rows > SMALL_GEMM_ROWS and not need:
@@ -473,7 +472,7 @@ def linear(x, w, bias=None, elu=False):
             return gemm_nt(x, w, bias if elu else None, 2 if elu else 0)
         if x.dim() == 2 and rows <= SMALL_GEMM_ROWS and SMALL_GEMM_K < x.shape[1] <= LONGK_MAX and not elu and not (need and x.requires_grad):
             return _LinearLongK.apply(x, w) if need else gemm_longk(x, w)
-    if _USE_SGEMM and x.is_cuda and x.dim() == 2 and x.shape[0] <= SMALL_GEMM_ROWS and x.shape[1] <= SMALL_GEMM_K and x.dtype == torch.float32:
+    if x.is_cuda and x.dim() == 2 and x.shape[0] <= SMALL_GEMM_ROWS and x.shape[1] <= SMALL_GEMM_K and x.dtype == torch.float32:
         if not (torch.is_grad_enabled() and (x.requires_grad or w.requires_grad or (bias is not None and bias.requires_grad))):
             # forward only (target networks, actors): nothing is saved, and W may be a column slice of a wider matrix (row stride)
             if x.stride(1) == 1 and w.stride(1) == 1:
@@ -555,7 +554,7 @@ class _GaussHeadLinear(torch.autograd.Function):
 
 def gauss_head_linear(h, wm, bm, ws, bs, mul, min_scale):
     """(mean, stddev) of the Gaussian policy head from the torso output h."""
-    if _USE_SGEMM and h.is_cuda and h.dim() == 2 and h.shape[0] <= SMALL_GEMM_ROWS and h.shape[1] <= SMALL_GEMM_K:
+    if h.is_cuda and h.dim() == 2 and h.shape[0] <= SMALL_GEMM_ROWS and h.shape[1] <= SMALL_GEMM_K:
         return _GaussHeadLinear.apply(h, wm, bm, ws, bs, mul, min_scale)
     return gauss_head(linear(h, wm), linear(h, ws), bm, bs, mul, min_scale)
 
@@ -602,9 +601,10 @@ def replay_gather(u, size, capacity, fields):
 
 
 # ------------------------------------------------------------------ the policy network behind its first layer: one launch
-# 'auto' (default): batches of more than SMALL_GEMM_ROWS rows (the actors' forward pass over all environments); at the learner's B = 256 the
-# fused chain was measured 3 % SLOWER than the layer-by-layer launches (16 workgroups) -- '1' forces it on, '0' off
-_POLICY_TAIL_MODE = os.environ.get('FB_LEARNER_POLICY_TAIL', 'auto')
+# 'auto': batches of more than SMALL_GEMM_ROWS rows (the actors' forward pass over all environments); at the learner's B = 256 the
+# fused chain was measured 3 % SLOWER than the layer-by-layer launches (16 workgroups) -- '1' forces it on (the kernel's
+# test at the learner's batch sizes), '0' off
+_POLICY_TAIL_MODE = 'auto'
 
 
 def _ptr(t):
@@ -664,7 +664,7 @@ def can_policy_tail(h1, torso_rest, head) -> bool:
     """The fused tail applies to the reference's policy: two ELU layers of width 256 behind the LayerNorm layer, action dimension <= 64."""
     if _POLICY_TAIL_MODE == '0' or (_POLICY_TAIL_MODE != '1' and h1.shape[0] <= SMALL_GEMM_ROWS):
         return False
-    return (_USE_SGEMM and h1.is_cuda and h1.dim() == 2 and h1.dtype == torch.float32 and len(torso_rest) == 2
+    return (h1.is_cuda and h1.dim() == 2 and h1.dtype == torch.float32 and len(torso_rest) == 2
             and all(tuple(l.weight.shape) == (256, 256) for l in torso_rest) and h1.shape[1] == 256 and head.mean.weight.shape[0] <= 64)
 
 

@@ -82,7 +82,6 @@ class Trainer:
         self.views = self.env.reset_all()
         self.obs = self.views['obs'].clone()
         self.env_steps = 0; self.learner_steps = 0; self._gate_checked = False
-        self.overlap = os.environ.get('FB_TRAIN_OVERLAP', '1') == '1'
         self._env_stream = torch.cuda.Stream(device=self.device); self._ev_act = torch.cuda.Event(); self._ev_phys = torch.cuda.Event()
         # checkpoints / policy snapshots / metrics (rank 0 writes; every rank restores so that replicas stay identical)
         self.counter = Counter(); self.checkpointer = self.snapshotter = None; self.logger = MetricsLogger(None)
@@ -104,24 +103,21 @@ class Trainer:
     def iterate(self, learn=True):
         """One control step of every environment, replay insertion, and the scheduled learner steps.
 
-        overlap (default on): the physics kernel of this control step runs on its own HIP stream WHILE the learner steps run on
-        the main stream -- the actor's forward pass precedes both, and the replay append (the only thing that depends on both)
-        follows them on the main stream.  The learner therefore samples transitions up to the PREVIOUS control step, one step
-        of lag in a pipeline that is asynchronous in the reference anyway (Ray actors + Reverb).  FB_TRAIN_OVERLAP=0: serial."""
+        The physics kernel of this control step runs on its own HIP stream WHILE the learner steps run on the main stream -- the
+        actor's forward pass precedes both, and the replay append (the only thing that depends on both) follows them on the main
+        stream.  The learner therefore samples transitions up to the PREVIOUS control step, one step of lag in a pipeline that is
+        asynchronous in the reference anyway (Ray actors + Reverb)."""
         canon = self.learner.act(self.obs)
         real = (self.a_min + 0.5 * (canon + 1.0) * self.a_scale).contiguous()       # CanonicalSpecWrapper inverse
         main = torch.cuda.current_stream()
-        if self.overlap:
-            self._ev_act.record(main)
-            with torch.cuda.stream(self._env_stream):
-                self._env_stream.wait_event(self._ev_act)
-                real.record_stream(self._env_stream)                                # (allocated on the main stream, consumed on the physics stream)
-                v = self.env.step_tensor(real)
-                self._ev_phys.record(self._env_stream)
-            stats = self._learn(learn)                                             # concurrent with the physics kernel
-            main.wait_event(self._ev_phys)
-        else:
+        self._ev_act.record(main)
+        with torch.cuda.stream(self._env_stream):
+            self._env_stream.wait_event(self._ev_act)
+            real.record_stream(self._env_stream)                                    # (allocated on the main stream, consumed on the physics stream)
             v = self.env.step_tensor(real)
+            self._ev_phys.record(self._env_stream)
+        stats = self._learn(learn)                                                 # concurrent with the physics kernel
+        main.wait_event(self._ev_phys)
         st = v['step_type']
         first, last = st == 0, st == 2
         nxt = v['obs'].clone()
@@ -145,8 +141,6 @@ class Trainer:
                 self._fin_n.zero_(); self._fin_ret.zero_(); self._fin_len.zero_()
         self.counter.increment(actor_steps=self.env.n_env*self.world)
         self.limiter.insert(self.env.n_env)
-        if not self.overlap:
-            stats = self._learn(learn)
         return stats
 
     def _learn(self, learn=True):
@@ -168,9 +162,9 @@ class Trainer:
             else:
                 self._gate_checked = True
         if allowed > 0:
-            if self.use_graphs and self.learner._graph_fb is None and self.learner._sets is None:
+            if self.use_graphs and not self.learner.graphs_captured:
                 self.learner.enable_graphs(self.replay.sample(B), sampler=lambda: self.replay.sample(B))
-            sampled_in_graph = self.learner._sampler is not None
+            sampled_in_graph = self.learner.samples_in_graph
             if self._burst_events is not None:
                 e0 = torch.cuda.Event(enable_timing=True); e0.record()
             for k in range(allowed):
@@ -247,10 +241,10 @@ def measure(tr: 'Trainer', warmup: int, iters: int):
                          'learner_time_share': burst_s/dt,
                          'note': 'learner_time_share = HIP-event time of the learner bursts / wall time (rank 0); the physics kernel of the '
                                  'same control step runs concurrently on its own stream'},
-            'num_samples': tr.cfg.num_samples, 'replay_size': tr.replay.size, 'independent_queues_found': getattr(lr, 'independent_queues_found', None),
+            'num_samples': tr.cfg.num_samples, 'replay_size': tr.replay.size, 'independent_queues_found': lr.independent_queues_found,
             'gradient_allreduce': ('none (single rank)' if tr.world == 1 else
                                    ('one flat buffer of %d floats per learner step over %s, %s' % (lr.flat_grad.numel(), dist.get_backend(),
-                                    'overlapped with the next step\'s target-network forwards (side stream)' if lr._sets is not None else 'serial'))),
+                                    'overlapped with the next step\'s target-network forwards (side stream)' if lr.pipelined else 'serial'))),
             'stats': {k: float(v) for k, v in (stats or {}).items() if k in ('critic_loss', 'policy_loss', 'dual_temperature', 'kl_q_rel')}}
 
 

@@ -41,5 +41,5 @@ if dist.get_rank() == 0:
     if os.environ.get('FB_TEST_PARAMS_OUT'):
         import numpy as np
         np.save(os.environ['FB_TEST_PARAMS_OUT'], mine.cpu().numpy())
-    print('TWO_RANKS_OK graphs=%s steps=%d pipelined=%s' % (graphs, tr.learner.num_steps, tr.learner._sets is not None))
+    print('TWO_RANKS_OK graphs=%s steps=%d pipelined=%s' % (graphs, tr.learner.num_steps, tr.learner.pipelined))
 dist.destroy_process_group()

@@ -231,6 +231,26 @@ def test_learner_step_mechanics():
     assert torch.equal(a1, a2) and a1.abs().max() <= 1.0
 
 
+# The FB_* names the learner's Python layer reads from the environment (the quoted ones: comments and docstrings may mention others):
+# the ones a committed test or tool sets (tests/test_gpu_fly_envs.py, tests/_dmpo_two_ranks.py: FB_LEARNER_GRAPHS, FB_LEARNER_PIPELINE,
+# FB_BENCH_DEVICE, FB_BENCH_BACKEND; bench.py: the FB_BENCH_* pair) and FB_LEARNER_FUSED_ELU_BWD, whose test patches the module constant
+# (it goes with the kernel's operand transform).  A new switch lands together with the test or tool that sets it.
+LEARNER_PYTHON_SOURCES = ('dmpo/learner.py', 'dmpo/fused.py', 'train_dmpo.py')
+KEPT_ENVIRONMENT_SWITCHES = {'FB_LEARNER_GRAPHS', 'FB_LEARNER_PIPELINE', 'FB_LEARNER_FUSED_ELU_BWD', 'FB_BENCH_DEVICE', 'FB_BENCH_BACKEND'}
+
+
+def test_learner_python_reads_only_switches_something_sets():
+    import re
+    found = {}
+    for name in LEARNER_PYTHON_SOURCES:
+        for n, line in enumerate(open(os.path.join(ROOT, 'flybody_amd', name)), 1):
+            for sw in re.findall(r'''['"](FB_\w+)['"]''', line):
+                found.setdefault(sw, []).append('%s:%d' % (name, n))
+    stray = {sw: where for sw, where in found.items() if sw not in KEPT_ENVIRONMENT_SWITCHES}
+    assert not stray, 'switches no test or tool sets: %s' % stray
+    assert set(found) == KEPT_ENVIRONMENT_SWITCHES, sorted(found)
+
+
 WORKER = r"""
 import os, sys
 sys.path.insert(0, %(root)r)
