@@ -42,36 +42,44 @@ class _MpoArgs(C.Structure):
                 ('stats', C.c_void_p), ('workspace', C.c_void_p)]
 
 
+# The C prototypes of include/flybody_learner.h as (restype, argtypes); tests/test_abi.py checks every entry against the header.
+_P, _I, _I64, _F = C.c_void_p, C.c_int, C.c_int64, C.c_float
+_SIGNATURES = {
+    'fbl_last_error': (C.c_char_p, []),
+    'fbl_version': (C.c_char_p, []),
+    'fbl_td_loss': (_I, [_P]*7 + [_F, _I, _I, _I] + [_P]*6),
+    'fbl_mpo_loss': (_I, [_P, _P]),
+    'fbl_mpo_workspace_floats': (C.c_size_t, [_I, _I]),
+    'fbl_adam': (_I, [_P]*6 + [_I64, _I] + [_P]*4 + [_F, _F, _F, _I, _P]),
+    'fbl_gather_flat': (_I, [_P, _P, _I, _P, _I, _P, _P, _P, _P]),
+    'fbl_bias_ln_act': (_I, [_P]*5 + [_I, _F, _I, _I, _I] + [_P]*4),
+    'fbl_bias_ln_act_bwd': (_I, [_P]*5 + [_I, _I, _I] + [_P]*5),
+    'fbl_bias_elu': (_I, [_P, _P, _I, _I, _P, _P]),
+    'fbl_bias_elu_bwd': (_I, [_P, _P, _I, _I, _P, _P, _P]),
+    'fbl_gauss_head': (_I, [_P]*4 + [_F, _F, _I, _I] + [_P]*3),
+    'fbl_gauss_head_bwd': (_I, [_P]*4 + [_F, _I, _I] + [_P]*4),
+    'fbl_gauss_head_bwd_std': (_I, [_P]*3 + [_F, _F, _I, _I] + [_P]*4),
+    'fbl_sample_actions': (_I, [_P]*3 + [_I]*3 + [_P]*3),
+    'fbl_concat_clamp': (_I, [_P, _P, _I, _I, _I, _P, _P]),
+    'fbl_sgemm': (_I, [_P, _I64, _I64, _P, _I64, _I64, _P, _I64, _I, _I, _I, _I, _P, _P]),
+    'fbl_sgemm_pair': (_I, [_P, _P, _I, _I64, _I, _I, _I, _P]),
+    'fbl_sgemm_op': (_I, [_P, _I64, _I, _I, _I, _P]),
+    'fbl_gemm_nt': (_I, [_P, _I64, _P, _I64, _P, _I64, _I, _I, _I, _I, _P, _P]),
+    'fbl_gemm_longk': (_I, [_P, _I64, _P, _I64, _P, _I, _P, _I64, _P, _I, _I, _I, _P]),
+    'fbl_replay_gather': (_I, [_P, _P, _I64, _I, _I, _P, _P, _P, _P]),
+    'fbl_policy_tail': (_I, [_P, _I, _I] + [_P]*8 + [_I, _F, _F] + [_P]*5),
+    'fbl_nstep_add': (_I, [_I, _I, _I64, _F, _I64, _I, _I] + [_P]*23),
+}
+
+
 def lib():
     global _lib
     if _lib is None:
         if not os.path.exists(LIB):
             raise LearnerLibError(f'{LIB} not found: build it with `python -c "import __graft_entry__ as g; g.build()"`')
         L = C.CDLL(LIB)
-        L.fbl_last_error.restype = C.c_char_p; L.fbl_version.restype = C.c_char_p
-        L.fbl_td_loss.argtypes = [C.c_void_p]*7 + [C.c_float, C.c_int, C.c_int, C.c_int] + [C.c_void_p]*6
-        L.fbl_mpo_loss.argtypes = [C.c_void_p, C.c_void_p]
-        L.fbl_mpo_workspace_floats.argtypes = [C.c_int, C.c_int]; L.fbl_mpo_workspace_floats.restype = C.c_size_t
-        L.fbl_adam.argtypes = [C.c_void_p]*6 + [C.c_int64, C.c_int] + [C.c_void_p]*4 + [C.c_float, C.c_float, C.c_float, C.c_int, C.c_void_p]
-        L.fbl_gather_flat.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.fbl_bias_ln_act.argtypes = [C.c_void_p]*5 + [C.c_int, C.c_float, C.c_int, C.c_int, C.c_int] + [C.c_void_p]*4
-        L.fbl_gauss_head.argtypes = [C.c_void_p]*4 + [C.c_float, C.c_float, C.c_int, C.c_int] + [C.c_void_p]*3
-        L.fbl_gauss_head_bwd.argtypes = [C.c_void_p]*4 + [C.c_float, C.c_int, C.c_int] + [C.c_void_p]*4
-        L.fbl_sample_actions.argtypes = [C.c_void_p]*3 + [C.c_int]*3 + [C.c_void_p]*3
-        L.fbl_concat_clamp.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-        L.fbl_sgemm.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int,
-                                C.c_int, C.c_void_p, C.c_void_p]
-        L.fbl_bias_ln_act_bwd.argtypes = [C.c_void_p]*5 + [C.c_int, C.c_int, C.c_int] + [C.c_void_p]*5
-        L.fbl_bias_elu.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-        L.fbl_bias_elu_bwd.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.fbl_replay_gather.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.fbl_policy_tail.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p]*8 + [C.c_int, C.c_float, C.c_float] + [C.c_void_p]*5
-        L.fbl_nstep_add.argtypes = [C.c_int, C.c_int, C.c_int64, C.c_float, C.c_int64, C.c_int, C.c_int] + [C.c_void_p]*23
-        L.fbl_sgemm_pair.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p]
-        L.fbl_sgemm_op.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p]
-        L.fbl_gauss_head_bwd_std.argtypes = [C.c_void_p]*3 + [C.c_float, C.c_float, C.c_int, C.c_int] + [C.c_void_p]*4
-        L.fbl_gemm_nt.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-        L.fbl_gemm_longk.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
+        for name, (restype, argtypes) in _SIGNATURES.items():
+            f = getattr(L, name); f.restype = restype; f.argtypes = argtypes
         _lib = L
     return _lib
 
@@ -100,6 +108,11 @@ def _stream():
 def _f32c(t):
     assert t.is_cuda and t.dtype == torch.float32
     return t if t.is_contiguous() else t.contiguous()
+
+
+def _p(t):
+    """Device pointer of an optional tensor (None -> NULL)."""
+    return t.data_ptr() if t is not None else None
 
 
 def available() -> bool:
@@ -171,8 +184,7 @@ def td_loss_grad(q_tm1_raw, bias_tm1, q_t_raw, bias_t, values, reward, discount,
     qt = _f32c(q_t_raw.detach()); q1 = _f32c(q_tm1_raw.detach()); dev = qt.device
     sampled_q = torch.empty(N, B, device=dev); dlog = torch.empty(B, K, device=dev); rows = torch.empty(B, device=dev)
     acc = zero_pool.take(K + 1, device=dev)
-    _check(lib().fbl_td_loss(qt.data_ptr(), bias_t.data_ptr() if bias_t is not None else None, q1.data_ptr(),
-                             bias_tm1.data_ptr() if bias_tm1 is not None else None, _f32c(values).data_ptr(), _f32c(reward).data_ptr(),
+    _check(lib().fbl_td_loss(qt.data_ptr(), _p(bias_t), q1.data_ptr(), _p(bias_tm1), _f32c(values).data_ptr(), _f32c(reward).data_ptr(),
                              _f32c(discount).data_ptr(), float(gamma), N, B, K, sampled_q.data_ptr(), dlog.data_ptr(), acc.data_ptr(),
                              rows.data_ptr(), acc[K:].data_ptr(), _stream()))
     return acc[K], sampled_q, dlog, acc[:K]
@@ -230,7 +242,7 @@ def mpo_loss_grad(mod, om, os_, tm, ts, actions, q):
     ws = _mpo_ws[key]
     pc = mod.penalization_cost
     a = _MpoArgs(N, B, D, om_c.data_ptr(), os_c.data_ptr(), tm_c.data_ptr(), ts_c.data_ptr(), a_c.data_ptr(), q_c.data_ptr(),
-                 pc.scale.data_ptr() if pc is not None else None, pc.offset.data_ptr() if pc is not None else None,
+                 _p(getattr(pc, 'scale', None)), _p(getattr(pc, 'offset', None)),
                  mod.log_temperature.data_ptr(), mod.log_alpha_mean.data_ptr(), mod.log_alpha_stddev.data_ptr(), mod.log_penalty_temperature.data_ptr(),
                  mod.epsilon, mod.epsilon_penalty, mod.epsilon_mean, mod.epsilon_stddev, int(bool(mod.action_penalization)),
                  g_om.data_ptr(), g_os.data_ptr(), g_lt.data_ptr(), g_am.data_ptr(), g_as.data_ptr(), g_pt.data_ptr(),
@@ -281,9 +293,8 @@ class _BiasLnAct(torch.autograd.Function):
         y = torch.empty_like(x)
         xhat = torch.empty_like(x) if need else None; rstd = torch.empty(M, device=x.device) if need else None
         _check(lib().fbl_bias_ln_act(x.data_ptr(), bias.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
-                                     rowadd.data_ptr() if rowadd is not None else None, rowadd.shape[0] if rowadd is not None else 1,
-                                     float(eps), int(act), M, W, y.data_ptr(),
-                                     xhat.data_ptr() if need else None, rstd.data_ptr() if need else None, _stream()))
+                                     _p(rowadd), rowadd.shape[0] if rowadd is not None else 1,
+                                     float(eps), int(act), M, W, y.data_ptr(), _p(xhat), _p(rstd), _stream()))
         if need:
             ctx.save_for_backward(y, xhat, rstd, gamma)
         ctx.act = int(act)
@@ -339,16 +350,22 @@ def bias_elu(x, bias):
     return F.elu(x + bias)
 
 
-# ------------------------------------------------------------------ the B = 256 layers: small MFMA GEMM (+ bias + ELU epilogue)
-SMALL_GEMM_ROWS = 1024          # layers with more rows than this (the [5120 x 512] target-critic products) go to fbl_gemm_nt (LDS-tiled)
-SMALL_GEMM_K = 512              # ... longer reductions (741 / 800 input columns) to fbl_gemm_longk
+# ------------------------------------------------------------------ the GEMMs: three hand-written MFMA kernels and the routing between them
+SMALL_GEMM_ROWS = 1024          # fbl_sgemm (32 x 32 tile per workgroup, K split over its waves): up to this many rows; more, forward only -> fbl_gemm_nt (LDS-tiled)
+SMALL_GEMM_K = 512              # ... and reductions up to this length; longer ones at few rows (741 / 800 input columns) -> fbl_gemm_longk
+LONGK_MAX = 832                 # fbl_gemm_longk: reductions of up to 13 x 64 columns
 
 
 def _sgemm(a, sai, sak, b, sbk, sbj, M, N, K, epilogue=0, bias=None):
     c = torch.empty(M, N, device=a.device)
-    _check(lib().fbl_sgemm(a.data_ptr(), sai, sak, b.data_ptr(), sbk, sbj, c.data_ptr(), N, M, N, K, int(epilogue),
-                           bias.data_ptr() if bias is not None else None, _stream()))
+    _check(lib().fbl_sgemm(a.data_ptr(), sai, sak, b.data_ptr(), sbk, sbj, c.data_ptr(), N, M, N, K, int(epilogue), _p(bias), _stream()))
     return c
+
+
+def _op(a, sai, sak, b, sbk, sbj, c=None, bias=None, epilogue=0, p0=0.0, p1=0.0, a_elu_of=None, a_rowsum=None):
+    """a_elu_of: the ELU layer's output, indexed like `a` -- operand A is a ELU'(output) (the backward pass's d z, never stored);
+    a_rowsum: receives the row sums of that operand (d bias of a d W product)."""
+    return _GemmOp(a.data_ptr(), b.data_ptr(), _p(c), _p(bias), sai, sak, sbk, sbj, epilogue, p0, p1, _p(a_elu_of), _p(a_rowsum))
 
 
 # Round 6 experiment, measured and left OFF: d z = d y ELU'(y) formed inside the d x | d W products (operand transform of fbl_sgemm) and
@@ -356,6 +373,37 @@ def _sgemm(a, sai, sak, b, sbk, sbj, M, N, K, epilogue=0, bias=None):
 # step got SLOWER: 4 100 against 4 280 learner steps/s (three runs each, profiles/r6/learner_fused_elu_bwd.txt).  The chains of the step
 # are bound by the duration of their ~6 us kernels, not by the number of launches.  FB_LEARNER_FUSED_ELU_BWD=1 switches it on.
 _FUSED_ELU_BWD = os.environ.get('FB_LEARNER_FUSED_ELU_BWD', '0') == '1'
+
+
+def _dx_dw(dz, x, w, need_dx, need_dw, a_elu_of=None, a_rowsum=None):
+    """(d x [M, K] = d z W, d W [N, K] = d z^T x) of z = x W^T on fbl_sgemm; a product that is not needed is None."""
+    M, K = x.shape; N = w.shape[0]; dev = dz.device
+    dx = torch.empty(M, K, device=dev) if need_dx else None; dw = torch.empty(N, K, device=dev) if need_dw else None
+    o0 = _op(dz, N, 1, w, K, 1, dx, a_elu_of=a_elu_of) if need_dx else None                        # [M, K] = d z [M, N] W [N, K]
+    o1 = _op(dz, 1, N, x, K, 1, dw, a_elu_of=a_elu_of, a_rowsum=a_rowsum) if need_dw else None     # [N, K] = d z^T [N, M] x [M, K]
+    if M == N and need_dx and need_dw:
+        # batch = layer width (the 256-wide layers at B = 256): the two products have the SAME shape and reduction length -- one launch
+        # with them side by side in the grid instead of two launches one after the other
+        _check(lib().fbl_sgemm_pair(C.byref(o0), C.byref(o1), 0, K, M, K, N, _stream()))
+        return dx, dw
+    if need_dx:
+        _check(lib().fbl_sgemm_op(C.byref(o0), K, M, K, N, _stream()))
+    if need_dw:
+        _check(lib().fbl_sgemm_op(C.byref(o1), K, N, K, M, _stream()))
+    return dx, dw
+
+
+def _elu_layer_backward(dy, y, x, w, need_dx, need_dw):
+    """(d x, d W, d bias) of y = ELU(x W^T + bias): d z = d y ELU'(y) and d bias = its column sums in one launch (fbl_bias_elu_bwd), then
+    the products -- or, with _FUSED_ELU_BWD, d z formed INSIDE the products (operand transform of fbl_sgemm) and d bias = the row sums of
+    d z^T leaving with d W: no launch of its own (a bias gradient without a weight gradient, not a case of the learner: the plain kernel)."""
+    M, N = dy.shape
+    if need_dw and _FUSED_ELU_BWD:
+        db = torch.empty(N, device=dy.device)
+        return (*_dx_dw(dy, x, w, need_dx, need_dw, a_elu_of=y, a_rowsum=db), db)
+    dz = torch.empty_like(dy); db = zero_pool.take(N, device=dy.device)
+    _check(lib().fbl_bias_elu_bwd(dy.data_ptr(), y.data_ptr(), M, N, dz.data_ptr(), db.data_ptr(), _stream()))
+    return (*_dx_dw(dz, x, w, need_dx, need_dw), db)
 
 
 class _Linear(torch.autograd.Function):
@@ -371,36 +419,16 @@ class _Linear(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         x, w, y = ctx.saved_tensors
-        dy = _f32c(dy); M, K = x.shape; N = w.shape[0]; dev = dy.device
-        nx, nw = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        ye = y if ctx.elu else None                                # d z = d y ELU'(y) is formed INSIDE the products (operand transform of
-        db = torch.empty(N, device=dev) if (ctx.elu and nw) else None   # fbl_sgemm), d bias = the row sums of d z^T leaves with d W: no launch of its own
-        if ctx.elu and (not nw or not _FUSED_ELU_BWD):            # (bias gradient without a weight gradient: not a case of the learner; keep the plain kernel)
-            dz = torch.empty_like(dy); db = zero_pool.take(N, device=dev)
-            _check(lib().fbl_bias_elu_bwd(dy.data_ptr(), y.data_ptr(), M, N, dz.data_ptr(), db.data_ptr(), _stream()))
-            dy = dz; ye = None
-        if M == N and nx and nw:
-            # batch = layer width (the 256-wide layers at B = 256): d x [M, K] = d z W and d W [N, K] = d z^T x have the SAME shape and
-            # reduction length -- one launch with the two products side by side in the grid instead of two launches one after the other
-            dx = torch.empty(M, K, device=dev); dw = torch.empty(N, K, device=dev)
-            o0 = _op(dy, N, 1, w, K, 1, dx, a_elu_of=ye); o1 = _op(dy, 1, N, x, K, 1, dw, a_elu_of=ye, a_rowsum=db if ye is not None else None)
-            _check(lib().fbl_sgemm_pair(C.byref(o0), C.byref(o1), 0, K, M, K, N, _stream()))
-            return dx, dw, db, None
-        dx = dw = None
-        if nx:                                                    # [M, K] = d z [M, N] W [N, K]
-            dx = torch.empty(M, K, device=dev); o0 = _op(dy, N, 1, w, K, 1, dx, a_elu_of=ye)
-            _check(lib().fbl_sgemm_op(C.byref(o0), K, M, K, N, _stream()))
-        if nw:                                                    # [N, K] = d z^T [N, M] x [M, K]
-            dw = torch.empty(N, K, device=dev); o1 = _op(dy, 1, N, x, K, 1, dw, a_elu_of=ye, a_rowsum=db if ye is not None else None)
-            _check(lib().fbl_sgemm_op(C.byref(o1), K, N, K, M, _stream()))
-        return dx, dw, db, None
-
-
-LONGK_MAX = 832                 # fbl_gemm_longk: reductions of up to 13 x 64 columns (the 741 / 800-column first layers)
+        dy = _f32c(dy); nx, nw = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if ctx.elu:
+            return (*_elu_layer_backward(dy, y, x, w, nx, nw), None)
+        return (*_dx_dw(dy, x, w, nx, nw), None, None)
 
 
 def _rows2d(x):
     """[..., K] -> [rows, K] view with a unit inner stride (no copy for the tensors of the learner step)."""
+    if x.dim() == 2 and x.stride(1) == 1:
+        return x
     x2 = x.reshape(-1, x.shape[-1])
     return x2 if x2.stride(1) == 1 else x2.contiguous()
 
@@ -411,8 +439,7 @@ def gemm_nt(x, w, bias=None, epilogue=0):
     x2 = _rows2d(x); M, K = x2.shape; N = w.shape[0]
     assert w.shape[1] == K and w.stride(1) == 1 and x2.dtype == torch.float32 and w.dtype == torch.float32
     y = torch.empty(M, N, device=x.device)
-    _check(lib().fbl_gemm_nt(x2.data_ptr(), x2.stride(0), w.data_ptr(), w.stride(0), y.data_ptr(), N, M, N, K, int(epilogue),
-                             bias.data_ptr() if bias is not None else None, _stream()))
+    _check(lib().fbl_gemm_nt(x2.data_ptr(), x2.stride(0), w.data_ptr(), w.stride(0), y.data_ptr(), N, M, N, K, int(epilogue), _p(bias), _stream()))
     return y.view(*x.shape[:-1], N)
 
 
@@ -426,10 +453,9 @@ def gemm_longk(x, w0, w1=None):
     learner's batch).  Forward only; returns one tensor or a pair."""
     x2 = _rows2d(x); M, K = x2.shape
     assert K <= LONGK_MAX and w0.shape[1] == K and w0.stride(1) == 1 and (w1 is None or (w1.shape[1] == K and w1.stride(1) == 1))
-    y0 = torch.empty(M, w0.shape[0], device=x.device); y1 = torch.empty(M, w1.shape[0], device=x.device) if w1 is not None else None
+    y0 = torch.empty(M, w0.shape[0], device=x.device); y1 = None if w1 is None else torch.empty(M, w1.shape[0], device=x.device)
     _check(lib().fbl_gemm_longk(x2.data_ptr(), x2.stride(0), w0.data_ptr(), w0.stride(0), y0.data_ptr(), w0.shape[0],
-                                w1.data_ptr() if w1 is not None else None, w1.stride(0) if w1 is not None else 0,
-                                y1.data_ptr() if w1 is not None else None, w1.shape[0] if w1 is not None else 0, M, K, _stream()))
+                                _p(w1), w1.stride(0) if w1 is not None else 0, _p(y1), w1.shape[0] if w1 is not None else 0, M, K, _stream()))
     return y0 if w1 is None else (y0, y1)
 
 
@@ -452,44 +478,53 @@ class _LinearLongK(torch.autograd.Function):
         return None, _sgemm(dy, 1, N, x, K, 1, N, K, M)                                        # [N, K] = d y^T [N, M] x [M, K]
 
 
+def route(x, w, bias=None, elu=False) -> str:
+    """The kernel fused.linear runs x [..., K] @ w [N, K]^T on -- 'sgemm', 'gemm_nt', 'gemm_longk' (forward only), '_LinearLongK', '_Linear'
+    (autograd) -- by the first rule below that holds; a product none of them covers RAISES.  It reads shapes, strides, dtypes, requires_grad
+    and the grad mode, never the device: tests/test_dmpo.py pins the learner's products on meta tensors."""
+    dim = x.dim(); K = x.shape[-1]; N = w.shape[0]
+    need = torch.is_grad_enabled() and (x.requires_grad or w.requires_grad or (bias is not None and bias.requires_grad))
+    # float32; x is 2-D, or has more dimensions, is forward only and runs as its rows (_rows2d: unit inner stride)
+    if x.dtype == w.dtype == torch.float32 and (dim == 2 or (dim > 2 and not need)):
+        small = x.numel() // K <= SMALL_GEMM_ROWS
+        w_unit = w.stride(1) == 1; x_unit = dim > 2 or x.stride(1) == 1
+        if w_unit and not small and not need:
+            # (few output columns, the 51 logits: one column tile would leave fbl_gemm_nt with 64 workgroups walking K one after the other)
+            return 'sgemm' if N <= 64 and K <= SMALL_GEMM_K else 'gemm_nt'
+        if w_unit and small and SMALL_GEMM_K < K <= LONGK_MAX and not elu and not (need and x.requires_grad):
+            return '_LinearLongK' if need else 'gemm_longk'
+        if small and K <= SMALL_GEMM_K:
+            # forward only (target networks, actors): nothing is saved, and w may be a column slice of a wider matrix (its row stride is passed)
+            return 'sgemm' if (not need and x_unit and w_unit) else '_Linear'
+        if x_unit and w_unit:
+            # any other 2-D shape (long reductions WITH an input gradient, many rows under autograd -- the test-suite's shapes): the K-split
+            # tile kernel covers every M, N, K, only slower off the shapes it was tuned for
+            return '_Linear'
+    raise LearnerLibError('fused.linear: no hand-written kernel covers x %s (%s, requires_grad=%s) @ w %s^T on the GPU; the learner never '
+                          'falls back to a BLAS library (shapes: DESIGN.md 5)' % (tuple(x.shape), x.dtype, x.requires_grad, tuple(w.shape)))
+
+
 def linear(x, w, bias=None, elu=False):
-    """x W^T (bias None) or ELU(x W^T + bias).  Every GPU shape of the learner step runs on a hand-written MFMA kernel (round 5: no BLAS
-    library call is left in it): up to SMALL_GEMM_ROWS rows and SMALL_GEMM_K columns -> fbl_sgemm (32 x 32 tile per workgroup, K split
-    over its waves, epilogue fused); more rows, forward only (the target critic's N x B = 5120 rows) -> fbl_gemm_nt (LDS-tiled, epilogue
-    fused); longer reductions at the learner's batch (the 741 / 800-column first layers) -> fbl_gemm_longk.  CPU tensors (the test-suite's
-    reference) are F.linear + the plain epilogue; a GPU shape none of the kernels covers RAISES -- there is no BLAS fall-through."""
+    """x W^T (bias None) or ELU(x W^T + bias).  GPU tensors run on the hand-written kernel `route` names, epilogue fused (a shape none of
+    them covers raises: there is no BLAS fall-through); CPU tensors (the test-suite's reference) are F.linear + the plain epilogue."""
     assert bias is None or elu, 'bias without activation is not used by the networks (the loss kernels add the output biases)'
-    if x.is_cuda and x.dtype == torch.float32 and w.stride(1) == 1:
-        need = torch.is_grad_enabled() and (x.requires_grad or w.requires_grad or (bias is not None and bias.requires_grad))
-        rows = x.numel() // x.shape[-1]
-        if rows > SMALL_GEMM_ROWS and not need:
-            if w.shape[0] <= 64 and x.shape[-1] <= SMALL_GEMM_K:
-                # few output columns (the 51 logits): one column tile would leave the LDS-tiled kernel with 64 workgroups walking K one
-                # after the other (11 us); the K-split kernel has 160 x 2 of them (8 us; the library: 5 us)
-                x2 = _rows2d(x)
-                return _sgemm(x2, x2.stride(0), 1, w, 1, w.stride(0), x2.shape[0], w.shape[0], x2.shape[1], 2 if elu else 0,
-                              bias if elu else None).view(*x.shape[:-1], w.shape[0])
-            return gemm_nt(x, w, bias if elu else None, 2 if elu else 0)
-        if x.dim() == 2 and rows <= SMALL_GEMM_ROWS and SMALL_GEMM_K < x.shape[1] <= LONGK_MAX and not elu and not (need and x.requires_grad):
-            return _LinearLongK.apply(x, w) if need else gemm_longk(x, w)
-    if x.is_cuda and x.dim() == 2 and x.shape[0] <= SMALL_GEMM_ROWS and x.shape[1] <= SMALL_GEMM_K and x.dtype == torch.float32:
-        if not (torch.is_grad_enabled() and (x.requires_grad or w.requires_grad or (bias is not None and bias.requires_grad))):
-            # forward only (target networks, actors): nothing is saved, and W may be a column slice of a wider matrix (row stride)
-            if x.stride(1) == 1 and w.stride(1) == 1:
-                return _sgemm(x, x.stride(0), 1, w, 1, w.stride(0), x.shape[0], w.shape[0], x.shape[1], 2 if elu else 0, bias if elu else None)
-        return _Linear.apply(x, w, bias, elu)
-    if x.is_cuda and x.dim() > 2 and x.dtype == torch.float32 and not (torch.is_grad_enabled() and (x.requires_grad or w.requires_grad or (bias is not None and bias.requires_grad))):
-        # forward-only [N, B, K] stacks with few rows (reduced test configurations of the target critic): the 2-D kernels on the flattened rows
-        return linear(_rows2d(x), w, bias, elu).view(*x.shape[:-1], w.shape[0])
-    if x.is_cuda and x.dim() == 2 and x.dtype == torch.float32 and w.dtype == torch.float32 and x.stride(1) == 1 and w.stride(1) == 1:
-        # any other 2-D shape (with gradients beyond the learner's own: long reductions WITH an input gradient, more than SMALL_GEMM_ROWS rows with
-        # autograd -- the test-suite's shapes): the K-split tile kernel covers every M, N, K, only slower off the shapes it was tuned for
-        return _Linear.apply(x, w, bias, elu)
-    if x.is_cuda:
-        raise LearnerLibError('fused.linear: no hand-written kernel covers x %s (%s, requires_grad=%s) @ w %s^T on the GPU; the learner never '
-                              'falls back to a BLAS library (shapes: DESIGN.md 5)' % (tuple(x.shape), x.dtype, x.requires_grad, tuple(w.shape)))
-    z = F.linear(x, w)
-    return bias_elu(z, bias) if elu else z
+    if not x.is_cuda:
+        z = F.linear(x, w)
+        return bias_elu(z, bias) if elu else z
+    r = route(x, w, bias, elu)
+    ep, b = (2, bias) if elu else (0, None)
+    if r == 'gemm_nt':
+        return gemm_nt(x, w, b, ep)
+    x2 = _rows2d(x) if (r == 'sgemm' or x.dim() > 2) else x
+    if r == 'sgemm':
+        y = _sgemm(x2, x2.stride(0), 1, w, 1, w.stride(0), x2.shape[0], w.shape[0], x2.shape[1], ep, b)
+    elif r == 'gemm_longk':
+        y = gemm_longk(x2, w)
+    elif r == '_LinearLongK':
+        y = _LinearLongK.apply(x2, w)
+    else:
+        y = _Linear.apply(x2, w, bias, elu)
+    return y if x.dim() == 2 else y.view(*x.shape[:-1], w.shape[0])
 
 
 class _GaussHead(torch.autograd.Function):
@@ -512,18 +547,27 @@ class _GaussHead(torch.autograd.Function):
         return dmean, dzs, db[0], db[1], None, None
 
 
-def _op(a, sai, sak, b, sbk, sbj, c=None, bias=None, epilogue=0, p0=0.0, p1=0.0, a_elu_of=None, a_rowsum=None):
-    """a_elu_of: the ELU layer's output, indexed like `a` -- operand A is a ELU'(output) (the backward pass's d z, never stored);
-    a_rowsum: receives the row sums of that operand (d bias of a d W product)."""
-    return _GemmOp(a.data_ptr(), b.data_ptr(), c.data_ptr() if c is not None else None, bias.data_ptr() if bias is not None else None,
-                   sai, sak, sbk, sbj, epilogue, p0, p1, a_elu_of.data_ptr() if a_elu_of is not None else None,
-                   a_rowsum.data_ptr() if a_rowsum is not None else None)
+def _heads_backward(dmean, dstd, h, wm, ws, std, mul, min_scale, need_dh):
+    """(d h, d Wm, d bm, d Ws, d bs) of the two heads on the torso output h: one element-wise launch (d zs + the two bias gradients), the two
+    weight gradients in one launch, and -- when need_dh -- d h = d mean Wm + d zs Ws in one launch (K split between the two products)."""
+    dmean = _f32c(dmean); dstd = _f32c(dstd); M, K = h.shape; D = wm.shape[0]; dev = h.device
+    dzs = torch.empty_like(std); db = zero_pool.take(2, D, device=dev)
+    _check(lib().fbl_gauss_head_bwd_std(dmean.data_ptr(), dstd.data_ptr(), std.data_ptr(), mul, min_scale, M, D, dzs.data_ptr(),
+                                        db[0].data_ptr(), db[1].data_ptr(), _stream()))
+    dwm = torch.empty(D, K, device=dev); dws = torch.empty(D, K, device=dev)
+    o0 = _op(dmean, 1, D, h, K, 1, dwm); o1 = _op(dzs, 1, D, h, K, 1, dws)                 # d W = d z^T h  ([D, K], reduction over M)
+    _check(lib().fbl_sgemm_pair(C.byref(o0), C.byref(o1), 0, K, D, K, M, _stream()))
+    dh = None
+    if need_dh:
+        dh = torch.empty(M, K, device=dev)
+        o0 = _op(dmean, D, 1, wm, K, 1, dh); o1 = _op(dzs, D, 1, ws, K, 1)                 # d h = d mean Wm + d zs Ws  ([M, K], reduction over D, twice)
+        _check(lib().fbl_sgemm_pair(C.byref(o0), C.byref(o1), 1, K, M, K, D, _stream()))
+    return dh, dwm, db[0], dws, db[1]
 
 
 class _GaussHeadLinear(torch.autograd.Function):
     """Both heads of the Gaussian policy in ONE launch (fbl_sgemm_pair: mean = h Wm^T + bm | stddev = softplus(h Ws^T + bs) mul + min);
-    backward: one element-wise launch (d zs + the two bias gradients), the two weight gradients in one launch, and d h = d mean Wm +
-    d zs Ws in one launch (K split between the two products)."""
+    backward: _heads_backward."""
 
     @staticmethod
     def forward(ctx, h, wm, bm, ws, bs, mul, min_scale):
@@ -537,19 +581,7 @@ class _GaussHeadLinear(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dmean, dstd):
         h, wm, ws, std = ctx.saved_tensors
-        dmean = _f32c(dmean); dstd = _f32c(dstd); M, K = h.shape; D = wm.shape[0]; dev = h.device
-        dzs = torch.empty_like(std); db = zero_pool.take(2, D, device=dev)
-        _check(lib().fbl_gauss_head_bwd_std(dmean.data_ptr(), dstd.data_ptr(), std.data_ptr(), ctx.mul, ctx.min_scale, M, D, dzs.data_ptr(),
-                                            db[0].data_ptr(), db[1].data_ptr(), _stream()))
-        dwm = torch.empty(D, K, device=dev); dws = torch.empty(D, K, device=dev)
-        o0 = _op(dmean, 1, D, h, K, 1, dwm); o1 = _op(dzs, 1, D, h, K, 1, dws)                 # d W = d z^T h  ([D, K], reduction over M)
-        _check(lib().fbl_sgemm_pair(C.byref(o0), C.byref(o1), 0, K, D, K, M, _stream()))
-        dh = None
-        if ctx.needs_input_grad[0]:
-            dh = torch.empty(M, K, device=dev)
-            o0 = _op(dmean, D, 1, wm, K, 1, dh); o1 = _op(dzs, D, 1, ws, K, 1)                 # d h = d mean Wm + d zs Ws  ([M, K], reduction over D, twice)
-            _check(lib().fbl_sgemm_pair(C.byref(o0), C.byref(o1), 1, K, M, K, D, _stream()))
-        return dh, dwm, db[0], dws, db[1], None, None
+        return (*_heads_backward(dmean, dstd, h, wm, ws, std, ctx.mul, ctx.min_scale, ctx.needs_input_grad[0]), None, None)
 
 
 def gauss_head_linear(h, wm, bm, ws, bs, mul, min_scale):
@@ -607,14 +639,9 @@ def replay_gather(u, size, capacity, fields):
 _POLICY_TAIL_MODE = 'auto'
 
 
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
-
-
 class _PolicyTail(torch.autograd.Function):
     """(mean, stddev) = heads(ELU(ELU(h1 W2^T + b2) W3^T + b3)) through fbl_policy_tail (activations in LDS from layer 2 to the heads);
-    backward: the same launches the layer-by-layer path issues (Gaussian head, bias-ELU, the d x | d W pairs), on the h2 / h3 the
-    forward kernel stored."""
+    backward: the layer-by-layer path's (_heads_backward, _elu_layer_backward twice), on the h2 / h3 the forward kernel stored."""
 
     @staticmethod
     def forward(ctx, h1, w2, b2, w3, b3, wm, bm, ws, bs, mul, min_scale):
@@ -623,8 +650,8 @@ class _PolicyTail(torch.autograd.Function):
         need = any(ctx.needs_input_grad[:9])
         h2 = torch.empty(M, H, device=dev) if need else None; h3 = torch.empty(M, H, device=dev) if need else None
         mean = torch.empty(M, D, device=dev); std = torch.empty(M, D, device=dev)
-        _check(lib().fbl_policy_tail(_ptr(h1), M, H, _ptr(w2), _ptr(b2), _ptr(w3), _ptr(b3), _ptr(wm), _ptr(bm), _ptr(ws), _ptr(bs), D, float(mul), float(min_scale),
-                                     _ptr(h2), _ptr(h3), _ptr(mean), _ptr(std), _stream()))
+        _check(lib().fbl_policy_tail(_p(h1), M, H, _p(w2), _p(b2), _p(w3), _p(b3), _p(wm), _p(bm), _p(ws), _p(bs), D, float(mul), float(min_scale),
+                                     _p(h2), _p(h3), _p(mean), _p(std), _stream()))
         if need:
             ctx.save_for_backward(h1, w2, h2, w3, h3, wm, ws, std)
         ctx.mul = float(mul); ctx.min_scale = float(min_scale)
@@ -633,31 +660,10 @@ class _PolicyTail(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dmean, dstd):
         h1, w2, h2, w3, h3, wm, ws, std = ctx.saved_tensors
-        dmean = _f32c(dmean); dstd = _f32c(dstd); M, H = h1.shape; D = wm.shape[0]; dev = h1.device; st = _stream()
-        # heads (as _GaussHeadLinear.backward)
-        dzs = torch.empty_like(std); db = zero_pool.take(2, D, device=dev)
-        _check(lib().fbl_gauss_head_bwd_std(dmean.data_ptr(), dstd.data_ptr(), std.data_ptr(), ctx.mul, ctx.min_scale, M, D, dzs.data_ptr(),
-                                            db[0].data_ptr(), db[1].data_ptr(), st))
-        dwm = torch.empty(D, H, device=dev); dws = torch.empty(D, H, device=dev)
-        o0 = _op(dmean, 1, D, h3, H, 1, dwm); o1 = _op(dzs, 1, D, h3, H, 1, dws)
-        _check(lib().fbl_sgemm_pair(C.byref(o0), C.byref(o1), 0, H, D, H, M, st))
-        dh = torch.empty(M, H, device=dev)
-        o0 = _op(dmean, D, 1, wm, H, 1, dh); o1 = _op(dzs, D, 1, ws, H, 1)
-        _check(lib().fbl_sgemm_pair(C.byref(o0), C.byref(o1), 1, H, M, H, D, st))
-        # the two ELU layers (as _Linear.backward): d z = d h ELU'(.), d bias = column sums, then d x | d W
-        grads = []
-        for hin, w, hout in ((h2, w3, h3), (h1, w2, h2)):
-            dz = torch.empty_like(dh); dbias = zero_pool.take(H, device=dev)
-            _check(lib().fbl_bias_elu_bwd(dh.data_ptr(), hout.data_ptr(), M, H, dz.data_ptr(), dbias.data_ptr(), st))
-            dx = torch.empty(M, H, device=dev); dw = torch.empty(H, H, device=dev)
-            if M == H:
-                o0 = _op(dz, H, 1, w, H, 1, dx); o1 = _op(dz, 1, H, hin, H, 1, dw)
-                _check(lib().fbl_sgemm_pair(C.byref(o0), C.byref(o1), 0, H, M, H, H, st))
-            else:
-                dx = _sgemm(dz, H, 1, w, H, 1, M, H, H); dw = _sgemm(dz, 1, H, hin, H, 1, H, H, M)
-            grads.append((dw, dbias)); dh = dx
-        (dw3, db3), (dw2, db2) = grads
-        return dh, dw2, db2, dw3, db3, dwm, db[0], dws, db[1], None, None
+        dh3, dwm, dbm, dws, dbs = _heads_backward(dmean, dstd, h3, wm, ws, std, ctx.mul, ctx.min_scale, True)
+        dh2, dw3, db3 = _elu_layer_backward(dh3, h3, h2, w3, True, True)
+        dh1, dw2, db2 = _elu_layer_backward(dh2, h2, h1, w2, True, True)
+        return dh1, dw2, db2, dw3, db3, dwm, dbm, dws, dbs, None, None
 
 
 def can_policy_tail(h1, torso_rest, head) -> bool:
@@ -678,11 +684,10 @@ def nstep_add(rep, obs, action, reward, discount, next_obs, first, last):
     obs, action, next_obs, reward, discount = (_f32c(x) for x in (obs, action, next_obs, reward, discount))
     first = first.contiguous(); last = last.contiguous()
     assert first.dtype == torch.bool and last.dtype == torch.bool and obs.shape == (rep.n_env, rep.obs.shape[1]) and action.shape == (rep.n_env, rep.action.shape[1])
-    p = lambda t: C.c_void_p(t.data_ptr())
     _check(lib().fbl_nstep_add(rep.n_env, rep.n, int(rep._t), float(rep.gamma), int(rep.capacity), int(rep.obs.shape[1]), int(rep.action.shape[1]),
-                               p(obs), p(action), p(reward), p(discount), p(next_obs), p(first), p(last),
-                               p(rep.w_obs), p(rep.w_act), p(rep.w_rew), p(rep.w_disc), p(rep.w_len), p(rep._head), p(rep._size), p(rep._inserted),
-                               p(rep.obs), p(rep.action), p(rep.reward), p(rep.discount), p(rep.next_obs), p(rep._plan_i), p(rep._plan_f), _stream()))
+                               _p(obs), _p(action), _p(reward), _p(discount), _p(next_obs), _p(first), _p(last),
+                               _p(rep.w_obs), _p(rep.w_act), _p(rep.w_rew), _p(rep.w_disc), _p(rep.w_len), _p(rep._head), _p(rep._size), _p(rep._inserted),
+                               _p(rep.obs), _p(rep.action), _p(rep.reward), _p(rep.discount), _p(rep.next_obs), _p(rep._plan_i), _p(rep._plan_f), _stream()))
 
 
 # ------------------------------------------------------------------ clipped Adam on one flat buffer
@@ -720,11 +725,11 @@ class FlatAdam:
         assert acc == self.p.numel(), 'gradient list does not cover the flat buffer'
         if self.p.is_cuda:
             n = len(grads)
-            src = (C.c_void_p*n)(*[(_f32c(g).data_ptr() if g is not None else None) for g in grads])
+            src = (C.c_void_p*n)(*[_p(None if g is None else _f32c(g)) for g in grads])
             if self._norms_ready:                                  # a norm pass without its update (an interrupted step): start clean
                 self._norms.zero_()
             _check(lib().fbl_gather_flat(src, (C.c_int64*n)(*ends), n, self.g.data_ptr(), len(self.ends), self._c['seg_end'],
-                                         self._norms.data_ptr() if with_norms else None, self.step_t.data_ptr(), _stream()))
+                                         _p(self._norms if with_norms else None), self.step_t.data_ptr(), _stream()))
             self._norms_ready = bool(with_norms)
             return
         lo = 0

@@ -115,3 +115,50 @@ def test_python_field_table_matches_header():
     ids = {name: int(v) for name, v in re.findall(r'\bFB_([A-Z0-9_]+)\s*=\s*(\d+)', block)}
     assert len(ids) >= 40 and ids['QPOS'] == 0 and ids['CONTACT_FORCE'] == 39
     assert {name: f[0] for name, f in engine.FIELDS.items()} == ids
+
+
+def _learner_header():
+    hdr = open(os.path.join(ROOT, 'include', 'flybody_learner.h')).read()
+    return re.sub(r'/\*.*?\*/', '', hdr, flags=re.S)
+
+
+_SCALARS = {'int': C.c_int, 'int32_t': C.c_int, 'int64_t': C.c_int64, 'float': C.c_float, 'size_t': C.c_size_t}
+
+
+def _ctype_of(decl, base=None):
+    """ctypes kind of one C parameter / field declarator / return type: any pointer is c_void_p, a scalar the kind of its type name (`base`
+    for the later declarators of 'const float *a, *b')."""
+    return C.c_void_p if '*' in decl else _SCALARS[base or [t for t in re.findall(r'\w+', decl) if t != 'const'][0]]
+
+
+def _struct_fields(hdr, name):
+    """[(field, ctypes kind)] of `typedef struct name { ... } name;`, in order."""
+    body = re.search(r'typedef\s+struct\s+%s\s*\{(.*?)\}\s*%s\s*;' % (name, name), hdr, flags=re.S).group(1)
+    out = []
+    for decl in filter(None, (d.strip() for d in body.split(';'))):
+        base = [t for t in re.findall(r'\w+', decl) if t != 'const'][0]
+        out += [(re.search(r'(\w+)\s*$', piece).group(1), _ctype_of(piece, base)) for piece in decl.split(',')]
+    return out
+
+
+def test_learner_ctypes_declarations_match_header():
+    """fused._SIGNATURES against the prototypes of include/flybody_learner.h: an entry for every function (and for every lib().fbl_* call of
+    fused.py), as many argument types as parameters, each of the parameter's kind, the return type; and the two Structure mirrors field by
+    field.  A miscounted pointer would otherwise stay silent until it corrupts memory on a GPU."""
+    from flybody_amd.dmpo import fused
+    hdr = _learner_header()
+    protos = re.findall(r'([\w\s\*]+?)\b(fbl_\w+)\s*\(([^()]*)\)\s*;', re.sub(r'typedef\s+struct.*?\}\s*\w+\s*;', '', hdr, flags=re.S))
+    assert len(protos) >= 24 and {'fbl_sgemm_op', 'fbl_mpo_loss', 'fbl_nstep_add'} <= {name for _, name, _ in protos}
+    for ret, name, params in protos:
+        assert name in fused._SIGNATURES, f'{name}: declared in flybody_learner.h, no ctypes declaration'
+        restype, argtypes = fused._SIGNATURES[name]
+        params = [] if params.strip() == 'void' else params.split(',')
+        assert len(argtypes) == len(params), f'{name}: {len(argtypes)} argument types for {len(params)} parameters'
+        for i, (t, prm) in enumerate(zip(argtypes, params)):
+            assert t is _ctype_of(prm), f'{name}: parameter {i} ({prm.strip()}) declared as {t.__name__}'
+        assert restype is (C.c_char_p if '*' in ret else _ctype_of(ret)), f'{name}: return type {ret.strip()} declared as {restype.__name__}'
+    assert set(fused._SIGNATURES) == {name for _, name, _ in protos}
+    called = set(re.findall(r'lib\(\)\.(fbl_\w+)', open(os.path.join(ROOT, 'flybody_amd', 'dmpo', 'fused.py')).read()))
+    assert len(called) >= 20 and called <= set(fused._SIGNATURES), called - set(fused._SIGNATURES)
+    for struct, mirror in (('fbl_gemm_op', fused._GemmOp), ('fbl_mpo_args', fused._MpoArgs)):
+        assert [(n, t) for n, t in mirror._fields_] == _struct_fields(hdr, struct), struct

@@ -251,6 +251,48 @@ def test_learner_python_reads_only_switches_something_sets():
     assert set(found) == KEPT_ENVIRONMENT_SWITCHES, sorted(found)
 
 
+def test_linear_routes_of_the_reference_configuration():
+    """Which hand-written kernel every product of the learner step and of the actors reaches (fused.route; obs 741, action 59, B 256,
+    N 20), on meta tensors: a routing slip would otherwise show only as a slower step on a GPU, or as the LearnerLibError at the bottom."""
+    from flybody_amd.dmpo import fused
+
+    def x(*shape, grad=False):
+        return torch.empty(*shape, device='meta', requires_grad=grad)
+
+    def w(n, k, ld=None, off=0, grad=False):                    # [n, k] weights, or columns off .. off + k of an [n, ld] matrix
+        return torch.empty(n, ld or k, device='meta', requires_grad=grad)[:, off:off + k]
+
+    def b(n):
+        return torch.empty(n, device='meta', requires_grad=True)
+
+    route = fused.route
+    # online networks: weights (and biases) require gradients; the observations and the critic's [obs | action] input do not
+    assert route(x(256, 741), w(256, 741, grad=True)) == '_LinearLongK' and route(x(256, 800), w(512, 800, grad=True)) == '_LinearLongK'
+    for k, n in ((256, 256), (512, 512), (512, 256)):
+        assert route(x(256, k, grad=True), w(n, k, grad=True), b(n), elu=True) == '_Linear'
+    assert route(x(256, 256, grad=True), w(51, 256, grad=True)) == '_Linear'
+    # ... and with a gradient into x itself every 2-D product is _Linear's
+    for (m, k), n, elu in (((256, 741), 256, False), ((256, 800), 512, True), ((4096, 741), 256, False), ((37, 203), 45, False)):
+        assert route(x(m, k, grad=True), w(n, k, grad=True), b(n) if elu else None, elu=elu) == '_Linear'
+    with torch.no_grad():                                       # target networks, actors
+        wc = w(512, 800, grad=True)                             # the critic's first layer: observation | action columns
+        assert route(x(256, 256), w(256, 256, grad=True), b(256), elu=True) == 'sgemm'
+        assert route(x(256, 741), w(256, 741)) == 'gemm_longk' and route(x(256, 741), wc[:, :741]) == 'gemm_longk'
+        assert wc[:, 741:].stride() == (800, 1) and route(x(20, 256, 59), wc[:, 741:]) == 'gemm_nt'
+        assert route(x(20, 256, 512), w(512, 512), b(512), elu=True) == 'gemm_nt' and route(x(20, 256, 512), w(256, 512), b(256), elu=True) == 'gemm_nt'
+        assert route(x(4096, 741), w(256, 741)) == 'gemm_nt'
+        assert route(x(20, 256, 256), w(51, 256)) == 'sgemm' and route(x(5120, 256), w(51, 256)) == 'sgemm'      # (on the 5120 rows)
+        assert route(x(4, 8, 16), w(32, 16)) == route(x(32, 16), w(32, 16)) == 'sgemm'
+        assert route(x(300, 200), w(200, 100).t()) == '_Linear'                                                      # w inner stride != 1
+        for bad in ((x(256, 741).double(), w(256, 741)), (x(256, 256), w(256, 256).double())):
+            with pytest.raises(fused.LearnerLibError):
+                route(*bad)
+    with pytest.raises(fused.LearnerLibError):
+        route(x(20, 256, 59), w(512, 59, grad=True))
+    # the limits the rows above sit on either side of
+    assert (fused.SMALL_GEMM_ROWS, fused.SMALL_GEMM_K, fused.LONGK_MAX) == (1024, 512, 832)
+
+
 WORKER = r"""
 import os, sys
 sys.path.insert(0, %(root)r)

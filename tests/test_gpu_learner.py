@@ -436,7 +436,7 @@ def test_policy_tail_kernel(M, monkeypatch):
     _close(mean, mean_r, rtol=2e-5, atol=2e-5); _close(std, std_r, rtol=2e-5, atol=2e-5)
     with torch.no_grad():                      # forward-only path (target networks, actors): nothing stored
         m2, s2 = pol(obs)
-    # (above 1024 rows the forward-only first layer runs on fbl_gemm_nt while the grad-enabled path keeps the library GEMM: equal to
+    # (above 1024 rows the forward-only first layer runs on fbl_gemm_nt while the grad-enabled one runs _Linear on fbl_sgemm: equal to
     #  rounding there, bit-equal at the learner's batch sizes)
     if M <= 1024:
         assert torch.equal(m2, mean) and torch.equal(s2, std)
@@ -446,6 +446,13 @@ def test_policy_tail_kernel(M, monkeypatch):
         gm = torch.randn(M, 59, device=dev); gs = torch.randn(M, 59, device=dev)
         (mean*gm).sum().add((std*gs).sum()).backward()
         (mean_r*gm.double()).sum().add((std_r*gs.double()).sum()).backward()
+        for (n, p), (_, q) in zip(pol.named_parameters(), ref.named_parameters()):
+            _close(p.grad, q.grad, rtol=2e-4, atol=2e-4*float(q.grad.abs().max()) + 1e-7), n
+        # the tail's two ELU layers follow the fused-ELU-backward switch (off by default) like every other ELU layer: same gradients
+        monkeypatch.setattr(fused, '_FUSED_ELU_BWD', True)
+        for p in pol.parameters(): p.grad = None
+        mean, std = pol(obs)
+        (mean*gm).sum().add((std*gs).sum()).backward()
         for (n, p), (_, q) in zip(pol.named_parameters(), ref.named_parameters()):
             _close(p.grad, q.grad, rtol=2e-4, atol=2e-4*float(q.grad.abs().max()) + 1e-7), n
 

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """The learner's library-routed GEMM shapes, one by one: rocBLAS (F.linear / matmul) against the hand-written kernels (fbl_sgemm with its
-size limits lifted, fbl_gemm_nt when present), microseconds per call inside a HIP graph of 20 back-to-back calls.
+size limits lifted, fbl_gemm_nt, fbl_gemm_longk), microseconds per call inside a HIP graph of 20 back-to-back calls.
     python tools/gemm_shapes_probe.py"""
 import os, sys, json
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..'))
@@ -36,12 +36,11 @@ for name, M, N, K, lda, ldb in shapes:
     r['rocblas_us'] = bench(lambda: F.linear(x, w))
     r['rocblas+bias_elu_us'] = bench(lambda: fused.bias_elu(F.linear(x, w), bias))
     r['fbl_sgemm_us'] = bench(lambda: fused._sgemm(x, x.stride(0), 1, w, 1, w.stride(0), M, N, K, 2, bias))
-    if hasattr(fused, 'gemm_nt'):
-        ep = 0 if 'no epilogue' in name else 2
-        r['fbl_gemm_nt_us'] = bench(lambda: fused.gemm_nt(x, w, bias if ep else None, ep))
-        ref = F.linear(x.double(), w.double()); ref = F.elu(ref + bias.double()) if ep else ref
-        r['fbl_gemm_nt_err'] = float((fused.gemm_nt(x, w, bias if ep else None, ep).double() - ref).abs().max()/ref.abs().max())
-    if hasattr(fused, 'gemm_longk') and K <= 832 and (M <= 1024 or N <= 64):
+    ep = 0 if 'no epilogue' in name else 2
+    r['fbl_gemm_nt_us'] = bench(lambda: fused.gemm_nt(x, w, bias if ep else None, ep))
+    ref = F.linear(x.double(), w.double()); ref = F.elu(ref + bias.double()) if ep else ref
+    r['fbl_gemm_nt_err'] = float((fused.gemm_nt(x, w, bias if ep else None, ep).double() - ref).abs().max()/ref.abs().max())
+    if K <= fused.LONGK_MAX and (M <= 1024 or N <= 64):
         r['fbl_gemm_longk_us'] = bench(lambda: fused.gemm_longk(x, w))
         ref = F.linear(x.double(), w.double())
         r['fbl_gemm_longk_err'] = float((fused.gemm_longk(x, w).double() - ref).abs().max()/ref.abs().max())
@@ -53,7 +52,4 @@ for name, M, N, K in [('policy L1 dW 256x741 (M 256)', 256, 256, 741), ('critic 
     r = {'flop_G': 2*M*N*K/1e9}
     r['rocblas_us'] = bench(lambda: dz.t().mm(x))
     r['fbl_sgemm_us'] = bench(lambda: fused._sgemm(dz, 1, N, x, K, 1, N, K, M))
-    if hasattr(fused, 'gemm_tn'):
-        r['fbl_gemm_tn_us'] = bench(lambda: fused.gemm_tn(dz, x))
-        ref = dz.double().t().mm(x.double()); r['fbl_gemm_tn_err'] = float((fused.gemm_tn(dz, x).double() - ref).abs().max()/ref.abs().max())
     out[name] = r; print(name, json.dumps({k: (round(v, 3) if not k.endswith('err') else float('%.2e' % v)) for k, v in r.items()}), flush=True)
