@@ -558,8 +558,10 @@ __global__ void k_probe_xcc(unsigned* mask) { if (threadIdx.x == 0) atomicOr(mas
 #endif
 
 
-template <typename real>
-__device__ __forceinline__ void fly_kernel(const DevModel<real>* Mp, const Batch<real>& B, const float* action, const int* env_ids, int mode, int nsub, int nslot) {
+// FORCES: the step kernel with applied forces (k_step_forces; F = the batch's two force arrays, fb_forces.hpp).  k_fly and k_fly_reset instantiate it false.
+template <typename real, bool FORCES = false>
+__device__ __forceinline__ void fly_kernel(const DevModel<real>* Mp, const Batch<real>& B, const float* action, const int* env_ids, int mode, int nsub, int nslot,
+                                           const ForceArgs<real> F = ForceArgs<real>()) {
   // per-wave (per-environment) hot arrays
   constexpr int EPB = LdsCfg<real>::EPB;
   __shared__ real s_pool[EPB][LdsCfg<real>::POOL];          // [factor row | Delassus matrix | solve vector] of each environment
@@ -668,8 +670,11 @@ __device__ __forceinline__ void fly_kernel(const DevModel<real>* Mp, const Batch
 #if defined(FB_PROFILE) && !defined(FB_EMULATE)
       const long long tw1_ = wall_clock64();       // (tools/ticket_trace.py) per environment: wait for the predecessor, first start, last end, busy ticks
 #endif
-      const bool was_reset = d_run(M, w, env, mode, nsub, nslot, (int*)nullptr, action ? action + (size_t)env*M.nact : nullptr, obs, B.reward + env,
-                                   B.discount + env, B.step_type + env, lane, (round == 0 ? 1 : 0) | (round == nunit - 1 ? 2 : 0) | (tkhalf == 1 ? 4 : 0) | (tkhalf == 2 ? 8 : 0) | (late ? 16 : 0));
+      const real *qf_ = nullptr, *xf_ = nullptr;
+      if constexpr (FORCES) { qf_ = F.qfrc_applied + (size_t)env*M.nv; xf_ = F.xfrc_applied + (size_t)env*6*M.nbody; }
+      const bool was_reset = d_run<real, FORCES>(M, w, env, mode, nsub, nslot, (int*)nullptr, action ? action + (size_t)env*M.nact : nullptr, obs, B.reward + env,
+                                   B.discount + env, B.step_type + env, lane, (round == 0 ? 1 : 0) | (round == nunit - 1 ? 2 : 0) | (tkhalf == 1 ? 4 : 0) | (tkhalf == 2 ? 8 : 0) | (late ? 16 : 0),
+                                   -1, qf_, xf_);
 #ifndef FB_EMULATE
       // Release.  What the next holder of this environment (a wave of the SAME XCD: environments are bound to XCDs) must see is this
       // wave's global stores.  On gfx942 / gfx950 the vector L1 is write-through and an XCD has ONE L2, so "visible to the XCD" =
@@ -712,8 +717,10 @@ __device__ __forceinline__ void fly_kernel(const DevModel<real>* Mp, const Batch
     for (int i = lane; i < LdsCfg<real>::POOL; i += FB_WAVE) w.lLD[i] = pk[i];
     SYNC();
   } else if (lane == 0) { w.istate()[IS_PRIO] = 0; if (mode == MODE_STEP || mode == MODE_RESET) w.istate()[IS_WARN] = 0; }
-  d_run(M, w, env, only >= 0 ? (int)MODE_STEP : mode, nsub, nslot, only >= 0 ? (int*)nullptr : B.sched, action ? action + (size_t)env*M.nact : nullptr, obs, B.reward + env,
-        B.discount + env, B.step_type + env, lane, -1, only);
+  const real *qf_ = nullptr, *xf_ = nullptr;
+  if constexpr (FORCES) { qf_ = F.qfrc_applied + (size_t)env*M.nv; xf_ = F.xfrc_applied + (size_t)env*6*M.nbody; }
+  d_run<real, FORCES>(M, w, env, only >= 0 ? (int)MODE_STEP : mode, nsub, nslot, only >= 0 ? (int*)nullptr : B.sched, action ? action + (size_t)env*M.nact : nullptr, obs, B.reward + env,
+        B.discount + env, B.step_type + env, lane, -1, only, qf_, xf_);
   if (only >= 0) {
     SYNC();
     FB_GLOBAL real* pk = (FB_GLOBAL real*)(B.park + (size_t)env*LdsCfg<real>::POOL);
@@ -743,6 +750,14 @@ __global__ void __launch_bounds__(FB_WAVE*LdsCfg<real>::EPB, LdsCfg<real>::WAVES
 template <typename real>
 __global__ void __launch_bounds__(FB_WAVE*LdsCfg<real>::EPB, LdsCfg<real>::WAVES_PER_SIMD) k_fly_reset(const DevModel<real>* Mp, Batch<real> B, const int* env_ids, int nsub, int nslot) {
   fly_kernel<real>(Mp, B, nullptr, env_ids, (int)MODE_RESET, nsub, nslot);
+}
+
+// The step kernel with external forces (fb_forces.hpp): the same device code with the applied-force stage compiled in, under k_fly's launch bounds
+// and on its LDS layout, ticket scheduler included.  The two arrays are an extra kernel argument, so k_fly's own arguments stay where they are.
+// launch() uses it for control steps, substeps and forward evaluations while the batch's force arrays are allocated.
+template <typename real>
+__global__ void __launch_bounds__(FB_WAVE*LdsCfg<real>::EPB, LdsCfg<real>::WAVES_PER_SIMD) k_step_forces(const DevModel<real>* Mp, Batch<real> B, const float* action, const int* env_ids, int mode, int nsub, int nslot, ForceArgs<real> F) {
+  fly_kernel<real, true>(Mp, B, action, env_ids, mode, nsub, nslot, F);
 }
 
 // Launch order for the next control step: environments sorted by the duration of their last step, longest first (counting
@@ -875,6 +890,8 @@ struct fb_batch {
   double* ik_err = nullptr; int* ik_steps = nullptr;      // fb_batch_ik results (FB_IK_ERR / FB_IK_STEPS), allocated on the first call
   void* ik_buf = nullptr; size_t ik_buf_bytes = 0;        // ... its tables and targets (grown as needed)
   double* inv_qfrc = nullptr; double* inv_cforce = nullptr;      // fb_batch_inverse results (FB_QFRC_INVERSE / FB_CONTACT_FORCE), allocated on the first call
+  void *qfrc_applied = nullptr, *xfrc_applied = nullptr;         // applied forces (FB_QFRC_APPLIED / FB_XFRC_APPLIED) at the batch's precision: both allocated by the first
+                                                                 // fb_batch_set / fb_batch_device_ptr of either, freed by fb_batch_clear_forces; allocated = k_step_forces steps the batch
 };
 
 template <typename real, typename T, typename P>
@@ -1084,7 +1101,12 @@ static int batch_create_impl(fb_batch* b) {
     if (with_model(b, [&](auto& M) {
           using real = decltype(M.timestep);
           int nb = 0;
-          HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_fly<real>, FB_WAVE*LdsCfg<real>::EPB, 0)); b->slots = nb*prop.multiProcessorCount*LdsCfg<real>::EPB;
+          HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_fly<real>, FB_WAVE*LdsCfg<real>::EPB, 0));
+          // launch_fly may launch k_step_forces instead (applied forces): same launch bounds and LDS layout, so the same residency
+          // (tests/test_forces_resources.py); the slot count that decides for tickets is the smaller of the two all the same
+          int nbf = 0;
+          HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nbf, k_step_forces<real>, FB_WAVE*LdsCfg<real>::EPB, 0));
+          b->slots = std::min(nb, nbf)*prop.multiProcessorCount*LdsCfg<real>::EPB;
           return 0; })) return -1;
     unsigned* dmask; unsigned hmask = 0;
     HIPCHK(hipMalloc((void**)&dmask, sizeof(unsigned))); HIPCHK(hipMemset(dmask, 0, sizeof(unsigned)));
@@ -1128,7 +1150,7 @@ extern "C" void fb_batch_destroy(fb_batch* b) {
   if (!b) return;
   (void)hipSetDevice(b->device);
   for (void* p : b->allocs) (void)hipFree(p);
-  void* frees_[] = {b->rarena, b->iarena, b->obs, b->reward, b->discount, b->step_type, b->d_ids, b->sched, b->cost, b->order, b->ref_qpos, b->ref_qvel, b->dM, b->tick, b->done, b->sched_err, b->park, b->probe_word, b->torder, b->ik_err, b->ik_steps, b->ik_buf, b->inv_qfrc, b->inv_cforce};
+  void* frees_[] = {b->rarena, b->iarena, b->obs, b->reward, b->discount, b->step_type, b->d_ids, b->sched, b->cost, b->order, b->ref_qpos, b->ref_qvel, b->dM, b->tick, b->done, b->sched_err, b->park, b->probe_word, b->torder, b->ik_err, b->ik_steps, b->ik_buf, b->inv_qfrc, b->inv_cforce, b->qfrc_applied, b->xfrc_applied};
   for (void* p : frees_) (void)hipFree(p);
 
   if (b->ev0) (void)hipEventDestroy(b->ev0);
@@ -1263,7 +1285,7 @@ extern "C" int fb_batch_set_flight_dataset(fb_batch* b, const fb_flight_dataset*
   });
 }
 
-// the k_fly / k_fly_reset launch of launch()
+// the k_fly / k_fly_reset / k_step_forces launch of launch()
 template <typename real>
 static void launch_fly(fb_batch* b, int mode, const float* action, const int* ids, int n, int nsub, hipStream_t st, bool tickets, const int* tord) {
   constexpr int EPB = LdsCfg<real>::EPB;
@@ -1271,6 +1293,10 @@ static void launch_fly(fb_batch* b, int mode, const float* action, const int* id
   Batch<real> B = {(real*)b->rarena, b->iarena, b->obs, b->reward, b->discount, b->step_type, b->n_env, b->nobs, b->use_prio ? b->sched : nullptr, b->cost,
                    tickets ? b->tick : nullptr, b->done, b->nq, b->sched_err, tord, (real*)b->park};
   if (mode == MODE_RESET) hipLaunchKernelGGL((k_fly_reset<real>), dim3((n + EPB - 1)/EPB), dim3(FB_WAVE*EPB), 0, st, dM, B, ids, nsub, n);
+  else if (b->qfrc_applied) {
+    const ForceArgs<real> F = {(const real*)b->qfrc_applied, (const real*)b->xfrc_applied};
+    hipLaunchKernelGGL((k_step_forces<real>), dim3((n + EPB - 1)/EPB), dim3(FB_WAVE*EPB), 0, st, dM, B, action, ids, mode, nsub, n, F);
+  }
   else hipLaunchKernelGGL((k_fly<real>), dim3((n + EPB - 1)/EPB), dim3(FB_WAVE*EPB), 0, st, dM, B, action, ids, mode, nsub, n);
 }
 
@@ -1391,6 +1417,7 @@ extern "C" int fb_batch_synchronize(fb_batch* b, void* stream) {
 extern "C" int fb_batch_stage(fb_batch* b, int stage_word, const float* action, void* stream) {
   if (!b || stage_word < 0) return fail("fb_batch_stage: bad arguments");
   if (check_ready(b, "fb_batch_stage", false)) return -1;
+  if (b->qfrc_applied) return fail("fb_batch_stage: single-stage profiling runs k_fly, which knows no applied forces; call fb_batch_clear_forces first");
   HIPCHK(hipSetDevice(b->device));
   const size_t pool = with_model(b, [](auto& M) { return sizeof(M.timestep)*LdsCfg<decltype(M.timestep)>::POOL; });
   if (alloc_zeroed_once(&b->park, (size_t)b->n_env*pool)) return -1;
@@ -1499,7 +1526,7 @@ extern "C" int fb_batch_inverse(fb_batch* b, int flags, void* stream) {
 }
 
 // ------------------------------------------------------------------ field access
-enum FieldKind { REAL_ARENA, INT_ARENA, F32_ARRAY, I32_ARRAY, F64_ARRAY };
+enum FieldKind { REAL_ARENA, INT_ARENA, F32_ARRAY, I32_ARRAY, F64_ARRAY, REAL_ARRAY /* caller-owned input at the batch's precision: the applied forces */ };
 // rows of `width` at offset `off` of an arena row, or an array [n_env][width] of its own at `base`; `unset`: why such an array is not
 // allocated yet (the ones allocated with the batch need none)
 struct FieldDesc { FieldKind kind; size_t off, width; void* base = nullptr; const char* unset = nullptr; };
@@ -1509,6 +1536,7 @@ static int field_desc(fb_batch* b, int field, FieldDesc* f) {
   const char* no_ref = "fb_batch_get: field not allocated yet (set a reference first)";
   const char* no_ik = "fb_batch_get: field not allocated yet (run fb_batch_ik first)";
   const char* no_inv = "fb_batch_get: field not allocated yet (run fb_batch_inverse first)";
+  const char* no_frc = "fb_batch_get: no applied forces (fb_batch_set / fb_batch_device_ptr of FB_QFRC_APPLIED or FB_XFRC_APPLIED allocates them)";
   switch (field) {
     case FB_QPOS: *f = {REAL_ARENA, o.qpos, (size_t)m->nq}; break;
     case FB_QVEL: *f = {REAL_ARENA, o.qvel, (size_t)m->nv}; break;
@@ -1549,9 +1577,42 @@ static int field_desc(fb_batch* b, int field, FieldDesc* f) {
     case FB_IK_STEPS: *f = {I32_ARRAY, 0, 2, b->ik_steps, no_ik}; break;
     case FB_QFRC_INVERSE: *f = {F64_ARRAY, 0, (size_t)m->nv, b->inv_qfrc, no_inv}; break;
     case FB_CONTACT_FORCE: *f = {F64_ARRAY, 0, (size_t)3*FB_MAXCON_, b->inv_cforce, no_inv}; break;
+    case FB_QFRC_APPLIED: *f = {REAL_ARRAY, 0, (size_t)m->nv, b->qfrc_applied, no_frc}; break;
+    case FB_XFRC_APPLIED: *f = {REAL_ARRAY, 0, (size_t)6*m->nbody, b->xfrc_applied, no_frc}; break;
     default: return fail("unknown field");
   }
   return 0;
+}
+
+// The applied-force arrays, zeroed, on the first fb_batch_set / fb_batch_device_ptr of either field.  From then on launch() steps the batch with
+// k_step_forces.  (Both or neither: the kernel takes them as one argument.)
+static int alloc_forces(fb_batch* b) {
+  if (b->qfrc_applied && b->xfrc_applied) return 0;
+  const size_t rs = real_size(b);
+  HIPCHK(hipDeviceSynchronize());
+  void *q = nullptr, *x = nullptr;
+  const size_t nq_ = (size_t)b->n_env*b->m->nv*rs, nx_ = (size_t)b->n_env*6*b->m->nbody*rs;
+  if (hipMalloc(&q, nq_) != hipSuccess || hipMalloc(&x, nx_) != hipSuccess || hipMemset(q, 0, nq_) != hipSuccess || hipMemset(x, 0, nx_) != hipSuccess) {
+    (void)hipFree(q); (void)hipFree(x); (void)hipGetLastError();
+    return fail("applied forces: device allocation failed");
+  }
+  HIPCHK(hipDeviceSynchronize());                      // (the zeroes are there before a launch on any stream reads them)
+  b->qfrc_applied = q; b->xfrc_applied = x;
+  return 0;
+}
+
+extern "C" int fb_batch_clear_forces(fb_batch* b) {
+  if (!b) return fail("fb_batch_clear_forces: null batch");
+  HIPCHK(hipSetDevice(b->device));
+  HIPCHK(hipDeviceSynchronize());                      // (a launch in flight may still read the arrays)
+  (void)hipFree(b->qfrc_applied); (void)hipFree(b->xfrc_applied);
+  b->qfrc_applied = b->xfrc_applied = nullptr;
+  return 0;
+}
+
+extern "C" int fb_batch_forces_active(const fb_batch* b) {
+  if (!b) return fail("fb_batch_forces_active: null batch");
+  return b->qfrc_applied ? 1 : 0;
 }
 
 // a REAL_ARENA field of every environment, between the arena (the batch's precision) and FP64 rows [n_env][width] on the host
@@ -1602,6 +1663,15 @@ extern "C" int fb_batch_get(fb_batch* b, int field, void* dst, size_t bytes) {
   } else if (f.kind == INT_ARENA) {
     if (bytes != (size_t)n*f.width*sizeof(int)) return fail("fb_batch_get: size mismatch");
     HIPCHK(hipMemcpy2D(dst, f.width*4, (char*)b->iarena + f.off*4, (size_t)b->off.nint*4, f.width*4, n, hipMemcpyDeviceToHost));
+  } else if (f.kind == REAL_ARRAY) {
+    if (!f.base) return fail(f.unset);
+    if (bytes != (size_t)n*f.width*sizeof(double)) return fail("fb_batch_get: size mismatch (physics fields are returned as FP64)");
+    return with_model(b, [&](auto& M) {
+      std::vector<decltype(M.timestep)> tmp((size_t)n*f.width);
+      HIPCHK(hipMemcpy(tmp.data(), f.base, tmp.size()*sizeof(tmp[0]), hipMemcpyDeviceToHost));
+      std::copy(tmp.begin(), tmp.end(), (double*)dst);
+      return 0;
+    });
   } else {
     if (!f.base) return fail(f.unset);
     if (bytes != (size_t)n*f.width*(f.kind == F64_ARRAY ? 8 : 4)) return fail("fb_batch_get: size mismatch");
@@ -1623,6 +1693,21 @@ extern "C" int fb_batch_set(fb_batch* b, int field, const void* src, size_t byte
   } else if (f.kind == INT_ARENA) {
     if (bytes != (size_t)n*f.width*sizeof(int)) return fail("fb_batch_set: size mismatch");
     HIPCHK(hipMemcpy2D((char*)b->iarena + f.off*4, (size_t)b->off.nint*4, src, f.width*4, f.width*4, n, hipMemcpyHostToDevice));
+  } else if (f.kind == REAL_ARRAY) {
+    // applied forces: validated on the host (size, finite), then both arrays exist and k_step_forces steps the batch
+    const char* name = field == FB_QFRC_APPLIED ? "FB_QFRC_APPLIED" : "FB_XFRC_APPLIED";
+    if (bytes != (size_t)n*f.width*sizeof(double))
+      return fail(std::string("fb_batch_set: size mismatch: ") + name + " is [n_env][" + std::to_string(f.width) + "] FP64 = " + std::to_string((size_t)n*f.width*sizeof(double)) + " bytes, got " + std::to_string(bytes));
+    const double* v = (const double*)src;
+    for (size_t k = 0; k < (size_t)n*f.width; k++)
+      if (!std::isfinite(v[k])) return fail(std::string("fb_batch_set: ") + name + " of environment " + std::to_string(k/f.width) + " is not finite");
+    if (alloc_forces(b)) return -1;
+    void* dev = field == FB_QFRC_APPLIED ? b->qfrc_applied : b->xfrc_applied;
+    return with_model(b, [&](auto& M) {
+      const std::vector<decltype(M.timestep)> tmp(v, v + (size_t)n*f.width);
+      HIPCHK(hipMemcpy(dev, tmp.data(), tmp.size()*sizeof(tmp[0]), hipMemcpyHostToDevice));
+      return 0;
+    });
   } else return fail("fb_batch_set: field is read-only");
   return 0;
 }
@@ -1634,6 +1719,9 @@ extern "C" void* fb_batch_device_ptr(fb_batch* b, int field) {
     case FB_REWARD: return b->reward;
     case FB_DISCOUNT: return b->discount;
     case FB_STEP_TYPE: return b->step_type;
+    case FB_QFRC_APPLIED: case FB_XFRC_APPLIED:        // (allocates both arrays on first use: the batch is stepped by k_step_forces from then on)
+      if (hipSetDevice(b->device) != hipSuccess || alloc_forces(b)) return nullptr;
+      return field == FB_QFRC_APPLIED ? b->qfrc_applied : b->xfrc_applied;
     default: return nullptr;
   }
 }

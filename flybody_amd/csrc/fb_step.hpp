@@ -4,6 +4,7 @@
 #include "fb_types.hpp"
 #include "fb_math.hpp"
 #include "fb_smooth.hpp"
+#include "fb_forces.hpp"
 #include "fb_collide.hpp"
 #include "fb_constraint.hpp"
 
@@ -55,8 +56,9 @@ FBD real ray_site(const real* pos, const real* mat, const real* size, int type, 
 }
 
 // acceleration-stage sensors: accelerometer (thorax site), 6 force sensors, 6 touch sensors
-template <typename real>
-__device__ __forceinline__ void d_sensor_acc(const DevModel<real>& M, const WS<real>& w, int lane) {
+// FORCES (k_step_forces, fb_forces.hpp): xf = the environment's xfrc_applied rows (null: none); they enter cfrc_ext as in mj_rnePostConstraint
+template <typename real, bool FORCES = false>
+__device__ __forceinline__ void d_sensor_acc(const DevModel<real>& M, const WS<real>& w, int lane, const FB_GLOBAL real* xf = nullptr) {
   PROF_BEGIN();
   int ncon = w.istate()[IS_NCON];
   // wrench of each active contact about the tree CoM, in the lane that owns the contact (at most 64 contacts)
@@ -124,6 +126,9 @@ __device__ __forceinline__ void d_sensor_acc(const DevModel<real>& M, const WS<r
         real sgn = (b == rb2) ? (real)1 : (real)-1;
         for (int k = 0; k < 6; k++) ext[k] += sgn*wr[k];
       }
+    }
+    if constexpr (FORCES) {
+      if (xf && b > 0) { real xw[6]; applied_wrench(M, w, xf, b, xw); for (int k = 0; k < 6; k++) ext[k] += xw[k]; }
     }
     real qsum[6];
     dof_fetch6(Q, b >= 0 ? M.body_veldof[b] : -1, qsum);               // (wave collective)
@@ -196,6 +201,9 @@ __device__ __forceinline__ void d_sensor_acc(const DevModel<real>& M, const WS<r
         real sgn = (b == rb2) ? (real)1 : (real)-1;
         for (int k = 0; k < 6; k++) acc[k] += sgn*wr[k];
       }
+    }
+    if constexpr (FORCES) {
+      if (xf && b > 0) { real xw[6]; applied_wrench(M, w, xf, b, xw); for (int k = 0; k < 6; k++) acc[k] += xw[k]; }
     }
     if (b >= 0) for (int k = 0; k < 6; k++) w.cfrc_ext()[6*b + k] = acc[k];
   }
@@ -808,6 +816,9 @@ FB_STAGE_WRAP(s_actuation, d_actuation(M, w, lane))
 FB_STAGE_WRAP(s_constraint_b, d_constraint_b(M, w, lane))
 FB_STAGE_WRAP(s_sensor_acc, d_sensor_acc(M, w, lane))
 FB_STAGE_WRAP(s_integrate, d_integrate(M, w, lane))
+template <typename real> FB_STAGE_C void s_sensor_acc_forces(const DevModel<real>& M_, const WS<real>& w_, const real* xfrc_, int lane) {
+  const DevModel<real>& M = as_constant(M_); const WS<real> w = ws_uniform(w_, M);
+  d_sensor_acc<real, true>(M, w, lane, (const FB_GLOBAL real*)uniform_p(xfrc_)); }
 template <typename real> FB_STAGE_C bool s_constraint_a(const DevModel<real>& M_, const WS<real>& w_, int lane) {
   const DevModel<real>& M = as_constant(M_); const WS<real> w = ws_uniform(w_, M); return d_constraint_a(M, w, lane); }
 template <typename real> FB_STAGE_C void s_init(const DevModel<real>& M_, const WS<real>& w_, int env, int lane) {
@@ -835,9 +846,12 @@ template <typename real> FB_STAGE_C void s_post(const DevModel<real>& M_, const 
 // LDS-resident is alive at that boundary -- the factor of M is dead, the right-hand side of the Euler solve is assembled from the global row --
 // so the two halves may run on different waves (k_fly hands the last substeps of a step out in halves).
 // Returns true when the call was an auto-reset (the step is complete then).
-template <typename real>
+// FORCES (k_step_forces): qfrc_app / xfrc_app = the environment's rows of the applied-force arrays (fb_forces.hpp); every substep and a forward
+// evaluation read them, the forward pass of a reset does not.
+template <typename real, bool FORCES = false>
 __device__ __forceinline__ bool d_run(const DevModel<real>& M, const WS<real>& w, int env, int mode, int nsub_arg, int nslot, int* sched, const float* action,
-                      float* obs, float* reward, float* discount, int* step_type, int lane, int tk = -1, int only = -1) {
+                      float* obs, float* reward, float* discount, int* step_type, int lane, int tk = -1, int only = -1,
+                      const real* qfrc_app = nullptr, const real* xfrc_app = nullptr) {
   // every selector of the stage machine is wave-uniform: say so (v_readfirstlane), otherwise the interpreter's state lives in
   // VGPRs + saved exec masks across every stage call and counts against the register budget of all stages
   mode = uniform_int(mode); nsub_arg = uniform_int(nsub_arg); tk = uniform_int(tk); only = uniform_int(only);
@@ -895,6 +909,7 @@ __device__ __forceinline__ bool d_run(const DevModel<real>& M, const WS<real>& w
         // only.  The constraint projection, the factor's first consumer, follows.  Nothing LDS-resident crosses a launch
         // boundary any more (the factor and the Delassus matrix used to be parked in the global row between control steps).
         PROF_BEGIN();
+        if constexpr (FORCES) { if (!resetting) s_applied_forces(M, wc, qfrc_app, xfrc_app, lane); }      // lx += qfrc_applied + J' xfrc_applied
         for (int i = lane; i < M.nv; i += FB_WAVE) {
           real f = w.qfrc_passive()[i] - w.qfrc_bias()[i] + w.lx()[i];          // lx = qfrc_actuator (assembled there by ST_ACT)
           w.qfrc_smooth()[i] = f; w.lx()[i] = f;
@@ -932,7 +947,8 @@ __device__ __forceinline__ bool d_run(const DevModel<real>& M, const WS<real>& w
         pc = ST_SENS; break; }
       case ST_SENS: {
         PROF_BEGIN();
-        s_sensor_acc(M, wc, lane);
+        if constexpr (FORCES) s_sensor_acc_forces(M, wc, resetting ? (const real*)nullptr : xfrc_app, lane);
+        else s_sensor_acc(M, wc, lane);
         PROF(P_SENS);
         pc = (single_pass || tk_half_a) ? ST_DONE : ST_EULER_PRE; break; }
       case ST_EULER_PRE: {

@@ -40,7 +40,7 @@ FIELDS = dict(
     REWARD_FACTORS=(26, _F64, 5), GEOM_XPOS=(27, _F64, (3, 'ngeom')), GEOM_XMAT=(28, _F64, (9, 'ngeom')), CVEL=(29, _F64, (6, 'nbody')),
     STEP_TICKS=(30, _I32, 1), LAUNCH_ORDER=(31, _I32, 1), WARN=(32, _I32, 1), WARN_EVER=(33, _I32, 1), SIZE_STATS=(34, _I32, 4),
     SITE_XPOS=(35, _F64, (3, 'nsite')), IK_ERR=(36, _F64, 2), IK_STEPS=(37, _I32, 2), QFRC_INVERSE=(38, _F64, 'nv'),
-    CONTACT_FORCE=(39, _F64, 3*MAXCON))
+    CONTACT_FORCE=(39, _F64, 3*MAXCON), QFRC_APPLIED=(40, _F64, 'nv'), XFRC_APPLIED=(41, _F64, (6, 'nbody')))
 # bits of WARN / WARN_EVER (include/flybody_engine.h): the caps MuJoCo reports as nconmax / njmax warnings, and iteration limits
 WARN_BITS = dict(CONTACT_CAP=1, EFC_CAP=2, SOLVER_MAXITER=4, CCD_MAXITER=8, SCHED_WAIT=16, SOLVER_FALLBACK=32)
 
@@ -119,6 +119,9 @@ def load_library(lib_path: Optional[str] = None) -> C.CDLL:
         L.fb_batch_ik.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     if hasattr(L, 'fb_batch_inverse'):
         L.fb_batch_inverse.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+    if hasattr(L, 'fb_batch_clear_forces'):
+        L.fb_batch_clear_forces.argtypes = [C.c_void_p]
+        L.fb_batch_forces_active.argtypes = [C.c_void_p]
     _libs[path] = L
     return L
 
@@ -306,6 +309,18 @@ class Batch:
         ([n_env][MAXCON][3], contact frame); EFC_FORCE / QFRC_CONSTRAINT hold the inverse's values.  discrete: QACC is (qvel+ - qvel) / h
         of the engine's Euler substep (FB_INV_DISCRETE).  Noslip is not inverted.  FP64 batches only.  Asynchronous after its checks."""
         _check(self.L, self.L.fb_batch_inverse(self.h, 1 if discrete else 0, stream))
+
+    def clear_forces(self):
+        """Free the applied-force arrays (QFRC_APPLIED / XFRC_APPLIED) and return the batch to the plain step kernel
+        (fb_batch_clear_forces).  Zero-copy views of the arrays are dangling afterwards."""
+        _check(self.L, self.L.fb_batch_clear_forces(self.h))
+
+    @property
+    def forces_active(self) -> bool:
+        """True while the applied-force arrays are allocated (the first set() / device_ptr() of QFRC_APPLIED or XFRC_APPLIED allocates
+        both): control steps, substeps and forward evaluations then read them, every substep; the forward pass of a reset does not.
+        The arrays are caller-owned inputs: they persist until changed and nothing clears them on a reset (unlike MuJoCo)."""
+        return self.L.fb_batch_forces_active(self.h) == 1
 
     def synchronize(self, stream=None):
         _check(self.L, self.L.fb_batch_synchronize(self.h, stream))

@@ -104,7 +104,11 @@ class BatchedFlyEnv:
                  joint_filter: float = 0.01, future_steps: int = 64, time_limit: float = 10.0, task: str = 'walk_imitation',
                  wbpg_tables=None, seed: int = 0, traj_loader=None, env_id_base: int = 0, force_actuators: bool = False,
                  use_wings: Optional[bool] = None, use_legs: Optional[bool] = None, dyntype_filterexact: bool = False,
-                 use_mouth: bool = False, use_antennae: bool = False, adhesion_filter: Optional[float] = None, dense: Optional[bool] = None):
+                 use_mouth: bool = False, use_antennae: bool = False, adhesion_filter: Optional[float] = None, dense: Optional[bool] = None,
+                 control_callback=None):
+        """control_callback: a callable f(env) run before every CONTROL step of step() and step_tensor() -- the batched analogue of
+        MuJoCo's mjcb_control, typically writing applied_forces() from the batch's state.  It runs once per control step, not once
+        per physics substep: what it writes holds for all substeps of that step."""
         from . import model_zoo
         self.task_name = task
         # FruitFly._build's configuration space (fruitfly.py:123-386): the compiled tables come from the shipped assets, the
@@ -174,6 +178,8 @@ class BatchedFlyEnv:
             self.task._traj_generator.set_next_trajectory(qp, qv)
         self.layout, self.nobs = observation_layout(self.model, future_steps, ball=(task == 'walk_on_ball'))
         self._torch_views = None
+        self.control_callback = control_callback
+        self._force_views = None
 
     def _apply_reference(self):
         s = self.task._traj_generator._snippet
@@ -222,6 +228,34 @@ class BatchedFlyEnv:
                                      step_type=view('STEP_TYPE', (self.n_env,), torch.int32))
         return self._torch_views
 
+    def applied_forces(self):
+        """Zero-copy torch views of the engine's external-force inputs, MuJoCo's qfrc_applied and xfrc_applied:
+        dict(qfrc_applied=[n_env, nv], xfrc_applied=[n_env, nbody, 6]) at the batch's precision (float64 / float32); a body's row is
+        force(3) then torque(3) in the world frame, applied at its centre of mass; the world body's row is ignored.  The first call
+        allocates the arrays (zeroed) and puts the batch on the step kernel that reads them, every substep (Batch.forces_active).
+        They are caller-owned inputs like the actions: they persist until changed and an auto-reset does NOT clear them (MuJoCo's
+        reset does); the host-side reset() zeroes them.  perturbations.clear(env) frees them."""
+        if not self.batch.forces_active:                  # freed behind our back (Batch.clear_forces): earlier views point at freed memory
+            self._force_views = None
+        if self._force_views is None:
+            import torch
+            dt = torch.float64 if self.batch.precision == 64 else torch.float32
+            nv, nbody = self.model.dim('nv'), self.model.dim('nbody')
+
+            def view(name, shape):
+                iface = {'shape': tuple(shape), 'typestr': {torch.float64: '<f8', torch.float32: '<f4'}[dt],
+                         'data': (self.batch.device_ptr(name), False), 'version': 2}
+                holder = type('DevBuf', (), {'__cuda_array_interface__': iface})()
+                return torch.as_tensor(holder, device=f'cuda:{self.device}')
+            self._force_views = dict(qfrc_applied=view('QFRC_APPLIED', (self.n_env, nv)),
+                                     xfrc_applied=view('XFRC_APPLIED', (self.n_env, nbody, 6)))
+        return self._force_views
+
+    def clear_forces(self):
+        """Free the applied-force arrays and return the batch to the plain step kernel; earlier applied_forces() views are dropped."""
+        self._force_views = None
+        self.batch.clear_forces()
+
     def reset_all(self):
         import torch
         self.batch.reset(stream=torch.cuda.current_stream().cuda_stream)
@@ -233,6 +267,8 @@ class BatchedFlyEnv:
         import torch
         assert action.is_cuda and action.dtype == torch.float32 and action.is_contiguous()
         assert tuple(action.shape) == (self.n_env, self.model.dim('nact'))
+        if self.control_callback is not None:
+            self.control_callback(self)
         self.batch.step_ptr(action.data_ptr(), torch.cuda.current_stream().cuda_stream)
         self._time += self.control_timestep()
         return self.torch_views()
@@ -250,6 +286,12 @@ class BatchedFlyEnv:
         return TimeStep(st, float(self.batch.get('REWARD')[env, 0]), float(self.batch.get('DISCOUNT')[env, 0]), od)
 
     def reset(self) -> TimeStep:
+        if self.batch.forces_active:                      # MuJoCo's reset clears the applied forces; the engine leaves that to its caller
+            import torch
+            torch.cuda.synchronize()
+            for t in self.applied_forces().values():
+                t.zero_()
+            torch.cuda.synchronize()
         self.batch.reset(); self.batch.synchronize()
         self._time = 0.0
         return self._timestep()
@@ -258,6 +300,8 @@ class BatchedFlyEnv:
         import torch
         a = np.broadcast_to(np.asarray(action, np.float32), (self.n_env, self.model.dim('nact')))
         t = torch.from_numpy(np.array(a, np.float32, copy=True)).to(f'cuda:{self.device}')
+        if self.control_callback is not None:
+            self.control_callback(self)
         self.batch.step_ptr(t.data_ptr(), torch.cuda.current_stream().cuda_stream)
         torch.cuda.synchronize()
         ts = self._timestep()

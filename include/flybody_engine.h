@@ -76,6 +76,9 @@ enum {
   FB_QFRC_INVERSE = 38,  /* [n_env][nv] FP64: qfrc_inverse of the last fb_batch_inverse (read-only; allocated by the first call) */
   FB_CONTACT_FORCE = 39, /* [n_env][FB_MAXCON][3] FP64: force of contact c of the last fb_batch_inverse in its contact frame (normal,
                             tangent 1, tangent 2; zero beyond the contact's condim and for c >= FB_NCON), rows as FB_CONTACT (read-only) */
+  FB_QFRC_APPLIED = 40,  /* [n_env][nv] physics real: MuJoCo's qfrc_applied, a generalised force per dof (caller-owned input, see below) */
+  FB_XFRC_APPLIED = 41,  /* [n_env][nbody][6] physics real: MuJoCo's xfrc_applied, a Cartesian wrench per body: force(3) then torque(3) in the
+                            world frame, applied at the body's centre of mass (xipos); the world body's row is ignored */
   FB_NFIELD
 };
 
@@ -188,7 +191,8 @@ int fb_batch_row(fb_batch* b, int which, int env, void* host, size_t bytes, int 
 int fb_batch_get(fb_batch* b, int field, void* dst_host, size_t bytes);
 int fb_batch_set(fb_batch* b, int field, const void* src_host, size_t bytes);
 
-/* Device pointer of a field (e.g. to wrap FB_OBS in a torch tensor without a copy). */
+/* Device pointer of a field (e.g. to wrap FB_OBS in a torch tensor without a copy): FB_OBS, FB_REWARD, FB_DISCOUNT, FB_STEP_TYPE, and the
+ * applied-force arrays FB_QFRC_APPLIED / FB_XFRC_APPLIED at the batch's precision (allocating them: see fb_batch_clear_forces).  NULL otherwise. */
 void* fb_batch_device_ptr(fb_batch* b, int field);
 int fb_batch_synchronize(fb_batch* b, void* stream);
 
@@ -249,6 +253,28 @@ int fb_batch_ik(fb_batch* b, const fb_ik_config* cfg, const double* target_xpos,
  * FB_QACC (checked on the host: the call synchronises the device before it launches).  Asynchronous on `stream` after that. */
 enum { FB_INV_DISCRETE = 1 };
 int fb_batch_inverse(fb_batch* b, int flags, void* stream);
+
+/* External forces (FB_QFRC_APPLIED, FB_XFRC_APPLIED), MuJoCo's two user inputs for everything that is not an actuator, a contact or the
+ * fluid model.  Every substep
+ *     qfrc_smooth = qfrc_passive - qfrc_bias + qfrc_actuator + qfrc_applied + sum_b J_b(xipos_b)' xfrc_applied_b
+ * with J_b at that substep's positions (mj_xfrcAccumulate); xfrc_applied also enters cfrc_ext, so the force sensors read what
+ * mj_rnePostConstraint gives (qfrc_applied does not); the accelerometer reads qacc, which holds the effect.
+ * Who reads them: the substeps of fb_batch_step and fb_batch_substep, and fb_batch_forward.  The forward pass of a reset does NOT
+ * (fb_batch_reset, and the auto-reset of an environment whose last step was LAST): MuJoCo's reset clears the arrays, so a FIRST
+ * observation is the same with and without forces.  fb_batch_inverse needs nothing: its FB_QFRC_INVERSE of a forward pass's qacc equals
+ * qfrc_actuator + qfrc_applied + J' xfrc_applied.
+ * Ownership, and the difference from MuJoCo: the arrays are caller-owned inputs like the actions.  They persist until the caller changes
+ * them, the kernels never write them, and NOTHING clears them on a reset -- an environment that auto-resets keeps its row; clearing is the
+ * caller's job (fly_envs.BatchedFlyEnv.reset() does it for the host-side reset).
+ * Allocation: both arrays are allocated, zeroed, by the first fb_batch_set or fb_batch_device_ptr of either field (fb_batch_get before
+ * that fails).  From then on control steps, substeps and forward evaluations run a second step kernel that carries the applied-force
+ * stage (k_step_forces; with all-zero forces its results equal the plain kernel's, up to the sign of a zero); fb_batch_clear_forces frees
+ * the arrays and returns the batch to the plain kernel, whose code and speed the feature does not touch.  While forces are allocated
+ * fb_batch_stage (single-stage profiling) fails.  fb_batch_set rejects a wrong size and non-finite values; non-finite values written
+ * through the device pointer end the environment's episode through the blow-up guard, as a NaN action does.
+ * Both precisions.  fb_batch_forces_active: 1 while the arrays are allocated, 0 otherwise. */
+int fb_batch_clear_forces(fb_batch* b);
+int fb_batch_forces_active(const fb_batch* b);
 
 const char* fb_last_error(void);
 
