@@ -273,11 +273,91 @@ FBD void ar_from_registers_t(const DevModel<real>& M, const WS<real>& w, ARP AR,
   }
   SYNC();
 }
+// The same matrix with ONE LANE PER ENTRY of the packed lower triangle: pass k gives lane l the entry p = 64 k + l = ARIDX(r, c), c <= r,
+// while p < nefc (nefc + 1)/2 -- ceil(nefc (nefc + 1)/128) passes (one up to 10 rows, two up to 15) instead of nefc row iterations in which
+// at most nefc lanes hold a column and half of those compute an upper-triangle entry that is thrown away.  The lane fetches the Y of row r
+// and of column c from their owner lanes (ds_bpermute on statically indexed registers; every lane takes part in every fetch), four slots
+// at a time so that a group's fetches are in flight together, and looks the four shared-prefix lengths up itself.
+// Every entry is accumulated in exactly the order of the row loop above, r as its row and c as its column: the trunk slots ascending, the
+// slots of the row's A chain ascending (AA term, then AB), those of its B chain (BA, then BB), then R on the diagonal -- same bits.
+// A group of slots is skipped when no row of the system has a chain that long (a ballot: wave-uniform); the row loop skipped it per row,
+// and what is skipped here is masked by the prefix lengths anyway.
+template <int TRUNK, typename real, typename ARP>
+FBD void ar_entry_lanes_t(const DevModel<real>& M, const WS<real>& w, ARP AR, int nefc, int lane, const real* yA, const real* yB, int bA, int bB, int lA, int lB) {
+  const int* common = M.body_common; const int nb = M.nbody;
+  const real Rl = w.efc_R()[lane];          // (unpredicated: the array has a slot for every lane, and only rows < nefc are ever fetched)
+  const int bodies = bA | (bB << 16), lens = lA | (lB << 8);
+  real tr[TRUNK > 0 ? TRUNK : 1];
+#pragma unroll
+  for (int s = 0; s < TRUNK; s++) tr[s] = yA[s] + yB[s];
+  // chain lengths present in the system, per group of four slots (wave-uniform; bit g of `any`: an A chain, bit 8 + g: a B chain
+  // reaches slot 4 g -- one scalar register instead of a flag pair per group)
+  unsigned any = 0;
+#pragma unroll
+  for (int g = 0; g < FB_MAXCH/4; g++) any |= (__ballot(lA > 4*g) != 0 ? 1u << g : 0u) | (__ballot(lB > 4*g) != 0 ? 0x100u << g : 0u);
+  any = (unsigned)uniform_int((int)any);
+  const int nent = nefc*(nefc + 1)/2;
+  for (int p0 = 0; p0 < nent; p0 += FB_WAVE) {
+    const int p = p0 + lane;
+    const bool valid = p < nent;
+    const int pp = valid ? p : 0;
+    // row of entry pp: the largest r with r (r + 1)/2 <= pp (8 pp + 1 <= 16641 is exact in FP32; the two corrections cover a square root that is one off)
+    int r = (int)((sqrtf((float)(8*pp + 1)) - 1.0f)*0.5f);
+    r -= (r*(r + 1)/2 > pp) ? 1 : 0;
+    r += ((r + 1)*(r + 2)/2 <= pp) ? 1 : 0;
+    const int c = pp - r*(r + 1)/2;
+    const int rbod = nw_lane_i(bodies, r), cbod = nw_lane_i(bodies, c), rlen = nw_lane_i(lens, r), clen = nw_lane_i(lens, c);
+    const int rbA = rbod & 0xffff, rbB = rbod >> 16, cbA = cbod & 0xffff, cbB = cbod >> 16;
+    const int rlA = rlen & 0xff, rlB = rlen >> 8, clA = clen & 0xff, clB = clen >> 8;
+    const int cmAA = min(min(common[rbA*nb + cbA], clA), rlA), cmAB = min(min(common[rbA*nb + cbB], clB), rlA);
+    const int cmBA = min(min(common[rbB*nb + cbA], clA), rlB), cmBB = min(min(common[rbB*nb + cbB], clB), rlB);
+    const real Rr = nw_lane(Rl, r);
+    real acc = 0;
+    {
+      real tr_r[TRUNK > 0 ? TRUNK : 1], tr_c[TRUNK > 0 ? TRUNK : 1];
+#pragma unroll
+      for (int s = 0; s < TRUNK; s++) { tr_r[s] = nw_lane(tr[s], r); tr_c[s] = nw_lane(tr[s], c); }
+#pragma unroll
+      for (int s = 0; s < TRUNK; s++) acc += tr_r[s]*tr_c[s];
+    }
+#pragma unroll
+    for (int s0 = 0; s0 < FB_MAXCH; s0 += 4) {
+      if (s0 + 4 > TRUNK && ((any >> (s0/4)) & 1u)) {
+        real yr[4], ya[4], yb[4];
+#pragma unroll
+        for (int s = s0; s < s0 + 4; s++) if (s >= TRUNK) { yr[s - s0] = nw_lane(yA[s], r); ya[s - s0] = nw_lane(yA[s], c); yb[s - s0] = nw_lane(yB[s], c); }
+#pragma unroll
+        for (int s = s0; s < s0 + 4; s++) if (s >= TRUNK) { if (s < cmAA) acc += yr[s - s0]*ya[s - s0]; if (s < cmAB) acc += yr[s - s0]*yb[s - s0]; }
+      }
+    }
+#pragma unroll
+    for (int s0 = 0; s0 < FB_MAXCH; s0 += 4) {
+      if (s0 + 4 > TRUNK && ((any >> (8 + s0/4)) & 1u)) {
+        real yr[4], ya[4], yb[4];
+#pragma unroll
+        for (int s = s0; s < s0 + 4; s++) if (s >= TRUNK) { yr[s - s0] = nw_lane(yB[s], r); ya[s - s0] = nw_lane(yA[s], c); yb[s - s0] = nw_lane(yB[s], c); }
+#pragma unroll
+        for (int s = s0; s < s0 + 4; s++) if (s >= TRUNK) { if (s < cmBA) acc += yr[s - s0]*ya[s - s0]; if (s < cmBB) acc += yr[s - s0]*yb[s - s0]; }
+      }
+    }
+    if (valid) {
+      if (c == r) acc += Rr;
+      AR[p] = acc;                          // p == ARIDX(r, c)
+    }
+  }
+  SYNC();
+}
 template <typename real, typename ARP>
 FBD void ar_from_registers(const DevModel<real>& M, const WS<real>& w, ARP AR, int nefc, int lane, const real* yA, const real* yB, int bA, int bB, int lA, int lB) {
-  if (uniform_int(M.ntrunk) == FB_MAXTRUNK) ar_from_registers_t<FB_MAXTRUNK>(M, w, AR, nefc, lane, yA, yB, bA, bB, lA, lB);
-  else
-  ar_from_registers_t<0>(M, w, AR, nefc, lane, yA, yB, bA, bB, lA, lB);
+  // (M.ar_entry_lanes: FB_NO_AR_ENTRY_LANES=1 at model load keeps the row loop, for comparison)
+  const bool entry = uniform_int(M.ar_entry_lanes) != 0;
+  if (uniform_int(M.ntrunk) == FB_MAXTRUNK) {
+    if (entry) ar_entry_lanes_t<FB_MAXTRUNK>(M, w, AR, nefc, lane, yA, yB, bA, bB, lA, lB);
+    else ar_from_registers_t<FB_MAXTRUNK>(M, w, AR, nefc, lane, yA, yB, bA, bB, lA, lB);
+  } else {
+    if (entry) ar_entry_lanes_t<0>(M, w, AR, nefc, lane, yA, yB, bA, bB, lA, lB);
+    else ar_from_registers_t<0>(M, w, AR, nefc, lane, yA, yB, bA, bB, lA, lB);
+  }
 }
 
 template <typename real>

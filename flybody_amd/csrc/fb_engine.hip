@@ -978,6 +978,8 @@ static int build_devmodel(fb_batch* b, DevModel<real>& M) {
     M.vl_delta = (rb.empty() || m->npair <= 4*FB_WAVE) ? (real)0 : (real)(FB_VL_SCALE*rb[rb.size()/2]);
     { const char* e_ = getenv("FB_NO_NEIGHBOUR_LIST"); if (e_ && e_[0] == '1') M.vl_delta = 0; }      // (read at model load: the tests compare the two paths bit for bit)
   }
+  M.ar_entry_lanes = 1;
+  { const char* e_ = getenv("FB_NO_AR_ENTRY_LANES"); if (e_ && e_[0] == '1') M.ar_entry_lanes = 0; }      // (read at model load, like the switch above: the tests compare the two builds of the Delassus matrix bit for bit)
   M.noslip_tolerance = (real)m->d("opt_noslip_tolerance")[0]; M.meaninertia = (real)m->d("stat_meaninertia")[0];
   M.totalmass = (real)m->totalmass;
   size_t c;
