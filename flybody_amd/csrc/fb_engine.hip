@@ -558,10 +558,31 @@ __global__ void k_probe_xcc(unsigned* mask) { if (threadIdx.x == 0) atomicOr(mas
 #endif
 
 
+// Grouped batch (fb_batch_create_group): Mp is an ARRAY of n_models model structs that share one tree, and environment e is
+// stepped with Mp[env_model[e]].
+struct GroupArgs { const int* env_model = nullptr; int n_models = 1; };
+
+// The model an environment is stepped with.  MODELS off: the launch's one model.  On: element env_model[env] of the array, the id made
+// wave-uniform (v_readfirstlane) and clamped with scalar compares, so that the struct is addressed through the constant path like the
+// single model (as_constant: its fields stay scalar loads) and an id written out of range through the device pointer never becomes a
+// wild pointer (`bad`: raise WARN_MODEL_ID).
+template <typename real, bool MODELS>
+__device__ __forceinline__ const DevModel<real>& model_of_env(const DevModel<real>* Mp, const DevModel<real>& M0, const GroupArgs& G, int env, bool& bad) {
+  if constexpr (MODELS) {
+    const int id = uniform_int(G.env_model[env]), n = uniform_int(G.n_models);
+    const int k = id < 0 ? 0 : (id >= n ? n - 1 : id);
+    bad = k != id;
+    return as_constant(Mp[k]);
+  } else { (void)Mp; (void)G; (void)env; bad = false; return M0; }
+}
+
 // FORCES: the step kernel with applied forces (k_step_forces; F = the batch's two force arrays, fb_forces.hpp).  k_fly and k_fly_reset instantiate it false.
-template <typename real, bool FORCES = false>
+// MODELS: the kernels of a grouped batch (k_group_step, k_group_reset; G = the assignment).  The workgroup's LDS tables and the launch-wide
+// quantities (substep count, dimensions, workspace layout) come from element 0 -- the models of a group agree in all of them -- and the
+// model proper is bound once the environment is known: per launch on the per-wave path, per ticket under the substep scheduler.
+template <typename real, bool FORCES = false, bool MODELS = false>
 __device__ __forceinline__ void fly_kernel(const DevModel<real>* Mp, const Batch<real>& B, const float* action, const int* env_ids, int mode, int nsub, int nslot,
-                                           const ForceArgs<real> F = ForceArgs<real>()) {
+                                           const ForceArgs<real> F = ForceArgs<real>(), const GroupArgs G = GroupArgs()) {
   // per-wave (per-environment) hot arrays
   constexpr int EPB = LdsCfg<real>::EPB;
   __shared__ real s_pool[EPB][LdsCfg<real>::POOL];          // [factor row | Delassus matrix | solve vector] of each environment
@@ -657,7 +678,9 @@ __device__ __forceinline__ void fly_kernel(const DevModel<real>* Mp, const Batch
 #ifndef FB_EMULATE
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
 #endif
-      const WS<real> w = ws_env(M, B.rarena, B.iarena, env, s_pool, wave, &s_tab);
+      bool bad_id;
+      const DevModel<real>& Me = model_of_env<real, MODELS>(Mp, M, G, env, bad_id);
+      const WS<real> w = ws_env(Me, B.rarena, B.iarena, env, s_pool, wave, &s_tab);
       float* obs = B.obs ? B.obs + (size_t)env*B.nobs : nullptr;
 #ifdef FB_EMULATE
       // (host emulation, test infrastructure: every ticket starts from a POISONED LDS pool -- whatever a stage left there for a later ticket,
@@ -672,9 +695,10 @@ __device__ __forceinline__ void fly_kernel(const DevModel<real>* Mp, const Batch
 #endif
       const real *qf_ = nullptr, *xf_ = nullptr;
       if constexpr (FORCES) { qf_ = F.qfrc_applied + (size_t)env*M.nv; xf_ = F.xfrc_applied + (size_t)env*6*M.nbody; }
-      const bool was_reset = d_run<real, FORCES>(M, w, env, mode, nsub, nslot, (int*)nullptr, action ? action + (size_t)env*M.nact : nullptr, obs, B.reward + env,
+      const bool was_reset = d_run<real, FORCES>(Me, w, env, mode, nsub, nslot, (int*)nullptr, action ? action + (size_t)env*M.nact : nullptr, obs, B.reward + env,
                                    B.discount + env, B.step_type + env, lane, (round == 0 ? 1 : 0) | (round == nunit - 1 ? 2 : 0) | (tkhalf == 1 ? 4 : 0) | (tkhalf == 2 ? 8 : 0) | (late ? 16 : 0),
                                    -1, qf_, xf_);
+      if constexpr (MODELS) { if (bad_id && lane == 0) { atomicOr(w.istate() + IS_WARN, (int)WARN_MODEL_ID); atomicOr(w.istate() + IS_WARN_EVER, (int)WARN_MODEL_ID); } }
 #ifndef FB_EMULATE
       // Release.  What the next holder of this environment (a wave of the SAME XCD: environments are bound to XCDs) must see is this
       // wave's global stores.  On gfx942 / gfx950 the vector L1 is write-through and an XCD has ONE L2, so "visible to the XCD" =
@@ -700,7 +724,9 @@ __device__ __forceinline__ void fly_kernel(const DevModel<real>* Mp, const Batch
     return;
   }
   int env = uniform_int(env_ids ? env_ids[slot] : slot);
-  const WS<real> w = ws_env(M, B.rarena, B.iarena, env, s_pool, wave, &s_tab);
+  bool bad_id;
+  const DevModel<real>& Me = model_of_env<real, MODELS>(Mp, M, G, env, bad_id);
+  const WS<real> w = ws_env(Me, B.rarena, B.iarena, env, s_pool, wave, &s_tab);
   float* obs = B.obs ? B.obs + (size_t)env*B.nobs : nullptr;
 #if defined(FB_PROFILE) && !defined(FB_EMULATE)
   long long t0_ = clock64(), r0_ = wall_clock64();
@@ -719,8 +745,9 @@ __device__ __forceinline__ void fly_kernel(const DevModel<real>* Mp, const Batch
   } else if (lane == 0) { w.istate()[IS_PRIO] = 0; if (mode == MODE_STEP || mode == MODE_RESET) w.istate()[IS_WARN] = 0; }
   const real *qf_ = nullptr, *xf_ = nullptr;
   if constexpr (FORCES) { qf_ = F.qfrc_applied + (size_t)env*M.nv; xf_ = F.xfrc_applied + (size_t)env*6*M.nbody; }
-  d_run<real, FORCES>(M, w, env, only >= 0 ? (int)MODE_STEP : mode, nsub, nslot, only >= 0 ? (int*)nullptr : B.sched, action ? action + (size_t)env*M.nact : nullptr, obs, B.reward + env,
+  d_run<real, FORCES>(Me, w, env, only >= 0 ? (int)MODE_STEP : mode, nsub, nslot, only >= 0 ? (int*)nullptr : B.sched, action ? action + (size_t)env*M.nact : nullptr, obs, B.reward + env,
         B.discount + env, B.step_type + env, lane, -1, only, qf_, xf_);
+  if constexpr (MODELS) { if (bad_id && lane == 0) { atomicOr(w.istate() + IS_WARN, (int)WARN_MODEL_ID); atomicOr(w.istate() + IS_WARN_EVER, (int)WARN_MODEL_ID); } }
   if (only >= 0) {
     SYNC();
     FB_GLOBAL real* pk = (FB_GLOBAL real*)(B.park + (size_t)env*LdsCfg<real>::POOL);
@@ -758,6 +785,19 @@ __global__ void __launch_bounds__(FB_WAVE*LdsCfg<real>::EPB, LdsCfg<real>::WAVES
 template <typename real>
 __global__ void __launch_bounds__(FB_WAVE*LdsCfg<real>::EPB, LdsCfg<real>::WAVES_PER_SIMD) k_step_forces(const DevModel<real>* Mp, Batch<real> B, const float* action, const int* env_ids, int mode, int nsub, int nslot, ForceArgs<real> F) {
   fly_kernel<real, true>(Mp, B, action, env_ids, mode, nsub, nslot, F);
+}
+
+// The kernels of a grouped batch (fb_batch_create_group): the same device code with the per-environment model compiled in, under k_fly's
+// launch bounds and on its LDS layout, ticket scheduler included; with and without the applied-force stage, and the reset under a name of its
+// own as above.  The assignment is an extra kernel argument.  launch_fly uses them while the batch holds more than one model, so the
+// kernels above keep their arguments and their code.
+template <typename real, bool FORCES>
+__global__ void __launch_bounds__(FB_WAVE*LdsCfg<real>::EPB, LdsCfg<real>::WAVES_PER_SIMD) k_group_step(const DevModel<real>* Mp, Batch<real> B, const float* action, const int* env_ids, int mode, int nsub, int nslot, ForceArgs<real> F, GroupArgs G) {
+  fly_kernel<real, FORCES, true>(Mp, B, action, env_ids, mode, nsub, nslot, F, G);
+}
+template <typename real>
+__global__ void __launch_bounds__(FB_WAVE*LdsCfg<real>::EPB, LdsCfg<real>::WAVES_PER_SIMD) k_group_reset(const DevModel<real>* Mp, Batch<real> B, const int* env_ids, int nsub, int nslot, GroupArgs G) {
+  fly_kernel<real, false, true>(Mp, B, nullptr, env_ids, (int)MODE_RESET, nsub, nslot, ForceArgs<real>(), G);
 }
 
 // Launch order for the next control step: environments sorted by the duration of their last step, longest first (counting
@@ -881,6 +921,10 @@ struct fb_batch {
   void* park = nullptr;               // MODE_STAGE: LDS pools between single-stage launches (allocated on first use)
   std::vector<void*> allocs;          // model tables on the device
   DevModel<double> M64; DevModel<float> M32;   // the model at the batch's precision (with_model: only that one is built)
+  // grouped batch (fb_batch_create_group): the models, the device structs of all of them at the batch's precision (element 0 follows
+  // M64 / M32, which the setters change: sync_model) and the assignment FB_ENV_MODEL [n_env] (null: a batch made by fb_batch_create)
+  std::vector<const fb_model*> models; std::vector<DevModel<double>> G64; std::vector<DevModel<float>> G32; int* env_model = nullptr;
+  int n_models() const { return models.empty() ? 1 : (int)models.size(); }
   void* dM = nullptr;                 // the model struct in device memory (the kernels read it through the constant path)
   std::vector<char> dM_copy;          // ... what it currently holds (sync_model)
   void *ref_qpos = nullptr, *ref_qvel = nullptr;
@@ -925,14 +969,30 @@ static size_t real_size(fb_batch* b) { return with_model(b, [](auto& M) { return
 
 // The device copy of the model struct follows the host copy (the setters only touch the host copy); a changed model is rare,
 // so the refresh simply waits for the device to be idle
+// (a grouped batch holds the structs of all its models as one array: element 0 is the setters' model, the task-level fields of the others follow it)
+template <typename real>
+static void copy_task_fields(DevModel<real>& d, const DevModel<real>& s) {
+#define CP(f) d.f = s.f;
+  CP(ref_qpos) CP(ref_qvel) CP(T) CP(future_steps) CP(episode_steps) CP(nobs) CP(terminal_com_dist) CP(time_limit) CP(seed)
+  CP(wb_traj) CP(wb_phase) CP(wb_freqs) CP(wb_offset) CP(wb_nfreq) CP(wb_base_freq) CP(wb_rel_range) CP(wb_rate)
+  CP(ds_qpos) CP(ds_qvel) CP(ds_r2s) CP(ds_jq) CP(ds_offset) CP(ds_jid) CP(ds_sid) CP(ds_select)
+  CP(ds_nj) CP(ds_ns) CP(ds_ntraj) CP(ds_nselect) CP(ds_env_base) CP(max_episode_steps) CP(ds_random_start)
+#undef CP
+}
+static std::vector<DevModel<double>>& group_models(fb_batch* b, DevModel<double>&) { return b->G64; }
+static std::vector<DevModel<float>>& group_models(fb_batch* b, DevModel<float>&) { return b->G32; }
+
 static int sync_model(fb_batch* b) {
   return with_model(b, [&](auto& M) {
-    if (!b->dM) HIPCHK(hipMalloc(&b->dM, sizeof(M)));
-    const char* h = (const char*)&M;
-    if (b->dM_copy.empty() || memcmp(h, b->dM_copy.data(), sizeof(M)) != 0) {
+    auto& G = group_models(b, M);
+    const size_t bytes = sizeof(M)*(G.empty() ? 1 : G.size());
+    if (!b->dM) HIPCHK(hipMalloc(&b->dM, bytes));
+    if (!G.empty()) { G[0] = M; for (size_t k = 1; k < G.size(); k++) copy_task_fields(G[k], M); }
+    const char* h = G.empty() ? (const char*)&M : (const char*)G.data();
+    if (b->dM_copy.empty() || memcmp(h, b->dM_copy.data(), bytes) != 0) {
       HIPCHK(hipDeviceSynchronize());
-      HIPCHK(hipMemcpy(b->dM, h, sizeof(M), hipMemcpyHostToDevice));
-      b->dM_copy.assign(h, h + sizeof(M));
+      HIPCHK(hipMemcpy(b->dM, h, bytes, hipMemcpyHostToDevice));
+      b->dM_copy.assign(h, h + bytes);
     }
     return 0;
   });
@@ -955,8 +1015,7 @@ static int alloc_obs(fb_batch* b, int nobs) {
 }
 
 template <typename real>
-static int build_devmodel(fb_batch* b, DevModel<real>& M) {
-  const fb_model* m = b->m;
+static int build_devmodel(fb_batch* b, const fb_model* m, DevModel<real>& M) {
   memset(&M, 0, sizeof(M));
   M.nq = m->nq; M.nv = m->nv; M.nbody = m->nbody; M.njnt = m->njnt; M.ngeom = m->ngeom; M.nsite = m->nsite;
   M.nu = m->nu; M.na = m->na; M.ntendon = m->ntendon; M.npair = m->npair; M.nM = m->nM; M.nsubstep = m->nsubstep;
@@ -1059,27 +1118,85 @@ static void compute_offsets(const DevModel<real>& M, WSOff& o) {
 
 static int batch_create_impl(fb_batch* b);
 
-extern "C" int fb_batch_create(const fb_model* m, int n_env, int device, int precision, fb_batch** out) {
-  if (!out) return fail("fb_batch_create: null output pointer");
-  *out = nullptr;
-  if (!m || n_env <= 0) return fail("fb_batch_create: bad arguments");
-  if (precision != 32 && precision != 64) return fail("fb_batch_create: precision must be 32 or 64");
+// fb_batch_create (models == null: the one model m) and fb_batch_create_group (m = models[0]) behind their argument checks
+static int batch_create(const std::string& fn, const fb_model* m, const fb_model* const* models, int n_models, int n_env, int device, int precision, fb_batch** out) {
+  if (precision != 32 && precision != 64) return fail(fn + ": precision must be 32 or 64");
   int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail("fb_batch_create: no HIP device available (the engine has no CPU fallback)");
-  if (device < 0 || device >= ndev) return fail("fb_batch_create: bad device index");
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(fn + ": no HIP device available (the engine has no CPU fallback)");
+  if (device < 0 || device >= ndev) return fail(fn + ": bad device index");
   HIPCHK(hipSetDevice(device));
   fb_batch* b = new fb_batch();
   b->m = m; b->n_env = n_env; b->device = device; b->precision = precision;
+  if (models) b->models.assign(models, models + n_models);
   int rc;
-  try { rc = batch_create_impl(b); } catch (const std::exception& e_) { rc = fail(std::string("fb_batch_create: ") + e_.what()); }
+  try { rc = batch_create_impl(b); } catch (const std::exception& e_) { rc = fail(fn + ": " + e_.what()); }
   if (rc != 0) { std::string keep = g_err; fb_batch_destroy(b); g_err = keep; return rc; }     // every allocation made so far is released
   *out = b;
   return 0;
 }
 
+extern "C" int fb_batch_create(const fb_model* m, int n_env, int device, int precision, fb_batch** out) {
+  if (!out) return fail("fb_batch_create: null output pointer");
+  *out = nullptr;
+  if (!m || n_env <= 0) return fail("fb_batch_create: bad arguments");
+  return batch_create("fb_batch_create", m, nullptr, 1, n_env, device, precision, out);
+}
+
+// The first array in which model `o` is not compatible with model `m` (fb_batch_create_group), or null: the same arrays with the same
+// types and shapes, integer arrays equal, of the real arrays the two time steps equal.
+static const char* first_incompatible_array(const fb_model* m, const fb_model* o, std::string* why) {
+  for (const auto& kv : m->idx) {
+    const BlobEntry* a = kv.second;
+    auto it = o->idx.find(kv.first);
+    if (it == o->idx.end()) { *why = "is missing"; return a->name; }
+    const BlobEntry* c = it->second;
+    if (a->dtype != c->dtype || a->ndim != c->ndim || a->nbytes != c->nbytes || memcmp(a->shape, c->shape, sizeof(a->shape)) != 0) { *why = "has another type or shape"; return a->name; }
+    const bool fixed = a->dtype == 1 || kv.first == "opt_timestep" || kv.first == "opt_control_timestep";
+    if (fixed && memcmp(m->blob.data() + a->offset, o->blob.data() + c->offset, a->nbytes) != 0) { *why = "differs"; return a->name; }
+  }
+  for (const auto& kv : o->idx) if (m->idx.find(kv.first) == m->idx.end()) { *why = "is not an array of model 0"; return kv.second->name; }
+  return nullptr;
+}
+
+extern "C" int fb_batch_create_group(const fb_model* const* models, int n_models, int n_env, int device, int precision, fb_batch** out) {
+  if (!out) return fail("fb_batch_create_group: null output pointer");
+  *out = nullptr;
+  if (!models || n_models < 1 || n_env <= 0) return fail("fb_batch_create_group: bad arguments");
+  if (n_models > FB_MAX_MODELS) return fail("fb_batch_create_group: more than FB_MAX_MODELS (" + std::to_string((int)FB_MAX_MODELS) + ") models");
+  for (int k = 0; k < n_models; k++) if (!models[k]) return fail("fb_batch_create_group: model " + std::to_string(k) + " is null");
+  for (int k = 1; k < n_models; k++) {
+    std::string why;
+    if (const char* name = first_incompatible_array(models[0], models[k], &why))
+      return fail("fb_batch_create_group: model " + std::to_string(k) + " is not compatible with model 0: array '" + name + "' " + why +
+                  " (the models of a group share dimensions, every integer array and the time steps)");
+  }
+  return batch_create("fb_batch_create_group", models[0], models, n_models, n_env, device, precision, out);
+}
+
+extern "C" int fb_batch_n_models(const fb_batch* b) {
+  if (!b) return fail("fb_batch_n_models: null batch");
+  return b->n_models();
+}
+
 static int batch_create_impl(fb_batch* b) {
   const fb_model* m = b->m; const int n_env = b->n_env;
-  if (with_model(b, [&](auto& M) { if (build_devmodel(b, M)) return -1; compute_offsets(M, b->off); M.off = b->off; return 0; })) return -1;
+  if (with_model(b, [&](auto& M) {
+        if (build_devmodel(b, m, M)) return -1;
+        compute_offsets(M, b->off); M.off = b->off;
+        // a group of more than one model: the structs of all of them (element 0 is refreshed from M by sync_model); every model gets tables of
+        // its own, so whatever the host derives from real constants (vl_delta, body_box, geom_box, body_fluid_geom, totalmass) is per model
+        if (b->models.size() > 1) {
+          auto& G = group_models(b, M);
+          G.assign(b->models.size(), M);
+          for (size_t k = 1; k < G.size(); k++) { if (build_devmodel(b, b->models[k], G[k])) return -1; G[k].off = b->off; }
+        }
+        return 0; })) return -1;
+  if (!b->models.empty()) {
+    std::vector<int> em(n_env);
+    for (int e = 0; e < n_env; e++) em[e] = e % b->n_models();
+    HIPCHK(hipMalloc((void**)&b->env_model, n_env*sizeof(int)));
+    HIPCHK(hipMemcpy(b->env_model, em.data(), n_env*sizeof(int), hipMemcpyHostToDevice));
+  }
   const size_t rs = real_size(b);
   HIPCHK(hipMalloc(&b->rarena, (size_t)n_env*b->off.nreal*rs));
   HIPCHK(hipMemset(b->rarena, 0, (size_t)n_env*b->off.nreal*rs));
@@ -1108,7 +1225,11 @@ static int batch_create_impl(fb_batch* b) {
           // (tests/test_forces_resources.py); the slot count that decides for tickets is the smaller of the two all the same
           int nbf = 0;
           HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nbf, k_step_forces<real>, FB_WAVE*LdsCfg<real>::EPB, 0));
-          b->slots = std::min(nb, nbf)*prop.multiProcessorCount*LdsCfg<real>::EPB;
+          // ... and the kernels of a grouped batch (k_group_step, k_group_reset: tests/test_model_group_resources.py)
+          int nbg = 0, nbgf = 0;
+          HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nbg, (k_group_step<real, false>), FB_WAVE*LdsCfg<real>::EPB, 0));
+          HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nbgf, (k_group_step<real, true>), FB_WAVE*LdsCfg<real>::EPB, 0));
+          b->slots = std::min(std::min(nb, nbf), std::min(nbg, nbgf))*prop.multiProcessorCount*LdsCfg<real>::EPB;
           return 0; })) return -1;
     unsigned* dmask; unsigned hmask = 0;
     HIPCHK(hipMalloc((void**)&dmask, sizeof(unsigned))); HIPCHK(hipMemset(dmask, 0, sizeof(unsigned)));
@@ -1140,8 +1261,10 @@ static int batch_create_impl(fb_batch* b) {
   // initial state: qpos0 everywhere (fb_batch_reset overrides it once a reference is set)
   if (with_model(b, [&](auto& M) {
         std::vector<decltype(M.timestep)> rows((size_t)n_env*m->nq);
-        const double* q0 = m->d("qpos0");
-        for (int e = 0; e < n_env; e++) std::copy_n(q0, m->nq, rows.data() + (size_t)e*m->nq);
+        for (int e = 0; e < n_env; e++) {
+          const double* q0 = (b->models.empty() ? m : b->models[e % b->n_models()])->d("qpos0");
+          std::copy_n(q0, m->nq, rows.data() + (size_t)e*m->nq);
+        }
         HIPCHK(hipMemcpy2D((char*)b->rarena + (size_t)b->off.qpos*rs, (size_t)b->off.nreal*rs, rows.data(), (size_t)m->nq*rs, (size_t)m->nq*rs, n_env, hipMemcpyHostToDevice));
         return 0; })) return -1;
   b->nobs = 0;
@@ -1152,7 +1275,7 @@ extern "C" void fb_batch_destroy(fb_batch* b) {
   if (!b) return;
   (void)hipSetDevice(b->device);
   for (void* p : b->allocs) (void)hipFree(p);
-  void* frees_[] = {b->rarena, b->iarena, b->obs, b->reward, b->discount, b->step_type, b->d_ids, b->sched, b->cost, b->order, b->ref_qpos, b->ref_qvel, b->dM, b->tick, b->done, b->sched_err, b->park, b->probe_word, b->torder, b->ik_err, b->ik_steps, b->ik_buf, b->inv_qfrc, b->inv_cforce, b->qfrc_applied, b->xfrc_applied};
+  void* frees_[] = {b->rarena, b->iarena, b->obs, b->reward, b->discount, b->step_type, b->d_ids, b->sched, b->cost, b->order, b->ref_qpos, b->ref_qvel, b->dM, b->tick, b->done, b->sched_err, b->park, b->probe_word, b->torder, b->ik_err, b->ik_steps, b->ik_buf, b->inv_qfrc, b->inv_cforce, b->qfrc_applied, b->xfrc_applied, b->env_model};
   for (void* p : frees_) (void)hipFree(p);
 
   if (b->ev0) (void)hipEventDestroy(b->ev0);
@@ -1294,7 +1417,15 @@ static void launch_fly(fb_batch* b, int mode, const float* action, const int* id
   const DevModel<real>* dM = (const DevModel<real>*)b->dM;
   Batch<real> B = {(real*)b->rarena, b->iarena, b->obs, b->reward, b->discount, b->step_type, b->n_env, b->nobs, b->use_prio ? b->sched : nullptr, b->cost,
                    tickets ? b->tick : nullptr, b->done, b->nq, b->sched_err, tord, (real*)b->park};
-  if (mode == MODE_RESET) hipLaunchKernelGGL((k_fly_reset<real>), dim3((n + EPB - 1)/EPB), dim3(FB_WAVE*EPB), 0, st, dM, B, ids, nsub, n);
+  if (b->n_models() > 1) {
+    // a grouped batch: the kernels that bind the model per environment (dM is the array of the group's model structs)
+    const GroupArgs G = {b->env_model, b->n_models()};
+    const ForceArgs<real> F = {(const real*)b->qfrc_applied, (const real*)b->xfrc_applied};
+    if (mode == MODE_RESET) hipLaunchKernelGGL((k_group_reset<real>), dim3((n + EPB - 1)/EPB), dim3(FB_WAVE*EPB), 0, st, dM, B, ids, nsub, n, G);
+    else if (b->qfrc_applied) hipLaunchKernelGGL((k_group_step<real, true>), dim3((n + EPB - 1)/EPB), dim3(FB_WAVE*EPB), 0, st, dM, B, action, ids, mode, nsub, n, F, G);
+    else hipLaunchKernelGGL((k_group_step<real, false>), dim3((n + EPB - 1)/EPB), dim3(FB_WAVE*EPB), 0, st, dM, B, action, ids, mode, nsub, n, F, G);
+  }
+  else if (mode == MODE_RESET) hipLaunchKernelGGL((k_fly_reset<real>), dim3((n + EPB - 1)/EPB), dim3(FB_WAVE*EPB), 0, st, dM, B, ids, nsub, n);
   else if (b->qfrc_applied) {
     const ForceArgs<real> F = {(const real*)b->qfrc_applied, (const real*)b->xfrc_applied};
     hipLaunchKernelGGL((k_step_forces<real>), dim3((n + EPB - 1)/EPB), dim3(FB_WAVE*EPB), 0, st, dM, B, action, ids, mode, nsub, n, F);
@@ -1419,6 +1550,7 @@ extern "C" int fb_batch_synchronize(fb_batch* b, void* stream) {
 extern "C" int fb_batch_stage(fb_batch* b, int stage_word, const float* action, void* stream) {
   if (!b || stage_word < 0) return fail("fb_batch_stage: bad arguments");
   if (check_ready(b, "fb_batch_stage", false)) return -1;
+  if (b->n_models() > 1) return fail("fb_batch_stage: single-stage profiling runs k_fly, which steps one model; this batch is a group of " + std::to_string(b->n_models()) + " models (fb_batch_create_group)");
   if (b->qfrc_applied) return fail("fb_batch_stage: single-stage profiling runs k_fly, which knows no applied forces; call fb_batch_clear_forces first");
   HIPCHK(hipSetDevice(b->device));
   const size_t pool = with_model(b, [](auto& M) { return sizeof(M.timestep)*LdsCfg<decltype(M.timestep)>::POOL; });
@@ -1432,6 +1564,7 @@ extern "C" int fb_batch_stage(fb_batch* b, int stage_word, const float* action, 
 extern "C" int fb_batch_ik(fb_batch* b, const fb_ik_config* cfg, const double* target_xpos, void* stream) {
   if (!b || !cfg || !target_xpos) return fail("fb_batch_ik: null argument");
   if (b->precision != 64) return fail("fb_batch_ik: inverse kinematics needs an FP64 batch (precision 64)");
+  if (b->n_models() > 1) return fail("fb_batch_ik: per-model inverse kinematics is not supported: this batch is a group of " + std::to_string(b->n_models()) + " models (fb_batch_create_group)");
   const fb_model* m = b->m;
   const int ns = cfg->n_site, nj = cfg->n_joint, n = b->n_env;
   if (ns < 1 || !cfg->site_ids || !cfg->include) return fail("fb_batch_ik: at least one site (and its include mask) is required");
@@ -1504,6 +1637,7 @@ extern "C" int fb_batch_inverse(fb_batch* b, int flags, void* stream) {
   if (!b) return fail("fb_batch_inverse: null batch");
   if (b->precision != 64) return fail("fb_batch_inverse: inverse dynamics needs an FP64 batch (precision 64)");
   if (flags & ~FB_INV_DISCRETE) return fail("fb_batch_inverse: unknown flags");
+  if (b->n_models() > 1) return fail("fb_batch_inverse: per-model inverse dynamics is not supported: this batch is a group of " + std::to_string(b->n_models()) + " models (fb_batch_create_group)");
   FB_GUARD_BEGIN
   const int n = b->n_env, nv = b->m->nv;
   HIPCHK(hipSetDevice(b->device));
@@ -1538,6 +1672,7 @@ static int field_desc(fb_batch* b, int field, FieldDesc* f) {
   const char* no_ref = "fb_batch_get: field not allocated yet (set a reference first)";
   const char* no_ik = "fb_batch_get: field not allocated yet (run fb_batch_ik first)";
   const char* no_inv = "fb_batch_get: field not allocated yet (run fb_batch_inverse first)";
+  const char* no_grp = "FB_ENV_MODEL needs a grouped batch (fb_batch_create_group); this one was made by fb_batch_create";
   const char* no_frc = "fb_batch_get: no applied forces (fb_batch_set / fb_batch_device_ptr of FB_QFRC_APPLIED or FB_XFRC_APPLIED allocates them)";
   switch (field) {
     case FB_QPOS: *f = {REAL_ARENA, o.qpos, (size_t)m->nq}; break;
@@ -1581,6 +1716,7 @@ static int field_desc(fb_batch* b, int field, FieldDesc* f) {
     case FB_CONTACT_FORCE: *f = {F64_ARRAY, 0, (size_t)3*FB_MAXCON_, b->inv_cforce, no_inv}; break;
     case FB_QFRC_APPLIED: *f = {REAL_ARRAY, 0, (size_t)m->nv, b->qfrc_applied, no_frc}; break;
     case FB_XFRC_APPLIED: *f = {REAL_ARRAY, 0, (size_t)6*m->nbody, b->xfrc_applied, no_frc}; break;
+    case FB_ENV_MODEL: *f = {I32_ARRAY, 0, 1, b->env_model, no_grp}; break;
     default: return fail("unknown field");
   }
   return 0;
@@ -1710,6 +1846,14 @@ extern "C" int fb_batch_set(fb_batch* b, int field, const void* src, size_t byte
       HIPCHK(hipMemcpy(dev, tmp.data(), tmp.size()*sizeof(tmp[0]), hipMemcpyHostToDevice));
       return 0;
     });
+  } else if (field == FB_ENV_MODEL) {
+    // the assignment of a grouped batch: validated on the host (the kernels clamp what arrives through the device pointer)
+    if (!f.base) return fail(f.unset);
+    if (bytes != (size_t)n*sizeof(int)) return fail("fb_batch_set: size mismatch: FB_ENV_MODEL is [n_env] int32");
+    const int* v = (const int*)src;
+    for (int e = 0; e < n; e++)
+      if (v[e] < 0 || v[e] >= b->n_models()) return fail("fb_batch_set: FB_ENV_MODEL of environment " + std::to_string(e) + " is " + std::to_string(v[e]) + ", outside [0, " + std::to_string(b->n_models()) + ")");
+    HIPCHK(hipMemcpy(b->env_model, v, bytes, hipMemcpyHostToDevice));
   } else return fail("fb_batch_set: field is read-only");
   return 0;
 }
@@ -1721,6 +1865,7 @@ extern "C" void* fb_batch_device_ptr(fb_batch* b, int field) {
     case FB_REWARD: return b->reward;
     case FB_DISCOUNT: return b->discount;
     case FB_STEP_TYPE: return b->step_type;
+    case FB_ENV_MODEL: return b->env_model;            // (null on a batch made by fb_batch_create)
     case FB_QFRC_APPLIED: case FB_XFRC_APPLIED:        // (allocates both arrays on first use: the batch is stepped by k_step_forces from then on)
       if (hipSetDevice(b->device) != hipSuccess || alloc_forces(b)) return nullptr;
       return field == FB_QFRC_APPLIED ? b->qfrc_applied : b->xfrc_applied;

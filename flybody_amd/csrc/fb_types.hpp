@@ -56,7 +56,7 @@ enum { IS_STEP = 0, IS_RESET_NEXT = 1, IS_STEP_TYPE = 2, IS_NCON = 3, IS_NEFC = 
 #define FB_VLMAX 448         // capacity of the mid-phase neighbour list (pairs); a list that does not fit is not kept (every substep then tests every pair)
 // IS_WARN bits (include/flybody_engine.h FB_WARN_*): raised during a launch, cleared at the start of the next control step;
 // IS_WARN_EVER accumulates them since the last reset of the environment
-enum { WARN_CONTACT_CAP = 1, WARN_EFC_CAP = 2, WARN_SOLVER_MAXITER = 4, WARN_CCD_MAXITER = 8, WARN_SCHED_WAIT = 16, WARN_SOLVER_FALLBACK = 32 };
+enum { WARN_CONTACT_CAP = 1, WARN_EFC_CAP = 2, WARN_SOLVER_MAXITER = 4, WARN_CCD_MAXITER = 8, WARN_SCHED_WAIT = 16, WARN_SOLVER_FALLBACK = 32, WARN_MODEL_ID = 64 };
 
 
 // Address spaces are part of the pointer types.  Pointers that come out of a struct in memory carry no provenance the

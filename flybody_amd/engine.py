@@ -40,9 +40,9 @@ FIELDS = dict(
     REWARD_FACTORS=(26, _F64, 5), GEOM_XPOS=(27, _F64, (3, 'ngeom')), GEOM_XMAT=(28, _F64, (9, 'ngeom')), CVEL=(29, _F64, (6, 'nbody')),
     STEP_TICKS=(30, _I32, 1), LAUNCH_ORDER=(31, _I32, 1), WARN=(32, _I32, 1), WARN_EVER=(33, _I32, 1), SIZE_STATS=(34, _I32, 4),
     SITE_XPOS=(35, _F64, (3, 'nsite')), IK_ERR=(36, _F64, 2), IK_STEPS=(37, _I32, 2), QFRC_INVERSE=(38, _F64, 'nv'),
-    CONTACT_FORCE=(39, _F64, 3*MAXCON), QFRC_APPLIED=(40, _F64, 'nv'), XFRC_APPLIED=(41, _F64, (6, 'nbody')))
+    CONTACT_FORCE=(39, _F64, 3*MAXCON), QFRC_APPLIED=(40, _F64, 'nv'), XFRC_APPLIED=(41, _F64, (6, 'nbody')), ENV_MODEL=(42, _I32, 1))
 # bits of WARN / WARN_EVER (include/flybody_engine.h): the caps MuJoCo reports as nconmax / njmax warnings, and iteration limits
-WARN_BITS = dict(CONTACT_CAP=1, EFC_CAP=2, SOLVER_MAXITER=4, CCD_MAXITER=8, SCHED_WAIT=16, SOLVER_FALLBACK=32)
+WARN_BITS = dict(CONTACT_CAP=1, EFC_CAP=2, SOLVER_MAXITER=4, CCD_MAXITER=8, SCHED_WAIT=16, SOLVER_FALLBACK=32, MODEL_ID=64)
 
 # fb_step.hpp stage ids (ST_*) and the stage sequence of one control step as d_run walks it (profiling: fb_batch_stage)
 ST = dict(ACT=0, ACC_PRE=1, SOLVE=2, ACC_SOLVE=3, ACC_POST=4, CONSTR_A=5, CONSTR_B=6, SENS=7, EULER_PRE=8, FACTOR=9, EULER_SOLVE=10,
@@ -122,6 +122,9 @@ def load_library(lib_path: Optional[str] = None) -> C.CDLL:
     if hasattr(L, 'fb_batch_clear_forces'):
         L.fb_batch_clear_forces.argtypes = [C.c_void_p]
         L.fb_batch_forces_active.argtypes = [C.c_void_p]
+    if hasattr(L, 'fb_batch_create_group'):
+        L.fb_batch_create_group.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
+        L.fb_batch_n_models.argtypes = [C.c_void_p]
     _libs[path] = L
     return L
 
@@ -198,15 +201,57 @@ class Model:
             pass
 
 
-class Batch:
-    """n_env environments on one device (fb_batch)."""
+class ModelGroup:
+    """Models that one batch steps side by side (fb_batch_create_group): the same tree, different real-valued constants -- masses,
+    friction, gains, damping, gravity, ... (flybody_amd.randomization builds such variants).  `models` are array dicts or Model
+    objects of one library.  Compatibility (equal dimensions, integer arrays and time steps) is checked by the library when the
+    group is made; an incompatible model raises EngineError naming the first array that differs."""
 
-    def __init__(self, model: Model, n_env: int, device: int = 0, precision: int = 64):
-        self.model = model; self.L = model.L; self.n_env = n_env; self.precision = precision
+    def __init__(self, models, lib_path: Optional[str] = None, dense: bool = False):
+        models = list(models)
+        if not models:
+            raise ValueError('ModelGroup needs at least one model')
+        self.models = [m if isinstance(m, Model) else Model(m, lib_path, dense) for m in models]
+        self.L = self.models[0].L
+        if any(m.L is not self.L for m in self.models):
+            raise ValueError('the models of a group must come from one engine library')
+        self.handles = (C.c_void_p*len(self.models))(*(m.h for m in self.models))
+        if len(self.models) > 1:
+            # the library's own check, on a one-environment batch (nothing else of it is used)
+            h = C.c_void_p()
+            _check(self.L, self.L.fb_batch_create_group(self.handles, len(self.models), 1, 0, 64, C.byref(h)))
+            self.L.fb_batch_destroy(h)
+
+    def __len__(self):
+        return len(self.models)
+
+    def dim(self, name: str) -> int:
+        return self.models[0].dim(name)
+
+    @property
+    def arrays(self):
+        return self.models[0].arrays
+
+
+class Batch:
+    """n_env environments on one device (fb_batch).  `model`: a Model, or a ModelGroup for per-environment models (field ENV_MODEL)."""
+
+    def __init__(self, model, n_env: int, device: int = 0, precision: int = 64):
+        self.group = model if isinstance(model, ModelGroup) else None
+        self.model = model.models[0] if self.group else model
+        self.L = self.model.L; self.n_env = n_env; self.precision = precision
         h = C.c_void_p()
-        _check(self.L, self.L.fb_batch_create(model.h, n_env, device, precision, C.byref(h)))
+        if self.group:
+            _check(self.L, self.L.fb_batch_create_group(self.group.handles, len(self.group), n_env, device, precision, C.byref(h)))
+        else:
+            _check(self.L, self.L.fb_batch_create(self.model.h, n_env, device, precision, C.byref(h)))
         self.h = h
         self.nobs = 0
+
+    @property
+    def n_models(self) -> int:
+        """Number of models the batch steps (1 unless it was made from a ModelGroup)."""
+        return self.L.fb_batch_n_models(self.h)
 
     def set_reference(self, ref_qpos, ref_qvel, future_steps=64, terminal_com_dist=0.3, time_limit=10.0):
         rq = np.ascontiguousarray(ref_qpos, np.float64); rv = np.ascontiguousarray(ref_qvel, np.float64)

@@ -105,8 +105,13 @@ class BatchedFlyEnv:
                  wbpg_tables=None, seed: int = 0, traj_loader=None, env_id_base: int = 0, force_actuators: bool = False,
                  use_wings: Optional[bool] = None, use_legs: Optional[bool] = None, dyntype_filterexact: bool = False,
                  use_mouth: bool = False, use_antennae: bool = False, adhesion_filter: Optional[float] = None, dense: Optional[bool] = None,
-                 control_callback=None):
-        """control_callback: a callable f(env) run before every CONTROL step of step() and step_tensor() -- the batched analogue of
+                 control_callback=None, models=None, env_model=None, resample_on_reset: bool = False):
+        """models: a list of array dicts (flybody_amd.randomization.vary_model / sample_models) that the batch steps side by side --
+        per-environment physics models, engine.ModelGroup; they replace the task's compiled model (the first one answers the specs) and
+        must share its tree.  env_model: the initial assignment [n_env] (default: e % len(models)); env_model() is its device view.
+        resample_on_reset: after every control step, the environments whose step type is LAST draw a new model id from a generator
+        seeded with `seed` (a torch op on the device, no host sync), so that their auto-reset starts the next episode under it.
+        control_callback: a callable f(env) run before every CONTROL step of step() and step_tensor() -- the batched analogue of
         MuJoCo's mjcb_control, typically writing applied_forces() from the batch's state.  It runs once per control step, not once
         per physics substep: what it writes holds for all substeps of that step."""
         from . import model_zoo
@@ -137,7 +142,7 @@ class BatchedFlyEnv:
                 import warnings
                 warnings.warn(f'{engine.HIP_LIB_DENSE} is missing: FP64 batch of {n_env} environments runs on the default build '
                               '(8 instead of 12 environments per CU; build it with __graft_entry__.build())')
-        self.model = engine.Model(arrays, dense=bool(dense))
+        self.model = engine.ModelGroup(models, dense=bool(dense)) if models is not None else engine.Model(arrays, dense=bool(dense))
         # which binary steps this environment (the implicit choice used to leave no trace): part of the config, logged once
         self.build = 'libflybody_hip_dense.so (FP64, 12 environments per CU)' if dense else 'libflybody_hip.so (default build)'
         if isinstance(self.config, dict): self.config['engine_build'] = self.build
@@ -180,6 +185,12 @@ class BatchedFlyEnv:
         self._torch_views = None
         self.control_callback = control_callback
         self._force_views = None
+        self._model_view = None; self._model_gen = None; self._seed = seed
+        if (env_model is not None or resample_on_reset) and models is None:
+            raise ValueError('env_model / resample_on_reset need models=[...]')
+        self.resample_on_reset = bool(resample_on_reset)
+        if env_model is not None:
+            self.batch.set('ENV_MODEL', np.asarray(env_model, np.int32).reshape(n_env, 1))
 
     def _apply_reference(self):
         s = self.task._traj_generator._snippet
@@ -251,6 +262,26 @@ class BatchedFlyEnv:
                                      xfrc_applied=view('XFRC_APPLIED', (self.n_env, nbody, 6)))
         return self._force_views
 
+    def env_model(self):
+        """Zero-copy int32 torch view [n_env] of the model index every environment is stepped with (FB_ENV_MODEL; needs models=[...]).
+        The engine reads it when it picks an environment up; change an entry at an episode boundary only -- before a reset of that
+        environment, or while its step type is LAST (resample_on_reset does the latter)."""
+        if self._model_view is None:
+            import torch
+            iface = {'shape': (self.n_env,), 'typestr': '<i4', 'data': (self.batch.device_ptr('ENV_MODEL'), False), 'version': 2}
+            holder = type('DevBuf', (), {'__cuda_array_interface__': iface})()
+            self._model_view = torch.as_tensor(holder, device=f'cuda:{self.device}')
+        return self._model_view
+
+    def _resample_models(self):
+        """resample_on_reset: environments that just returned LAST get a new model id for the episode their auto-reset starts."""
+        import torch
+        if self._model_gen is None:
+            self._model_gen = torch.Generator(device=f'cuda:{self.device}'); self._model_gen.manual_seed(int(self._seed))
+        em = self.env_model()
+        new = torch.randint(0, self.batch.n_models, (self.n_env,), generator=self._model_gen, device=em.device, dtype=torch.int32)
+        em.copy_(torch.where(self.torch_views()['step_type'] == int(StepType.LAST), new, em))
+
     def clear_forces(self):
         """Free the applied-force arrays and return the batch to the plain step kernel; earlier applied_forces() views are dropped."""
         self._force_views = None
@@ -270,6 +301,8 @@ class BatchedFlyEnv:
         if self.control_callback is not None:
             self.control_callback(self)
         self.batch.step_ptr(action.data_ptr(), torch.cuda.current_stream().cuda_stream)
+        if self.resample_on_reset:
+            self._resample_models()
         self._time += self.control_timestep()
         return self.torch_views()
 
@@ -303,6 +336,8 @@ class BatchedFlyEnv:
         if self.control_callback is not None:
             self.control_callback(self)
         self.batch.step_ptr(t.data_ptr(), torch.cuda.current_stream().cuda_stream)
+        if self.resample_on_reset:
+            self._resample_models()
         torch.cuda.synchronize()
         ts = self._timestep()
         self._time = 0.0 if ts.first() else self._time + self.control_timestep()
@@ -312,8 +347,9 @@ class BatchedFlyEnv:
 def walk_imitation(ref_path: Optional[str] = None, force_actuators: bool = False, disable_wings: bool = True,
                    traj_indices: Optional[Sequence[int]] = None, random_state=None, terminal_com_dist: float = 0.3,
                    joint_filter: float = 0.01, n_env: int = 1, device: int = 0, precision: int = 64, seed: int = 0,
-                   env_id_base: int = 0) -> BatchedFlyEnv:
-    """Same keyword surface as flybody/fly_envs.py:100-106, plus n_env / device / precision / seed / env_id_base.
+                   env_id_base: int = 0, models=None, env_model=None, resample_on_reset: bool = False) -> BatchedFlyEnv:
+    """Same keyword surface as flybody/fly_envs.py:100-106, plus n_env / device / precision / seed / env_id_base and the
+    per-environment models of BatchedFlyEnv (models / env_model / resample_on_reset).
 
     ref_path: the reference's hdf5 walking dataset (needs h5py) or its .npz conversion (trajectory_loaders.WalkingDataset.save),
     or an already constructed loader; None = inference mode (reward == 1)."""
@@ -328,24 +364,27 @@ def walk_imitation(ref_path: Optional[str] = None, force_actuators: bool = False
             traj_loader = HDF5WalkingTrajectoryLoader(str(ref_path), traj_indices=traj_indices, random_state=random_state)
     return BatchedFlyEnv(n_env=n_env, device=device, precision=precision, terminal_com_dist=terminal_com_dist,
                          joint_filter=joint_filter, future_steps=64, time_limit=10.0, seed=seed, traj_loader=traj_loader,
-                         env_id_base=env_id_base, force_actuators=force_actuators, use_wings=not disable_wings)
+                         env_id_base=env_id_base, force_actuators=force_actuators, use_wings=not disable_wings,
+                         models=models, env_model=env_model, resample_on_reset=resample_on_reset)
 
 
 def walk_on_ball(force_actuators: bool = False, disable_wings: bool = True, random_state=None, n_env: int = 1, device: int = 0,
-                 precision: int = 64) -> BatchedFlyEnv:
+                 precision: int = 64, seed: int = 0, models=None, env_model=None, resample_on_reset: bool = False) -> BatchedFlyEnv:
     """Tethered fly walking on a floating ball: same keyword surface as flybody/fly_envs.py:158-191, plus n_env / device /
-    precision.  Observation = the walker observables + `ball_qvel`; reward = product of linear tolerances on the ball's
+    precision and the per-environment models of BatchedFlyEnv.  Observation = the walker observables + `ball_qvel`; reward = product of linear tolerances on the ball's
     angular velocity around the target (0, -5, 0) rad/s (tasks/walk_on_ball.py:62-73); 2 s episodes."""
     return BatchedFlyEnv(n_env=n_env, device=device, precision=precision, terminal_com_dist=float('inf'), joint_filter=0.01,
                          future_steps=0, time_limit=2.0, task='walk_on_ball', force_actuators=force_actuators,
-                         use_wings=not disable_wings)
+                         use_wings=not disable_wings, seed=seed, models=models, env_model=env_model, resample_on_reset=resample_on_reset)
 
 
 def flight_imitation(ref_path: Optional[str] = None, wpg_pattern_path: Optional[str] = None, force_actuators: bool = False,
                      disable_legs: bool = True, traj_indices: Optional[Sequence[int]] = None, randomize_start_step: bool = True,
                      joint_filter: float = 0.0, future_steps: int = 5, random_state=None, terminal_com_dist: float = 2.0,
-                     n_env: int = 1, device: int = 0, precision: int = 64, seed: int = 0, env_id_base: int = 0, dense=None) -> BatchedFlyEnv:
-    """Same keyword surface as flybody/fly_envs.py:30-39, plus n_env / device / precision / seed / env_id_base / dense (engine build).
+                     n_env: int = 1, device: int = 0, precision: int = 64, seed: int = 0, env_id_base: int = 0, dense=None,
+                     models=None, env_model=None, resample_on_reset: bool = False) -> BatchedFlyEnv:
+    """Same keyword surface as flybody/fly_envs.py:30-39, plus n_env / device / precision / seed / env_id_base / dense (engine build)
+    and the per-environment models of BatchedFlyEnv (models / env_model / resample_on_reset).
 
     ref_path: the reference's hdf5 flight dataset (needs h5py), its .npz conversion (trajectory_loaders.FlightDataset.save) or an
     already constructed loader; None = InferenceFlightTrajectoryLoader (the synthetic straight flight)."""
@@ -367,4 +406,5 @@ def flight_imitation(ref_path: Optional[str] = None, wpg_pattern_path: Optional[
     return BatchedFlyEnv(n_env=n_env, device=device, precision=precision, terminal_com_dist=terminal_com_dist,
                          joint_filter=joint_filter, future_steps=future_steps, time_limit=0.6, task='flight_imitation',
                          wbpg_tables=tables, seed=seed, traj_loader=traj_loader, env_id_base=env_id_base,
-                         force_actuators=force_actuators, use_legs=not disable_legs, dense=dense)
+                         force_actuators=force_actuators, use_legs=not disable_legs, dense=dense,
+                         models=models, env_model=env_model, resample_on_reset=resample_on_reset)

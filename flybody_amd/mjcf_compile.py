@@ -304,6 +304,104 @@ def _any_in(subs, s):
 
 
 # ----------------------------------------------------------------------------
+# -- kinematics at qpos0 in numpy (compile-time only) ---------------------------
+def fk0(m):
+    """Body frames (xpos, xquat) of the array dict `m` at qpos0."""
+    nbody = len(m['body_parent'])
+    xpos = np.zeros((nbody, 3)); xquat = np.tile([1., 0, 0, 0], (nbody, 1))
+    for bi in range(1, nbody):
+        p = m['body_parent'][bi]
+        if m['body_jntnum'][bi] and m['jnt_type'][m['body_jntadr'][bi]] == JNT_FREE:
+            q0 = m['qpos0'][m['jnt_qposadr'][m['body_jntadr'][bi]]:][:7]
+            xpos[bi] = q0[:3]; xquat[bi] = qnorm(q0[3:])
+        else:
+            xpos[bi] = xpos[p] + qrot(xquat[p], m['body_pos'][bi])
+            xquat[bi] = qmul(xquat[p], m['body_quat'][bi])
+        # hinge joints at ref: no rotation
+    return xpos, xquat
+
+
+def set_const0(m, springdamper=None):
+    """The constants MuJoCo's mj_setConst derives at the reference configuration, as a function of the array dict `m` (written into
+    it): dof_M0, M0_full, body_invweight0, dof_invweight0, tendon_invweight0.  The compiler calls it with the joints' `springdamper`
+    attributes ([njnt][2]: stiffness and damping of such a joint are set from its inertia at qpos0, before the inverse weights);
+    flybody_amd.randomization.vary_model calls it without (the compiled stiffness and damping stay)."""
+    nbody = len(m['body_parent']); nv = len(m['dof_bodyid'])
+    xpos, xquat = fk0(m)
+    xipos = np.array([xpos[b] + qrot(xquat[b], m['body_ipos'][b]) for b in range(nbody)])
+    # dof axes in world
+    dof_axis = np.zeros((nv, 3)); dof_anchor = np.zeros((nv, 3)); dof_isrot = np.zeros(nv, bool); dof_istrans = np.zeros(nv, bool)
+    for j in range(len(m['jnt_type'])):
+        b = m['jnt_bodyid'][j]; d = m['jnt_dofadr'][j]
+        if m['jnt_type'][j] == JNT_FREE:
+            R = q2mat(xquat[b])
+            for k in range(3):
+                dof_axis[d + k] = np.eye(3)[k]; dof_istrans[d + k] = True
+                dof_axis[d + 3 + k] = R[:, k]; dof_isrot[d + 3 + k] = True; dof_anchor[d + 3 + k] = xpos[b]
+        elif m['jnt_type'][j] == JNT_BALL:
+            R = q2mat(xquat[b])
+            for k in range(3):
+                dof_axis[d + k] = R[:, k]; dof_isrot[d + k] = True; dof_anchor[d + k] = xpos[b] + qrot(xquat[b], m['jnt_pos'][j])
+        else:
+            dof_axis[d] = qrot(xquat[b], m['jnt_axis'][j]); dof_isrot[d] = True
+            dof_anchor[d] = xpos[b] + qrot(xquat[b], m['jnt_pos'][j])
+    anc = [[] for _ in range(nbody)]   # dofs affecting each body
+    for b in range(1, nbody):
+        p = m['body_parent'][b]
+        anc[b] = anc[p] + list(range(m['body_dofadr'][b], m['body_dofadr'][b] + m['body_dofnum'][b]))
+
+    def jac(b, point):
+        Jp = np.zeros((3, nv)); Jr = np.zeros((3, nv))
+        for d in anc[b]:
+            if dof_istrans[d]:
+                Jp[:, d] = dof_axis[d]
+            else:
+                Jr[:, d] = dof_axis[d]; Jp[:, d] = np.cross(dof_axis[d], point - dof_anchor[d])
+        return Jp, Jr
+    M = np.diag(m['dof_armature'].astype(float))
+    for b in range(1, nbody):
+        if m['body_mass'][b] <= 0:
+            continue
+        Jp, Jr = jac(b, xipos[b])
+        R = q2mat(qmul(xquat[b], m['body_iquat'][b]))
+        Iw = R @ np.diag(m['body_inertia'][b]) @ R.T
+        M += m['body_mass'][b] * Jp.T @ Jp + Jr.T @ Iw @ Jr
+    m['dof_M0'] = np.diag(M).copy()
+    # springdamper (haltere): stiffness/damping from joint inertia at qpos0
+    for j in range(len(m['jnt_type']) if springdamper is not None else 0):
+        sd = springdamper[j]
+        if sd[0] > 0 and sd[1] > 0:
+            d = m['jnt_dofadr'][j]
+            inertia = M[d, d]
+            m['jnt_stiffness'][j] = inertia / max(MINVAL, sd[0]**2 * sd[1]**2)
+            m['dof_damping'][d] = 2 * inertia / max(MINVAL, sd[0])
+    Minv = np.linalg.inv(M)
+    biw = np.zeros((nbody, 2))
+    for b in range(1, nbody):
+        Jp, Jr = jac(b, xipos[b])
+        biw[b, 0] = np.trace(Jp @ Minv @ Jp.T) / 3
+        biw[b, 1] = np.trace(Jr @ Minv @ Jr.T) / 3
+    m['body_invweight0'] = biw
+    diw = np.zeros(nv)
+    for j in range(len(m['jnt_type'])):
+        d = m['jnt_dofadr'][j]
+        if m['jnt_type'][j] == JNT_FREE:
+            diw[d:d + 3] = np.mean(np.diag(Minv)[d:d + 3]); diw[d + 3:d + 6] = np.mean(np.diag(Minv)[d + 3:d + 6])
+        elif m['jnt_type'][j] == JNT_BALL:
+            diw[d:d + 3] = np.mean(np.diag(Minv)[d:d + 3])
+        else:
+            diw[d] = Minv[d, d]
+    m['dof_invweight0'] = diw
+    tiw = np.zeros(len(m['tendon_adr']))
+    for t in range(len(tiw)):
+        J = np.zeros(nv)
+        for w in range(m['tendon_adr'][t], m['tendon_adr'][t] + m['tendon_num'][t]):
+            J[m['wrap_dofid'][w]] = m['wrap_coef'][w]
+        tiw[t] = J @ Minv @ J
+    m['tendon_invweight0'] = tiw
+    m['M0_full'] = M
+
+
 class FlyCompiler:
     def __init__(self, xml_path: str, cfg: TaskConfig):
         self.cfg = cfg
@@ -950,96 +1048,8 @@ class FlyCompiler:
             i = self.bodies[i].parent
         return False
 
-    # -- kinematics at qpos0 in numpy (compile-time only) ---------------------------
-    def _fk0(self, m):
-        nbody = len(self.bodies)
-        xpos = np.zeros((nbody, 3)); xquat = np.tile([1., 0, 0, 0], (nbody, 1))
-        for bi in range(1, nbody):
-            p = m['body_parent'][bi]
-            if m['body_jntnum'][bi] and m['jnt_type'][m['body_jntadr'][bi]] == JNT_FREE:
-                q0 = m['qpos0'][m['jnt_qposadr'][m['body_jntadr'][bi]]:][:7]
-                xpos[bi] = q0[:3]; xquat[bi] = qnorm(q0[3:])
-            else:
-                xpos[bi] = xpos[p] + qrot(xquat[p], m['body_pos'][bi])
-                xquat[bi] = qmul(xquat[p], m['body_quat'][bi])
-            # hinge joints at ref: no rotation
-        return xpos, xquat
-
     def _set0(self, m, jnt):
-        nbody = len(self.bodies); nv = len(m['dof_bodyid'])
-        xpos, xquat = self._fk0(m)
-        xipos = np.array([xpos[b] + qrot(xquat[b], m['body_ipos'][b]) for b in range(nbody)])
-        # dof axes in world
-        dof_axis = np.zeros((nv, 3)); dof_anchor = np.zeros((nv, 3)); dof_isrot = np.zeros(nv, bool); dof_istrans = np.zeros(nv, bool)
-        for j in range(len(m['jnt_type'])):
-            b = m['jnt_bodyid'][j]; d = m['jnt_dofadr'][j]
-            if m['jnt_type'][j] == JNT_FREE:
-                R = q2mat(xquat[b])
-                for k in range(3):
-                    dof_axis[d + k] = np.eye(3)[k]; dof_istrans[d + k] = True
-                    dof_axis[d + 3 + k] = R[:, k]; dof_isrot[d + 3 + k] = True; dof_anchor[d + 3 + k] = xpos[b]
-            elif m['jnt_type'][j] == JNT_BALL:
-                R = q2mat(xquat[b])
-                for k in range(3):
-                    dof_axis[d + k] = R[:, k]; dof_isrot[d + k] = True; dof_anchor[d + k] = xpos[b] + qrot(xquat[b], m['jnt_pos'][j])
-            else:
-                dof_axis[d] = qrot(xquat[b], m['jnt_axis'][j]); dof_isrot[d] = True
-                dof_anchor[d] = xpos[b] + qrot(xquat[b], m['jnt_pos'][j])
-        anc = [[] for _ in range(nbody)]   # dofs affecting each body
-        for b in range(1, nbody):
-            p = m['body_parent'][b]
-            anc[b] = anc[p] + list(range(m['body_dofadr'][b], m['body_dofadr'][b] + m['body_dofnum'][b]))
-
-        def jac(b, point):
-            Jp = np.zeros((3, nv)); Jr = np.zeros((3, nv))
-            for d in anc[b]:
-                if dof_istrans[d]:
-                    Jp[:, d] = dof_axis[d]
-                else:
-                    Jr[:, d] = dof_axis[d]; Jp[:, d] = np.cross(dof_axis[d], point - dof_anchor[d])
-            return Jp, Jr
-        M = np.diag(m['dof_armature'].astype(float))
-        for b in range(1, nbody):
-            if m['body_mass'][b] <= 0:
-                continue
-            Jp, Jr = jac(b, xipos[b])
-            R = q2mat(qmul(xquat[b], m['body_iquat'][b]))
-            Iw = R @ np.diag(m['body_inertia'][b]) @ R.T
-            M += m['body_mass'][b] * Jp.T @ Jp + Jr.T @ Iw @ Jr
-        m['dof_M0'] = np.diag(M).copy()
-        # springdamper (haltere): stiffness/damping from joint inertia at qpos0
-        for j in range(len(m['jnt_type'])):
-            sd = jnt['springdamper'][j]
-            if sd[0] > 0 and sd[1] > 0:
-                d = m['jnt_dofadr'][j]
-                inertia = M[d, d]
-                m['jnt_stiffness'][j] = inertia / max(MINVAL, sd[0]**2 * sd[1]**2)
-                m['dof_damping'][d] = 2 * inertia / max(MINVAL, sd[0])
-        Minv = np.linalg.inv(M)
-        biw = np.zeros((nbody, 2))
-        for b in range(1, nbody):
-            Jp, Jr = jac(b, xipos[b])
-            biw[b, 0] = np.trace(Jp @ Minv @ Jp.T) / 3
-            biw[b, 1] = np.trace(Jr @ Minv @ Jr.T) / 3
-        m['body_invweight0'] = biw
-        diw = np.zeros(nv)
-        for j in range(len(m['jnt_type'])):
-            d = m['jnt_dofadr'][j]
-            if m['jnt_type'][j] == JNT_FREE:
-                diw[d:d + 3] = np.mean(np.diag(Minv)[d:d + 3]); diw[d + 3:d + 6] = np.mean(np.diag(Minv)[d + 3:d + 6])
-            elif m['jnt_type'][j] == JNT_BALL:
-                diw[d:d + 3] = np.mean(np.diag(Minv)[d:d + 3])
-            else:
-                diw[d] = Minv[d, d]
-        m['dof_invweight0'] = diw
-        tiw = np.zeros(len(m['tendon_adr']))
-        for t in range(len(tiw)):
-            J = np.zeros(nv)
-            for w in range(m['tendon_adr'][t], m['tendon_adr'][t] + m['tendon_num'][t]):
-                J[m['wrap_dofid'][w]] = m['wrap_coef'][w]
-            tiw[t] = J @ Minv @ J
-        m['tendon_invweight0'] = tiw
-        m['M0_full'] = M
+        set_const0(m, jnt['springdamper'])
 
     def _pairs(self, m, geoms):
         B = self.bodies

@@ -79,6 +79,8 @@ enum {
   FB_QFRC_APPLIED = 40,  /* [n_env][nv] physics real: MuJoCo's qfrc_applied, a generalised force per dof (caller-owned input, see below) */
   FB_XFRC_APPLIED = 41,  /* [n_env][nbody][6] physics real: MuJoCo's xfrc_applied, a Cartesian wrench per body: force(3) then torque(3) in the
                             world frame, applied at the body's centre of mass (xipos); the world body's row is ignored */
+  FB_ENV_MODEL = 42,     /* [n_env] int32: index into the models of fb_batch_create_group that the environment is stepped with (see below);
+                            fails on a batch made by fb_batch_create */
   FB_NFIELD
 };
 
@@ -92,7 +94,9 @@ enum { FB_WARN_CONTACT_CAP = 1, FB_WARN_EFC_CAP = 2, FB_WARN_SOLVER_MAXITER = 4,
                                        stays defined so that FB_WARN words keep their layout.) */,
        FB_WARN_SCHED_WAIT = 16 /* substep scheduler: the wait for an environment's previous substep hit its iteration cap (never observed).
                                   The environment's control step was ABANDONED (its row is not stepped concurrently with its holder);
-                                  fb_batch_synchronize / fb_batch_get fail from then on until the batch is destroyed. */ };
+                                  fb_batch_synchronize / fb_batch_get fail from then on until the batch is destroyed. */,
+       FB_WARN_MODEL_ID = 64 /* grouped batch: the environment's FB_ENV_MODEL entry was outside [0, n_models) when the kernel picked the
+                                environment up (only possible through the device pointer); it was clamped into range for that launch. */ };
 
 /* model dimensions by name: "nq","nv","nu","na","nbody","nobs","nsubstep", ... ; -1 if unknown */
 int fb_model_dim(const fb_model* m, const char* name);
@@ -192,7 +196,8 @@ int fb_batch_get(fb_batch* b, int field, void* dst_host, size_t bytes);
 int fb_batch_set(fb_batch* b, int field, const void* src_host, size_t bytes);
 
 /* Device pointer of a field (e.g. to wrap FB_OBS in a torch tensor without a copy): FB_OBS, FB_REWARD, FB_DISCOUNT, FB_STEP_TYPE, and the
- * applied-force arrays FB_QFRC_APPLIED / FB_XFRC_APPLIED at the batch's precision (allocating them: see fb_batch_clear_forces).  NULL otherwise. */
+ * applied-force arrays FB_QFRC_APPLIED / FB_XFRC_APPLIED at the batch's precision (allocating them: see fb_batch_clear_forces), and FB_ENV_MODEL of a
+ * grouped batch.  NULL otherwise. */
 void* fb_batch_device_ptr(fb_batch* b, int field);
 int fb_batch_synchronize(fb_batch* b, void* stream);
 
@@ -275,6 +280,27 @@ int fb_batch_inverse(fb_batch* b, int flags, void* stream);
  * Both precisions.  fb_batch_forces_active: 1 while the arrays are allocated, 0 otherwise. */
 int fb_batch_clear_forces(fb_batch* b);
 int fb_batch_forces_active(const fb_batch* b);
+
+/* Per-environment physics models in one batch (domain randomisation).  fb_batch_create_group creates n_env environments that share ONE
+ * tree and differ in real-valued constants: environment e is stepped with models[FB_ENV_MODEL[e]].  The models must be compatible with
+ * models[0]: the same arrays with the same shapes, every integer array equal (topology, types, ids, iteration counts, solver, task and
+ * action layout), opt_timestep and opt_control_timestep equal.  Every other real array may differ (masses, inertias, frames, sizes,
+ * qpos0, springs, ranges, damping, armature, gains, biases, pair_*, geom_fluid, gravity, density, viscosity, solref / solimp,
+ * invweights, stat_meaninertia); what the host derives from real constants (neighbour-list slack, bounding boxes, fluid geoms, total
+ * mass) is derived per model.  A violation fails with fb_last_error() naming the first array that differs.  At most FB_MAX_MODELS models;
+ * n_models == 1 steps like fb_batch_create (the plain kernels).  The batch keeps the model pointers: destroy the models after the batch.
+ * FB_ENV_MODEL is initialised to e % n_models and is available through fb_batch_get / fb_batch_set (ids outside [0, n_models) are
+ * rejected) / fb_batch_device_ptr.  The kernels read it when they pick the environment up: once per launch, or once per ticket of the
+ * substep scheduler.  A change is supported AT AN EPISODE BOUNDARY ONLY: before fb_batch_reset of the environment, or while its step type
+ * is LAST, so that the auto-reset of the next fb_batch_step runs under the new model (the forward pass of a reset recomputes every cached
+ * stage).  Changing it mid-episode is unsupported: the first substep would use the old model's position stage.  An id written out of
+ * range through the device pointer is clamped by the kernel and raises FB_WARN_MODEL_ID.
+ * The setters (fb_batch_set_reference, _time_limit, _wbpg, both datasets) apply to every model of the group.  fb_batch_step, _substep,
+ * _forward and _reset work at both precisions, under both schedulers and together with applied forces; fb_batch_ik, fb_batch_inverse
+ * and fb_batch_stage fail on a batch of more than one model (they never silently use model 0). */
+enum { FB_MAX_MODELS = 256 };
+int fb_batch_create_group(const fb_model* const* models, int n_models, int n_env, int device, int precision, fb_batch** out);
+int fb_batch_n_models(const fb_batch* b);
 
 const char* fb_last_error(void);
 
