@@ -631,7 +631,8 @@ template <typename T> struct R3 { T v0, v1, v2; };
 // S (small): the system has at most 64 rows, only v0 is live and the selects fold away
 template <bool S = false, typename T> FBD T r3_get(const R3<T>& f, int i) {
   if (S) return rdlane(f.v0, i);
-  T v = (i < 64) ? f.v0 : (i < 128 ? f.v1 : f.v2);
+  const T a = f.v0, b = f.v1, c = f.v2;              // (a choice between VALUES: between the members it is one between addresses, and a vector handed on by reference then stays in scratch)
+  T v = (i < 64) ? a : (i < 128 ? b : c);
   return rdlane(v, i & 63);
 }
 template <bool S = false, typename T> FBD void r3_set(R3<T>& f, int i, int lane, T v) {
@@ -670,14 +671,136 @@ template <bool S, typename real, typename ARP> FBD void res_axpy3(R3<double>& re
   }
 }
 
+// res += d0*AR[i,:], then res += d1*AR[i+1,:] -- the two rows are read in ONE round of LDS reads; the multiply-adds run in the order of
+// two res_axpy calls, and a zero delta leaves the residual as it is (to the bit: no update is applied, as when the call was skipped)
+template <bool S, typename real, typename ARP> FBD void res_axpy2(R3<double>& res, ARP AR, int i, int n, real d0, real d1, int lane) {
+  const int T0 = i*(i + 1)/2, T1 = T0 + i + 1;
+#pragma unroll
+  for (int q = 0; q < (S ? 1 : 3); q++) {
+    int k = lane + 64*q;
+    if (k < n) {
+      int tk = k*(k + 1)/2;
+      real a0 = AR[k <= i ? T0 + k : tk + i], a1 = AR[k <= i + 1 ? T1 + k : tk + i + 1];
+      double r = q == 0 ? res.v0 : (q == 1 ? res.v1 : res.v2);
+      r = (d0 != 0) ? r + (double)d0*(double)a0 : r;
+      r = (d1 != 0) ? r + (double)d1*(double)a1 : r;
+      if (q == 0) res.v0 = r; else if (q == 1) res.v1 = r; else res.v2 = r;
+    }
+  }
+}
+// value of row idx of a per-row register vector for a PER-LANE row index (ds_bpermute; every lane must call)
+template <bool S, typename T> FBD T r3_lane(const R3<T>& f, int idx) {
+  const T a = __shfl(f.v0, idx & 63, 64);
+  if (S) return a;
+  const T b = __shfl(f.v1, idx & 63, 64), c = __shfl(f.v2, idx & 63, 64);
+  return idx < 64 ? a : (idx < 128 ? b : c);
+}
+
+// ------------------------------------------------------------------ noslip passes (after either solver)
+// Friction dims only, regularisation removed, on the solver's registers: f the forces, res = b + AR f, rR the regulariser, rfr0 / rfr1 the
+// friction coefficients of a row's contact (lane k owns rows k, k + 64, k + 128; S: at most 64 rows, only v0 is live).  The forces stay in f;
+// the caller stores them.  Stated once: d_pgs runs it behind its sweeps, the Newton paths call it on what d_newton hands over in registers
+// (d_constraint_a) or through d_noslip_mem.
+// Lane == contact reads the constants of its own 2 x 2 friction block ONCE per solve -- the three entries of AR in one round of LDS reads,
+// R and the friction coefficients by lane shuffles -- and the serial loop takes them with v_readlane: a visit used to start with three LDS
+// reads at addresses recomputed every time and to end with two separate row updates (res_axpy2 reads both rows together).  Same values,
+// same operations in the same order: the passes are bit-identical given the same f and res.
+template <bool S, typename real, typename ARP>
+FBD void d_noslip(const DevModel<real>& M, const WS<real>& w, ARP AR, int nefc, int lane, R3<real>& f, R3<double>& res,
+                  const R3<real>& rR, const R3<real>& rfr0, const R3<real>& rfr1) {
+  PROF_BEGIN();
+  const int max_noslip = M.noslip_iterations;
+  const real noslip_tol = M.noslip_tolerance;
+  const real scale = (real)1 / (M.meaninertia * (real)(M.nv > 1 ? M.nv : 1));
+  int ncon = w.istate()[IS_NCON];
+  int my_efc;
+  { const int cl_ = lane < ncon ? lane : 0; const int cd_ = w.con_dim()[cl_], ce_ = w.con_efc()[cl_]; my_efc = (lane < ncon && cd_ > 1) ? ce_ : -1; }      // (both loads in one round)
+  real kA0 = 0, kA1 = 0, kA3 = 0;
+  const int ib = my_efc < 0 ? 0 : my_efc;
+  const real kF0 = r3_lane<S>(rfr0, ib), kF1 = r3_lane<S>(rfr1, ib), kR0 = r3_lane<S>(rR, ib + 1), kR1 = r3_lane<S>(rR, ib + 2);
+  if (my_efc >= 0) {
+    const real a11 = AR[ARIDX(ib+1, ib+1)], a21 = AR[ARIDX(ib+2, ib+1)], a22 = AR[ARIDX(ib+2, ib+2)];
+    kA0 = a11 - kR0; kA1 = a21; kA3 = a22 - kR1;
+  }
+  for (int it = 0; it < max_noslip; it++) {
+    real improvement = 0;
+    for (int c = 0; c < ncon; c++) {
+      int i = rdlane(my_efc, c);
+      if (i < 0) continue;
+      real fr[2] = {rdlane(kF0, c), rdlane(kF1, c)};
+      real rs[2], old[2], Rj[2] = {rdlane(kR0, c), rdlane(kR1, c)};
+      real fnrm = r3_get<S>(f, i);
+      for (int j = 0; j < 2; j++) {
+        old[j] = r3_get<S>(f, i+1+j);
+        rs[j] = (real)r3_get<S>(res, i+1+j) - Rj[j]*old[j];
+      }
+      real Ac[4] = {rdlane(kA0, c), rdlane(kA1, c), 0, rdlane(kA3, c)};
+      Ac[2] = Ac[1];
+      real bc[2] = {rs[0] - (Ac[0]*old[0] + Ac[1]*old[1]), rs[1] - (Ac[2]*old[0] + Ac[3]*old[1])};
+      real fq[2] = {0, 0};
+      if (fnrm >= FB_MINV) {
+        bool active = qcqp2(fq, Ac, bc, fr, fnrm);
+        if (active) {
+          real s = sqrt((fq[0]/fr[0])*(fq[0]/fr[0]) + (fq[1]/fr[1])*(fq[1]/fr[1]));
+          if (s > FB_MINV) { fq[0] *= fnrm/s; fq[1] *= fnrm/s; }
+        }
+      }
+      real del[2] = {fq[0] - old[0], fq[1] - old[1]};
+      improvement -= (real)0.5*(del[0]*(Ac[0]*del[0] + Ac[1]*del[1]) + del[1]*(Ac[2]*del[0] + Ac[3]*del[1])) + del[0]*rs[0] + del[1]*rs[1];
+      res_axpy2<S>(res, AR, i+1, nefc, del[0], del[1], lane);
+      for (int j = 0; j < 2; j++)
+        if (del[j] != 0) r3_set<S>(f, i+1+j, lane, fq[j]);
+    }
+    if (improvement*scale < noslip_tol) break;
+  }
+  PROF(P_NOSLIP);
+}
+
+// The hand-over through the environment's row, behind a solver that left its forces in efc_force: the per-row vectors are loaded and
+// res = b + AR f is rebuilt column by column (accumulated in FP64 in both builds).  The hand-over of d_newton_wide, of a matrix in global
+// memory, of the FP32 build -- and of every Newton solve when FB_NO_SOLVER_HANDOVER=1 is set at model load (d_constraint_a).
+template <bool S, typename real, typename ARP>
+FBD void noslip_load(const DevModel<real>& M, const WS<real>& w, ARP AR, int nefc, int lane, R3<real>& f, R3<double>& res,
+                     R3<real>& rR, R3<real>& rfr0, R3<real>& rfr1) {
+  PROF_BEGIN();
+  R3<real> rb;
+  r3_load<S>(f, w.efc_force(), nefc, lane, (real)0);
+  r3_load<S>(rb, w.efc_b(), nefc, lane, (real)0);
+  r3_load<S>(rR, w.efc_R(), nefc, lane, (real)0);
+  r3_load<S>(rfr0, w.efc_s1(), nefc, lane, (real)1);
+  r3_load<S>(rfr1, w.efc_s2(), nefc, lane, (real)1);
+  res.v0 = rb.v0; res.v1 = rb.v1; res.v2 = rb.v2;
+  for (int k = 0; k < nefc; k++) {
+    real fk = r3_get<S>(f, k);
+    if (fk != 0) res_axpy<S>(res, AR, k, nefc, fk, lane);
+  }
+  PROF(P_CSETUP);
+}
+template <bool S, typename real>
+FBD void noslip_store(const WS<real>& w, int nefc, int lane, const R3<real>& f) {
+  if (lane < nefc) w.efc_force()[lane] = f.v0;
+  if (!S) {
+    if (lane + 64 < nefc) w.efc_force()[lane + 64] = f.v1;
+    if (lane + 128 < nefc) w.efc_force()[lane + 128] = f.v2;
+  }
+}
+template <typename real, typename ARP, bool S>
+FB_STAGE_A void d_noslip_mem(const DevModel<real>& M, const WS<real>& w, ARP AR, int nefc, int lane) {
+  R3<real> f, rR, rfr0, rfr1;
+  R3<double> res;
+  noslip_load<S>(M, w, AR, nefc, lane, f, res, rR, rfr0, rfr1);
+  d_noslip<S>(M, w, AR, nefc, lane, f, res, rR, rfr0, rfr1);
+  noslip_store<S>(w, nefc, lane, f);
+}
+
 // PGS + noslip sweeps; ARP is an LDS (address_space(3)) or a global pointer to the Delassus matrix.
 // Residual-maintaining Gauss-Seidel: the vector res = b + AR f lives in registers (lane k owns rows k, k+64,
 // k+128); a row update reads its residual with v_readlane and, if the force changed by delta, adds
 // delta * AR[row,:] to every lane's residuals -- one LDS row read and one FMA per lane, no reduction on the
 // critical path.  Mathematically identical to recomputing each row's dot product.
-// `sweeps` false: the forces in efc_force are final (the Newton solver produced them) and only the noslip passes run.
+// The noslip passes follow on the same registers (d_noslip); the Newton paths do not come through here.
 template <typename real, typename ARP, bool S>
-FB_STAGE_A int d_pgs(const DevModel<real>& M, const WS<real>& w, ARP AR, int nefc, int lane, bool sweeps = true) {
+FB_STAGE_A int d_pgs(const DevModel<real>& M, const WS<real>& w, ARP AR, int nefc, int lane) {
   int nv = M.nv;
   PROF_BEGIN();
   R3<real> f, rb, rR, rfr0, rfr1, rla, rdiag;
@@ -707,7 +830,7 @@ FB_STAGE_A int d_pgs(const DevModel<real>& M, const WS<real>& w, ARP AR, int nef
     real fk = r3_get<S>(f, k);
     if (fk != 0) res_axpy<S>(res, AR, k, nefc, fk, lane);
   }
-  if (sweeps) {
+  {
     // dual cost of the warm start 0.5 f'ARf + f'b; fall back to zero force if it is worse than zero
     real c = (real)0.5*(f.v0*((real)res.v0 + rb.v0) + f.v1*((real)res.v1 + rb.v1) + f.v2*((real)res.v2 + rb.v2));
     c = wave_sum(c);
@@ -721,7 +844,7 @@ FB_STAGE_A int d_pgs(const DevModel<real>& M, const WS<real>& w, ARP AR, int nef
 #define FB_C3Z(name) name.v0 = 0; name.v1 = 0; name.v2 = 0;
   FB_C3Z(cA00) FB_C3Z(cA01) FB_C3Z(cA02) FB_C3Z(cA11) FB_C3Z(cA12) FB_C3Z(cA22) FB_C3Z(cEc) FB_C3Z(cEs) FB_C3Z(cE1) FB_C3Z(cE2) FB_C3Z(cR1) FB_C3Z(cR2) FB_C3Z(cI00)
 #undef FB_C3Z
-  if (sweeps) {
+  {
     real t[13][3];
     for (int q = 0; q < (S ? 1 : 3); q++) {
       int r = lane + 64*q;
@@ -764,8 +887,8 @@ FB_STAGE_A int d_pgs(const DevModel<real>& M, const WS<real>& w, ARP AR, int nef
   // ---- projected Gauss-Seidel over rows; elliptic contacts are updated as 3-row blocks
   real scale = (real)1 / (M.meaninertia * (real)(nv > 1 ? nv : 1));
   // solver options into registers: a read of the model inside the sweep loop would sit on the critical path of every sweep
-  const int max_it = sweeps ? M.iterations : 0, max_noslip = M.noslip_iterations;
-  const real tol_scaled = M.tolerance, noslip_tol = M.noslip_tolerance;
+  const int max_it = M.iterations;
+  const real tol_scaled = M.tolerance;
   int niter = 0;
   if (S) {
   // ---- branch-lean sweep for systems of <= 64 rows (every row lives in lane == row).
@@ -1000,47 +1123,9 @@ FB_STAGE_A int d_pgs(const DevModel<real>& M, const WS<real>& w, ARP AR, int nef
   if (lane == 0) { long long* pp_ = (long long*)w.prof(); pp_[31] += bt_[4]; pp_[16] += bt_[0]; pp_[22] += bt_[1]; pp_[23] += bt_[2]; }
 #endif
   PROF(P_PGS);
-  // ---- noslip: friction dims only, regularisation removed; lane == contact keeps its row address
-  int ncon = w.istate()[IS_NCON];
-  int my_efc;
-  { const int cl_ = lane < ncon ? lane : 0; const int cd_ = w.con_dim()[cl_], ce_ = w.con_efc()[cl_]; my_efc = (lane < ncon && cd_ > 1) ? ce_ : -1; }      // (both loads in one round)
-  for (int it = 0; it < max_noslip; it++) {
-    real improvement = 0;
-    for (int c = 0; c < ncon; c++) {
-      int i = rdlane(my_efc, c);
-      if (i < 0) continue;
-      real fr[2] = {r3_get<S>(rfr0, i), r3_get<S>(rfr1, i)};
-      real rs[2], old[2], Rj[2];
-      real fnrm = r3_get<S>(f, i);
-      for (int j = 0; j < 2; j++) {
-        old[j] = r3_get<S>(f, i+1+j);
-        Rj[j] = r3_get<S>(rR, i+1+j);
-        rs[j] = (real)r3_get<S>(res, i+1+j) - Rj[j]*old[j];
-      }
-      real Ac[4] = {AR[ARIDX(i+1, i+1)] - Rj[0], AR[ARIDX(i+2, i+1)],
-                    AR[ARIDX(i+2, i+1)], AR[ARIDX(i+2, i+2)] - Rj[1]};
-      real bc[2] = {rs[0] - (Ac[0]*old[0] + Ac[1]*old[1]), rs[1] - (Ac[2]*old[0] + Ac[3]*old[1])};
-      real fq[2] = {0, 0};
-      if (fnrm >= FB_MINV) {
-        bool active = qcqp2(fq, Ac, bc, fr, fnrm);
-        if (active) {
-          real s = sqrt((fq[0]/fr[0])*(fq[0]/fr[0]) + (fq[1]/fr[1])*(fq[1]/fr[1]));
-          if (s > FB_MINV) { fq[0] *= fnrm/s; fq[1] *= fnrm/s; }
-        }
-      }
-      real del[2] = {fq[0] - old[0], fq[1] - old[1]};
-      improvement -= (real)0.5*(del[0]*(Ac[0]*del[0] + Ac[1]*del[1]) + del[1]*(Ac[2]*del[0] + Ac[3]*del[1])) + del[0]*rs[0] + del[1]*rs[1];
-      for (int j = 0; j < 2; j++)
-        if (del[j] != 0) { res_axpy<S>(res, AR, i+1+j, nefc, del[j], lane); r3_set<S>(f, i+1+j, lane, fq[j]); }
-    }
-    if (improvement*scale < noslip_tol) break;
-  }
-  PROF(P_NOSLIP);
-  if (lane < nefc) w.efc_force()[lane] = f.v0;
-  if (!S) {
-    if (lane + 64 < nefc) w.efc_force()[lane + 64] = f.v1;
-    if (lane + 128 < nefc) w.efc_force()[lane + 128] = f.v2;
-  }
+  // ---- noslip passes on the same registers
+  if (M.noslip_iterations > 0) d_noslip<S>(M, w, AR, nefc, lane, f, res, rR, rfr0, rfr1);
+  noslip_store<S>(w, nefc, lane, f);
   return niter;
 }
 
@@ -1126,6 +1211,14 @@ __device__ __forceinline__ bool d_constraint_a(const DevModel<real>& M, const WS
   if (!newton_any) SYNC();
   int niter;
   const int tri = nefc*(nefc + 1)/2;
+  // Round 7: Newton hands its result over IN REGISTERS (NwOut, fb_newton.hpp) for a system of at most one row per lane with its matrix in LDS
+  // -- slot, parked factor or wide placement: the noslip passes start from the force and the residual as d_newton returns them (R and the
+  // friction coefficients are loaded in the round of loads the passes open with), and the J'f pass below takes the force from the same
+  // register; no fence waits for the store of efc_force (which stays: later stages and fb_batch_get read it).  FB_NO_SOLVER_HANDOVER=1 at model load keeps the hand-over through the environment's
+  // row, for comparison; the FP32 build keeps it too (its residual is accumulated in FP64), as do d_newton_wide and a matrix in global memory.
+  const bool hand_ok = sizeof(real) == 8 && uniform_int(M.solver_handover) != 0;
+  const bool noslip = uniform_int(M.noslip_iterations) > 0;
+  bool fr_reg = false; real fr = 0;                  // the force of row `lane` is in `fr` (no reload for J'f)
   if (nefc <= LdsCfg<real>::WIDE_ROWS) {
     // Delassus matrix in LDS.  A system that does not fit the matrix slot alone borrows the factor row in front of it (the
     // pool is contiguous): the factor is parked in the environment's global row during the solve -- two coalesced passes
@@ -1153,15 +1246,31 @@ __device__ __forceinline__ bool d_constraint_a(const DevModel<real>& M, const WS
       // (two instantiations by system size: <= FB_NEWTON_NT rows -- 93 % of the solves -- runs the register-tile code alone, the rest the
       //  lane == row code alone)
       constexpr int MT = 1, MR = 2;
-      if (k_in_slot && nefc <= FB_NEWTON_NT) niter = d_newton<real, const FB_LDS real*, FB_LDS real*, MT>(M, wc, arp, w.lAR() + tri, nefc, lane);
-      else if (k_in_slot) niter = d_newton<real, const FB_LDS real*, FB_LDS real*, MR>(M, wc, arp, w.lAR() + tri, nefc, lane);
-      else if (!wide) niter = d_newton<real, const FB_LDS real*, FB_LDS real*, MR>(M, wc, arp, w.lLD, nefc, lane);
-      else if (2*tri <= FB_LDS_SCRATCH + LdsCfg<real>::AR_ELEMS) niter = d_newton<real, const FB_LDS real*, FB_LDS real*, MR>(M, wc, arp, w.lLD + tri, nefc, lane);
-      else niter = d_newton<real, const FB_LDS real*, real*, MR>(M, wc, arp, w.AR() + tri, nefc, lane);
-      SYNC();
+      NwOut<real> r;
+      // (K in LDS: behind AR in the matrix slot, in the parked factor row, or behind the wide matrix -- one call site for the three)
+      FB_LDS real* const kl = k_in_slot ? w.lAR() + tri : (wide ? w.lLD + tri : w.lLD);
+      if (k_in_slot && nefc <= FB_NEWTON_NT) r = d_newton<real, const FB_LDS real*, FB_LDS real*, MT, true>(M, wc, arp, kl, nefc, lane);
+      else if (!wide || 2*tri <= FB_LDS_SCRATCH + LdsCfg<real>::AR_ELEMS) r = d_newton<real, const FB_LDS real*, FB_LDS real*, MR, true>(M, wc, arp, kl, nefc, lane);
+      else r = d_newton<real, const FB_LDS real*, real*, MR, true>(M, wc, arp, w.AR() + tri, nefc, lane);
+      niter = r.niter;
+      if (!hand_ok) SYNC();
+      fr = r.f;
+      if (noslip) {
+        // the noslip passes, stated once for both hand-overs
+        R3<real> f, rR, rfr0, rfr1;
+        R3<double> res;
+        if (hand_ok) {
+          f.v0 = r.f; f.v1 = 0; f.v2 = 0; res.v0 = (double)r.res; res.v1 = 0; res.v2 = 0;
+          r3_load<true>(rR, w.efc_R(), nefc, lane, (real)0); r3_load<true>(rfr0, w.efc_s1(), nefc, lane, (real)1); r3_load<true>(rfr1, w.efc_s2(), nefc, lane, (real)1);
+        }
+        else noslip_load<true>(M, w, arp, nefc, lane, f, res, rR, rfr0, rfr1);
+        d_noslip<true>(M, w, arp, nefc, lane, f, res, rR, rfr0, rfr1);
+        noslip_store<true>(w, nefc, lane, f);
+        fr = f.v0;
+      }
+      fr_reg = hand_ok;
     }
-    // PGS sweeps (when PGS is the solver) and the noslip passes (after either solver)
-    if (!newton || M.noslip_iterations > 0) { const int it2 = d_pgs<real, const FB_LDS real*, true>(M, w, arp, nefc, lane, !newton); if (!newton) niter = it2; }
+    else niter = d_pgs<real, const FB_LDS real*, true>(M, w, arp, nefc, lane);      // PGS sweeps (opt_solver = 0) and the noslip passes behind them
     if (park) {
       SYNC();
       for (int i = lane; i < M.nM; i += FB_WAVE) w.lLD[i] = w.qLD()[i];
@@ -1171,16 +1280,17 @@ __device__ __forceinline__ bool d_constraint_a(const DevModel<real>& M, const WS
   else if (nefc <= 64) {
     if (newton) {
       const WS<real> wc = w;
-      niter = d_newton<real, const real*, real*, 2>(M, wc, (const real*)w.AR(), w.AR() + tri, nefc, lane);       // (beyond the LDS slot: > 16 rows)
+      niter = d_newton<real, const real*, real*, 2>(M, wc, (const real*)w.AR(), w.AR() + tri, nefc, lane).niter;       // (beyond the LDS slot: > 16 rows)
       SYNC();
+      if (noslip) d_noslip_mem<real, const real*, true>(M, w, (const real*)w.AR(), nefc, lane);
     }
-    if (!newton || M.noslip_iterations > 0) { const int it2 = d_pgs<real, const real*, true>(M, w, (const real*)w.AR(), nefc, lane, !newton); if (!newton) niter = it2; }
+    else niter = d_pgs<real, const real*, true>(M, w, (const real*)w.AR(), nefc, lane);
   }
   else if (newton_any) {
     const WS<real> wc = w;
     niter = d_newton_wide<real>(M, wc, nefc, lane);
     SYNC();
-    if (M.noslip_iterations > 0) d_pgs<real, const real*, false>(M, w, (const real*)w.AR(), nefc, lane, false);
+    if (noslip) d_noslip_mem<real, const real*, false>(M, w, (const real*)w.AR(), nefc, lane);
   }
   else niter = d_pgs<real, const real*, false>(M, w, (const real*)w.AR(), nefc, lane);
   if (lane == 0) {
@@ -1189,7 +1299,7 @@ __device__ __forceinline__ bool d_constraint_a(const DevModel<real>& M, const WS
     int wbits = (niter >= M.iterations ? WARN_SOLVER_MAXITER : 0);
     if (wbits) { atomicOr(w.istate() + IS_WARN, wbits); atomicOr(w.istate() + IS_WARN_EVER, wbits); }
   }
-  SYNC();
+  if (!fr_reg) SYNC();               // (hand-over in registers: nothing from here to the end of the function reads another lane's efc_force from memory)
   if (nefc <= FB_WAVE) {
     // ---- qfrc_constraint = J^T f, one lane per dof: lane == row keeps (force, last dof of each chain) in registers and
     // broadcasts them with v_readlane; dof i collects J[side][depth(i)][r] f_r from every row whose chain runs through it
@@ -1197,7 +1307,7 @@ __device__ __forceinline__ bool d_constraint_a(const DevModel<real>& M, const WS
     // (round 5: the chain ends come per row from make_constraint -- they used to be looked up here through efc_bA / efc_lA -> body_chain,
     //  two dependent round trips -- and the Jacobian entries of EIGHT rows are in flight together: the row-by-row loop waited for a
     //  global round trip per row, 12-24 per substep)
-    real fr = (lane < nefc) ? w.efc_force()[lane] : (real)0;
+    if (!fr_reg) fr = (lane < nefc) ? w.efc_force()[lane] : (real)0;
     int eA = (lane < nefc) ? w.efc_eA()[lane] : -1, eB = (lane < nefc) ? w.efc_eB()[lane] : -1;
     int dep[2], nd[2]; real acc[2] = {0, 0};
 #pragma unroll

@@ -1039,6 +1039,8 @@ static int build_devmodel(fb_batch* b, const fb_model* m, DevModel<real>& M) {
   }
   M.ar_entry_lanes = 1;
   { const char* e_ = getenv("FB_NO_AR_ENTRY_LANES"); if (e_ && e_[0] == '1') M.ar_entry_lanes = 0; }      // (read at model load, like the switch above: the tests compare the two builds of the Delassus matrix bit for bit)
+  M.solver_handover = 1;
+  { const char* e_ = getenv("FB_NO_SOLVER_HANDOVER"); if (e_ && e_[0] == '1') M.solver_handover = 0; }      // (read at model load, like the two above: the tests compare the two hand-overs against the oracle and each other)
   M.noslip_tolerance = (real)m->d("opt_noslip_tolerance")[0]; M.meaninertia = (real)m->d("stat_meaninertia")[0];
   M.totalmass = (real)m->totalmass;
   size_t c;

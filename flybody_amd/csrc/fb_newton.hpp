@@ -523,12 +523,26 @@ FB_NEWTON_ATTR real nw_gj32(KP K, int n_act_, unsigned long long m_act, real dg,
   SYNC();                                                            // (K is rewritten by the next iteration)
   return mine ? zr : (real)0;
 }
+// What d_newton returns, in registers (lane == row; zero beyond the system): the iteration count, the final force and, when the noslip
+// passes will take it (nw_hands_over), res = b + AR f at that force -- what the noslip passes and the J'f pass of d_constraint_a start
+// from.  (They used to reload the force from the environment's row behind a wave fence that waited for its store, and to rebuild res
+// column by column: one LDS row read, one multiply-add and one branch per row.)  What the solver did NOT compute -- R and the friction
+// coefficients of the row's contact -- is not part of it: the noslip passes open with a round of loads from the row anyway (contact
+// count, dimensions, first rows), these three ride in it, and three doubles fewer cross the call (with them in the struct the default
+// build's step kernels kept two more registers in scratch around the stage).
+template <typename real> struct NwOut { int niter; real f, res; };
+// the register hand-over with the residual: FP64, matrix in LDS, noslip passes to run, not switched off at model load (FB_NO_SOLVER_HANDOVER=1)
+template <typename real, bool HAND> FBD bool nw_hands_over(const DevModel<real>& M) {
+  if (sizeof(real) != 8 || !HAND) return false;
+  return uniform_int(M.solver_handover) != 0 && uniform_int(M.noslip_iterations) > 0;
+}
 // ARP / KP: LDS (address_space(3)) or global pointers to the packed lower triangles of AR and of the work matrix K.
-// Returns the number of Newton iterations; the forces are left in efc_force.
+// Returns the number of Newton iterations and the hand-over above; the forces are left in efc_force as well.
 // MODE: 1 = the caller guarantees nefc <= FB_NEWTON_NT (tile layout only: the lane == row code is not compiled in), 2 = nefc > FB_NEWTON_NT
-// (no tile-layout code), 0 = decided at run time.
-template <typename real, typename ARP, typename KP, int MODE = 0>
-FB_NEWTON_ATTR int d_newton(const DevModel<real>& M_, const WS<real>& w_, ARP AR, KP K, int nefc, int lane) {
+// (no tile-layout code), 0 = decided at run time.  HAND: the caller takes the register hand-over (matrix in LDS; the two pointer kinds are one
+// type in the host emulation, hence a parameter of its own).
+template <typename real, typename ARP, typename KP, int MODE = 0, bool HAND = false>
+FB_NEWTON_ATTR NwOut<real> d_newton(const DevModel<real>& M_, const WS<real>& w_, ARP AR, KP K, int nefc, int lane) {
   const DevModel<real>& M = as_constant(M_); const WS<real> w = ws_uniform(w_, M);
   const int n = nefc;
   const bool on = lane < n;
@@ -928,10 +942,17 @@ FB_NEWTON_ATTR int d_newton(const DevModel<real>& M_, const WS<real>& w_, ARP AR
     if (-g0*alpha*scale < tol) break;
   }
   if (on) w.efc_force()[lane] = o.f;
-  if (tile) { if (on) ARw[lane*(lane + 1)/2 + lane] = ar_diag; SYNC_LDS(); }
+  NwOut<real> out;
+  out.niter = niter; out.f = on ? o.f : (real)0; out.res = 0;      // (c.s1 / c.s2: efc_s1 / efc_s2 of the row -- 1 on scalar rows either way)
+  // res = b + A f + R f at the FINAL force o.f (lam is the iterate before the last constraint update: the two differ at solver tolerance,
+  // not at rounding): one more product on the tile / the lane == row code
+  // (asked for by the model, read here and not handed in: an argument would stay live through the whole solve.  FP64 with the matrix in LDS
+  //  only (HAND) -- the FP32 build accumulates the noslip residual in FP64, a matrix in global memory keeps the hand-over through the row)
+  if (nw_hands_over<real, HAND>(M)) { const real Af = amul(out.f); out.res = on ? (b + Af) + R*out.f : (real)0; }
+  if (tile) { if (on) ARw[lane*(lane + 1)/2 + lane] = ar_diag; SYNC_LDS(); }      // (the regulariser is back on the diagonal before the noslip passes read AR)
   if (n > FB_NEWTON_NT) FB_SETPRIO(uniform_int(w.istate()[IS_PRIO]));
 #if defined(FB_PROFILE) && !defined(FB_EMULATE)
   if (lane == 0) { long long* pp_ = (long long*)w.prof(); for (int k_ = 0; k_ < 7; k_++) pp_[32 + k_] += nwp_[k_]; pp_[39] += nwc_[0]; pp_[40] += nwc_[1]; pp_[41] += 1; }
 #endif
-  return niter;
+  return out;
 }

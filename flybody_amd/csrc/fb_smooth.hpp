@@ -827,10 +827,6 @@ FB_STAGE_FS void d_factor_tail(const DevModel<real>& M_, const WS<real>& w_, con
     int dp = has ? w.ldepth()[j] : 31, mj = has ? w.lmadr()[j] : 0;
     fd[q] = ((mj - dp*(dp + 1)/2) & 0x1fff) | (dp << 13);
   }
-  // (the work words of the normalisation below: fetched here, ahead of the reductions, so that their latency is covered)
-  int fw[FB_FSLOT];
-#pragma unroll
-  for (int s = 0; s < FB_FSLOT; s++) fw[s] = M.fac_w[s*FB_WAVE + lane];
   // trunk: S[a,b] = M[a,b] - sum_{k >= nT} M~[k,a] M~[k,b] / D[k], then dense LDL (every lane, uniform values)
   real S[FB_NTT], xt[FB_MAXTRUNK];
 #pragma unroll
@@ -854,36 +850,48 @@ FB_STAGE_FS void d_factor_tail(const DevModel<real>& M_, const WS<real>& w_, con
       }
     }
   }
+  // (the work words of the normalisation below: fetched ahead of the reductions, so that their latency is covered -- and behind the
+  //  column products above, whose operands they would otherwise sit next to)
+  int fw[FB_FSLOT];
+#pragma unroll
+  for (int s = 0; s < FB_FSLOT; s++) fw[s] = M.fac_w[s*FB_WAVE + lane];
 #pragma unroll
   for (int a = 0; a < FB_MAXTRUNK; a++) xt[a] = (a < nT) ? x[a] - wave_sum(xt[a]) : (real)0;
   // (round 5: the 21 + 6 trunk loads of M in ONE round, issued before the reductions that consume them.  Written entry by entry --
   //  load, reduce, subtract -- each load's latency was covered by one wave_sum only: 21 exposed round trips per factorisation)
+  // (round 7: ONE LANE PER ENTRY.  Every lane used to load all 27 values from the same wave-uniform addresses -- 54 registers of identical
+  //  values next to S, xt and the work words, which the 168-register budget of the 12-per-CU build answered with 29 scratch stores + 29
+  //  reloads on this straight-line path.  Lane e < FB_NTT now holds trunk entry e of M, lanes FB_NTT .. FB_NTT + 5 the six damping terms;
+  //  each is broadcast with v_readlane where S[e] is formed.  Same additions and subtractions on the same values: the same bits.)
   {
-    real m0[FB_NTT], dadd[FB_MAXTRUNK];
+    static_assert(FB_NTT + FB_MAXTRUNK <= FB_WAVE, "one lane per trunk entry of M and per damping term");
+    int ta = 0;
 #pragma unroll
-    for (int a = 0; a < FB_MAXTRUNK; a++) {
-      dadd[a] = diag_add ? hscale*diag_add[a < nT ? a : 0] : (real)0;
-#pragma unroll
-      for (int b2 = 0; b2 <= a; b2++) m0[a*(a + 1)/2 + b2] = qM[a < nT ? a*(a + 1)/2 + (a - b2) : 0];      // trunk dof a sits at depth a: its row of M starts at a(a+1)/2
-    }
+    for (int k = 1; k < FB_MAXTRUNK; k++) ta = (lane >= k*(k + 1)/2) ? k : ta;
+    const int tb = lane - ta*(ta + 1)/2;                                         // lane e < FB_NTT: entry (ta, tb) of the trunk block
+    const int da = lane - FB_NTT;                                                // lane FB_NTT + a: damping term a
+    real mt = (real)0;
+    if (lane < FB_NTT) mt = qM[ta < nT ? ta*(ta + 1)/2 + (ta - tb) : 0];         // trunk dof a sits at depth a: its row of M starts at a(a+1)/2
+    else if (da < FB_MAXTRUNK && diag_add) mt = hscale*diag_add[da < nT ? da : 0];
 #pragma unroll
     for (int a = 0; a < FB_MAXTRUNK; a++)
 #pragma unroll
       for (int b2 = 0; b2 <= a; b2++) {
         const int e = a*(a + 1)/2 + b2;
-        real m = m0[e];
-        if (a == b2) m += dadd[a];
+        real m = rdlane(mt, e);
+        if (a == b2) m += rdlane(mt, FB_NTT + a);
         S[e] = (a < nT) ? m - wave_sum(S[e]) : (real)0;
       }
   }
   SYNC();
   // normalise the published rows: L[i,j] = M~[i,j] / D[i]
   // (branch-free: all reads in flight together, an empty slot reads row 0 and writes the dummy word behind the factor)
-  // (in two halves of the slots: all 18 in flight at once need 90 registers next to the 54 of the trunk's Schur complement, which the
-  // 168-register budget of the 12-per-CU build answered with 42 scratch stores + 42 reloads per factorisation)
+  // (in three rounds of six slots: all 18 in flight at once need 90 registers next to the 54 of the trunk's Schur complement, which the
+  // 168-register budget of the 12-per-CU build answered with 42 scratch stores + 42 reloads per factorisation; two rounds of nine still
+  // reached into the callee-saved registers -- five of them saved and restored around the body)
 #pragma unroll
-  for (int h = 0; h < 2; h++) {
-    constexpr int HS = FB_FSLOT/2;
+  for (int h = 0; h < 3; h++) {
+    constexpr int HS = FB_FSLOT/3;
     real v[HS], dd[HS]; int adr[HS];
 #pragma unroll
     for (int s = 0; s < HS; s++) {

@@ -127,6 +127,7 @@ struct DevModel {
   real timestep, control_timestep, grav[3], density, viscosity, impratio, tolerance, noslip_tolerance, meaninertia, totalmass;
   real vl_delta;             // slack of the mid-phase neighbour list (fb_collide.hpp): FB_VL_SCALE x the median bounding radius of the model's geoms (0: no list)
   int ar_entry_lanes;        // Delassus matrix of a system of <= 64 rows: 1 = one lane per lower-triangle entry, 0 = lane == column with a loop over the rows (fb_constraint.hpp)
+  int solver_handover;       // Newton on a system of <= 64 rows with its matrix in LDS: 1 = force, residual and R reach the noslip passes and J'f in registers, 0 = through the environment's row (fb_constraint.hpp: d_constraint_a)
   // topology
   GP<const int> body_parent, body_dofadr, body_nsub, body_depth;
   GP<const int> body_chlen;     // [nbody] number of dofs on the root->body chain

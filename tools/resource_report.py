@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Per-function register / scratch table of an engine build, from the assembly hipcc emits (no GPU needed): VGPRs, scratch bytes per
-lane, scratch instructions (spill reloads and local arrays), instruction count.
+lane, scratch instructions (spill reloads and local arrays), instruction count, occupancy.  The stage functions and kernels of the precision asked for,
+and the instantiations of the Newton solver (d_newton<matrix, work matrix, MODE>: LDS or global pointers).
 resource_report.py [d|f] [extra hipcc flags...]      e.g.  resource_report.py d -DFB_F64_DENSE=1"""
 import os, re, subprocess, sys, tempfile
 ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), '..')
@@ -15,7 +16,7 @@ subprocess.check_call([os.environ.get('HIPCC', '/opt/rocm/bin/hipcc'), '--offloa
 lines = open(out).read().splitlines(); os.unlink(out)
 tag = 'I%sE' % prec
 i = 0
-print('%-34s %6s %5s %7s %7s %7s %6s' % ('function', 'instr', 'vgpr', 'scratch', 'sc_ld', 'sc_st', 'sgprsp'))
+print('%-34s %6s %5s %7s %7s %7s %4s %6s' % ('function', 'instr', 'vgpr', 'scratch', 'sc_ld', 'sc_st', 'occ', 'sgprsp'))      # occ: waves per SIMD of a kernel (-1: a function)
 while i < len(lines):
     m = re.match(r'^(_Z\w+):', lines[i])
     if not m: i += 1; continue
@@ -28,8 +29,10 @@ while i < len(lines):
         mm = re.match(r'^; (\w+): (\d+)', lines[j])
         if mm: meta[mm.group(1)] = int(mm.group(2))
         j += 1
-    if tag in name:
+    mn = re.match(r'^_Z8d_newtonI%s(PU3AS3K|PK)[df](PU3AS3|P)[df]Li(\d)E' % prec, name)      # d_newton<real, ARP, KP, MODE>: one line per instantiation
+    if tag in name or mn:
         short = re.sub(r'^_Z\d+', '', name)
         short = re.split(r'I[df]E', short)[0]
-        print('%-34s %6d %5d %7d %7d %7d %6s' % (short, len(body), meta.get('NumVgprs', -1), meta.get('ScratchSize', -1),
-              sum(x.startswith('scratch_load') for x in body), sum(x.startswith('scratch_store') for x in body), meta.get('NumSgprs', '')))
+        if mn: short = 'd_newton<%s,%s,%s>' % ('LDS' if 'AS3' in mn.group(1) else 'global', 'LDS' if 'AS3' in mn.group(2) else 'global', mn.group(3))
+        print('%-34s %6d %5d %7d %7d %7d %4d %6s' % (short, len(body), meta.get('NumVgprs', -1), meta.get('ScratchSize', -1),
+              sum(x.startswith('scratch_load') for x in body), sum(x.startswith('scratch_store') for x in body), meta.get('Occupancy', -1), meta.get('NumSgprs', '')))
