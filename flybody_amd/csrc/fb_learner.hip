@@ -154,7 +154,7 @@ extern "C" int fbl_td_loss(const float* q_t_logits, const float* bias_t, const f
 // online mean / stddev and the row's contribution to every batch sum (per-dimension KLs + 12 scalars); the workgroup's rows are
 // summed in LDS and added to the accumulator block with one atomic per slot.  Launch 2 (k_mpo_fin, one wavefront): batch means,
 // dual gradients, loss value, statistics -- and the accumulator block is zero again for the next step.
-enum { WS_LSE = 0, WS_WTQ, WS_KLNP, WS_LSEP, WS_PWTP, WS_KLNPP, WS_LPM, WS_LPS, WS_QMIN, WS_QMAX, WS_SMIN, WS_SMAX, WS_NSCALAR = 16 };
+enum { WS_LSE = 0, WS_ENT, WS_KLNP, WS_LSEP, WS_PENT, WS_KLNPP, WS_LPM, WS_LPS, WS_QMIN, WS_QMAX, WS_SMIN, WS_SMAX, WS_CMAX, WS_NSCALAR = 16 };
 #define MPO_ROWS 8
 
 __global__ void __launch_bounds__(WAVE*MPO_ROWS) k_mpo(fbl_mpo_args a) {
@@ -174,17 +174,20 @@ __global__ void __launch_bounds__(WAVE*MPO_ROWS) k_mpo(fbl_mpo_args a) {
 #pragma unroll
     for (int n = 0; n < MAXN; n++) areg[n] = (n < N && vd) ? a.actions[((size_t)n*B + b)*D + d] : 0.f;
     // E-step weights over the N samples: lane n holds sample n
+    // The row maximum is taken off BEFORE the division by T: (q - max) / T carries the rounding of one subtraction, q / T - max / T
+    // loses |q / T| ulps (Q ~ 150 under a temperature of 0.05: 2e-4 on every weight).  The batch sums are those of the SMALL quantities:
+    // lse = log(sum exp((q - max) / T) / N) <= 0 and ent = lse - sum w (q - max) / T, so that the temperature loss is
+    // T (eps + mean lse) + mean max and its gradient sigmoid (eps + mean ent) -- not differences of batch means of size |q / T|.
     float qn = vn ? a.q[(size_t)d*B + b] : NEG;
-    float tq = vn ? qn/T : NEG;
-    float mx = wmax(tq);
-    float e = vn ? expf(tq - mx) : 0.f;
+    float qmin = wmin(vn ? qn : INFINITY), qmax = wmax(qn);
+    float tq = vn ? (qn - qmax)/T : NEG;
+    float e = vn ? expf(tq) : 0.f;
     float s = wsum(e);
     float w = e/s;
-    float lse = mx + logf(s);
+    float lse = logf(s/(float)N);
     float klnp = wsum(vn ? w*logf((float)N*w + 1e-8f) : 0.f);
-    float wtq = wsum(vn ? w*tq : 0.f);
-    float qmin = wmin(vn ? qn : INFINITY), qmax = wmax(vn ? qn : NEG);
-    float W = w, lsep = 0.f, klnpp = 0.f, pwtp = 0.f;
+    float ent = lse - wsum(vn ? w*tq : 0.f);
+    float W = w, lsep = 0.f, klnpp = 0.f, pent = 0.f, cmax = 0.f;
     if (a.action_penalization) {
       const float pT = softplus_f(fmaxf(a.log_penalty_temperature[0], MIN_LOG)) + FEPS;
       const float sc = (vd && a.pen_scale) ? a.pen_scale[d] : 2.f, of = (vd && a.pen_offset) ? a.pen_offset[d] : -1.f;     // defaults: real == a
@@ -197,14 +200,14 @@ __global__ void __launch_bounds__(WAVE*MPO_ROWS) k_mpo(fbl_mpo_args a) {
           cn = d == n ? -sqrtf(c2) : cn;
         }
       }
-      float tp = vn ? cn/pT : NEG;
-      float mp = wmax(tp);
-      float ep = vn ? expf(tp - mp) : 0.f;
+      cmax = wmax(cn);
+      float tp = vn ? (cn - cmax)/pT : NEG;
+      float ep = vn ? expf(tp) : 0.f;
       float sp = wsum(ep);
       float pw = ep/sp;
-      lsep = mp + logf(sp);
+      lsep = logf(sp/(float)N);
       klnpp = wsum(vn ? pw*logf((float)N*pw + 1e-8f) : 0.f);
-      pwtp = wsum(vn ? pw*tp : 0.f);
+      pent = lsep - wsum(vn ? pw*tp : 0.f);
       W = w + pw;
     }
     // M-step: decoupled cross-entropies (fixed-stddev mean update, fixed-mean stddev update); lane-local sums over the samples,
@@ -226,15 +229,21 @@ __global__ void __launch_bounds__(WAVE*MPO_ROWS) k_mpo(fbl_mpo_args a) {
     const float invB = 1.f/(float)B;
     if (vd) {
       a.d_online_mean[bd] = (-gm*its*its + am*(om - tm)*its*its)*invB;
-      a.d_online_std[bd] = (-gs + as*(ios - ts*ts*ios*ios*ios))*invB;
+      // KL(target || target mean, online std) with r = (ts - os) / os (exact numerator): ts / os = 1 + r, so
+      //   log(os/ts) + ts^2 / (2 os^2) - 1/2 = (r - log1p(r)) + r^2 / 2,   d KL / d os = -r (2 + r) / os.
+      // The textbook form is the difference of two O(0.5) terms and keeps no digit at the constraint epsilon_stddev = 1e-7 (|r| ~ 3e-4,
+      // KL ~ 1e-7); r - log1p(r) = r^2 (1/2 - r/3 + r^2/4 - ...) still cancels for small r, so below 1/32 it is the series (truncation 5e-15).
+      const float r = (ts - os)*ios;
+      const float ser = r*r*(0.5f + r*(-0.33333334f + r*(0.25f + r*(-0.2f + r*(0.16666667f + r*(-0.14285715f + r*(0.125f + r*(-0.11111111f + r*0.1f))))))));
+      a.d_online_std[bd] = (-gs - as*ios*r*(2.f + r))*invB;
       klm = (tm - om)*(tm - om)*0.5f*its*its;                                         // KL(target || online mean, target std)
-      kls = logf(os*its) + ts*ts*0.5f*ios*ios - 0.5f;                                 // KL(target || target mean, online std)
+      kls = 0.5f*r*r + (fabsf(r) < 0.03125f ? ser : r - log1pf(r));
     }
     float smin = wmin(vd ? os : INFINITY), smax = wmax(vd ? os : NEG);
     float v = 0.f;
-    v = d == WS_LSE ? lse : v; v = d == WS_WTQ ? wtq : v; v = d == WS_KLNP ? klnp : v; v = d == WS_LSEP ? lsep : v; v = d == WS_PWTP ? pwtp : v;
+    v = d == WS_LSE ? lse : v; v = d == WS_ENT ? ent : v; v = d == WS_KLNP ? klnp : v; v = d == WS_LSEP ? lsep : v; v = d == WS_PENT ? pent : v;
     v = d == WS_KLNPP ? klnpp : v; v = d == WS_LPM ? lpm : v; v = d == WS_LPS ? lps : v; v = d == WS_QMIN ? qmin : v; v = d == WS_QMAX ? qmax : v;
-    v = d == WS_SMIN ? smin : v; v = d == WS_SMAX ? smax : v;
+    v = d == WS_SMIN ? smin : v; v = d == WS_SMAX ? smax : v; v = d == WS_CMAX ? cmax : v;
     scal = v;
   }
   sA[wv][0][d] = klm; sA[wv][1][d] = kls; sA[wv][2][d] = scal;
@@ -245,11 +254,11 @@ __global__ void __launch_bounds__(WAVE*MPO_ROWS) k_mpo(fbl_mpo_args a) {
   for (int w = 0; w < MPO_ROWS; w++) { klm += sA[w][0][d]; kls += sA[w][1][d]; scal += sA[w][2][d]; }
   float* acc = a.workspace;                                     // [2 D + WS_NSCALAR] sums over the batch
   if (vd) { atomicAdd(acc + d, klm); atomicAdd(acc + D + d, kls); }
-  if (d <= WS_SMAX) atomicAdd(acc + 2*D + d, scal);
+  if (d <= WS_CMAX) atomicAdd(acc + 2*D + d, scal);
 }
 
 __global__ void __launch_bounds__(WAVE) k_mpo_fin(fbl_mpo_args a) {
-  const int d = threadIdx.x, N = a.N, B = a.B, D = a.D;
+  const int d = threadIdx.x, B = a.B, D = a.D;
   const bool vd = d < D;
   const float invB = 1.f/(float)B;
   float* acc = a.workspace;
@@ -268,20 +277,19 @@ __global__ void __launch_bounds__(WAVE) k_mpo_fin(fbl_mpo_args a) {
   float loss_alpha = wsum(vd ? am*(a.epsilon_mean - km) + as*(a.epsilon_stddev - ks) : 0.f);
   float kl_mean_rel = wsum(vd ? km : 0.f)/((float)D*a.epsilon_mean), kl_std_rel = wsum(vd ? ks : 0.f)/((float)D*a.epsilon_stddev);
   float am_mean = wsum(am)/(float)D, as_mean = wsum(as)/(float)D;
-  float v_lse = rl(sc, WS_LSE), v_wtq = rl(sc, WS_WTQ), v_klnp = rl(sc, WS_KLNP), v_lsep = rl(sc, WS_LSEP), v_pwtp = rl(sc, WS_PWTP), v_klnpp = rl(sc, WS_KLNPP);
-  float v_lpm = rl(sc, WS_LPM), v_lps = rl(sc, WS_LPS), v_qmin = rl(sc, WS_QMIN), v_qmax = rl(sc, WS_QMAX), v_smin = rl(sc, WS_SMIN), v_smax = rl(sc, WS_SMAX);
+  float v_lse = rl(sc, WS_LSE), v_ent = rl(sc, WS_ENT), v_klnp = rl(sc, WS_KLNP), v_lsep = rl(sc, WS_LSEP), v_pent = rl(sc, WS_PENT), v_klnpp = rl(sc, WS_KLNPP);
+  float v_lpm = rl(sc, WS_LPM), v_lps = rl(sc, WS_LPS), v_qmin = rl(sc, WS_QMIN), v_qmax = rl(sc, WS_QMAX), v_smin = rl(sc, WS_SMIN), v_smax = rl(sc, WS_SMAX), v_cmax = rl(sc, WS_CMAX);
   if (d == 0) {
-    const float logN = logf((float)N);
     float lt = fmaxf(a.log_temperature[0], MIN_LOG); a.log_temperature[0] = lt;
     float T = softplus_f(lt) + FEPS;
-    float loss_T = T*(a.epsilon + v_lse - logN);
-    a.d_log_temperature[0] = sigmoid_f(lt)*(a.epsilon + v_lse - logN - v_wtq);
+    float loss_T = T*(a.epsilon + v_lse) + v_qmax;                 // v_lse = mean log(sum exp((q - max) / T) / N), v_ent = mean (that - sum w (q - max) / T) (k_mpo)
+    a.d_log_temperature[0] = sigmoid_f(lt)*(a.epsilon + v_ent);
     float pen_rel = 0.f;
     if (a.action_penalization) {
       float lp = fmaxf(a.log_penalty_temperature[0], MIN_LOG); a.log_penalty_temperature[0] = lp;
       float pT = softplus_f(lp) + FEPS;
-      loss_T += pT*(a.epsilon_penalty + v_lsep - logN);
-      a.d_log_penalty_temperature[0] = sigmoid_f(lp)*(a.epsilon_penalty + v_lsep - logN - v_pwtp);
+      loss_T += pT*(a.epsilon_penalty + v_lsep) + v_cmax;
+      a.d_log_penalty_temperature[0] = sigmoid_f(lp)*(a.epsilon_penalty + v_pent);
       pen_rel = v_klnpp/a.epsilon_penalty;
     } else if (a.d_log_penalty_temperature) a.d_log_penalty_temperature[0] = 0.f;
     float* st = a.stats;
@@ -517,6 +525,12 @@ extern "C" int fbl_gather_flat(const float* const* src, const int64_t* end, int 
   AdamSegs sg; sg.nseg = 1;
   for (int q = 0; q < 8; q++) sg.end[q] = total;
   if (norms && make_segs(sg, total, nseg, seg_end, nullptr, nullptr, nullptr)) return lfail("fbl_gather_flat: bad segments");
+  // a chunk inside one tensor is attributed to the Adam segment of its first element: a segment may only end where a tensor ends
+  if (norms)
+    for (int s = 0, k = 0; s < nseg; s++) {
+      while (k < ntensor && end[k] < seg_end[s]) k++;
+      if (k == ntensor || end[k] != seg_end[s]) return lfail("fbl_gather_flat: every segment end must be a tensor end");
+    }
   const int blocks = (int)((total + FLAT_CHUNK - 1)/FLAT_CHUNK);
   hipLaunchKernelGGL(k_gather_flat, dim3(blocks), dim3(256), 0, (hipStream_t)stream, f, flat, total, sg, norms, step);
   LCHK(hipGetLastError());
@@ -1181,7 +1195,7 @@ extern "C" int fbl_gemm_longk(const float* a, int64_t lda, const float* w0, int6
   return 0;
 }
 
-// Gaussian head backward when the head ran through fbl_sgemm_pair (its pre-activation was never stored): sigmoid(z) = 1 - exp(-softplus(z)),
+// Gaussian head backward when the head ran through fbl_sgemm_pair (its pre-activation was never stored): sigmoid(z) = -expm1(-softplus(z)),
 // softplus(z) = (std - min_scale) / mul.  dzs = dstd sigmoid mul; column sums of dmean and dzs by atomics (zero-initialised outputs).
 __global__ void __launch_bounds__(256) k_gauss_head_bwd_std(const float* __restrict__ dmean, const float* __restrict__ dstd, const float* __restrict__ std_,
                                                             float mul, float min_scale, int M, int D, float* __restrict__ dzs, float* __restrict__ dbm,
@@ -1198,7 +1212,7 @@ __global__ void __launch_bounds__(256) k_gauss_head_bwd_std(const float* __restr
   }
 #pragma unroll
   for (int j = 0; j < GH_ROWS; j++) {
-    float g = ds[j]*(1.f - expf(-(sd[j] - min_scale)/mul))*mul;
+    float g = ds[j]*(-expm1f(-(sd[j] - min_scale)/mul))*mul;      // (1 - exp(-s) loses the low bits of a small sigmoid)
     if (r0 + j < M) dzs[(size_t)(r0 + j)*D + c] = g;
     as += g; am += dm[j];
   }

@@ -18,8 +18,15 @@ _MIN_LOG = -18.0
 
 
 def _normal_kl(m0, s0, m1, s1):
-    """KL(N(m0,s0) || N(m1,s1)) per dimension."""
-    return torch.log(s1 / s0) + (s0 * s0 + (m0 - m1) ** 2) / (2.0 * s1 * s1) - 0.5
+    """KL(N(m0,s0) || N(m1,s1)) per dimension, as (r - log1p(r)) + r^2 / 2 + (m0 - m1)^2 / (2 s1^2) with r = (s0 - s1) / s1.
+
+    The textbook form log(s1/s0) + s0^2 / (2 s1^2) - 0.5 is the difference of two O(0.5) terms: at the stddev constraint
+    epsilon_stddev = 1e-7 (s1 within ~3e-4 of s0, KL ~ 1e-7) float32 keeps none of its digits.  With s0 / s1 = 1 + r it equals the
+    expression above; r - log1p(r) = r^2 (1/2 - r/3 + r^2/4 - ...) still cancels for small r and is summed as that series below
+    |r| = 1/32 (truncation 5e-15 relative: good for float64 too).  fbl_mpo_loss evaluates the same text."""
+    r = (s0 - s1) / s1
+    series = r * r * (0.5 + r * (-1 / 3 + r * (0.25 + r * (-0.2 + r * (1 / 6 + r * (-1 / 7 + r * (0.125 + r * (-1 / 9 + r * 0.1))))))))
+    return torch.where(r.abs() < 0.03125, series, r - torch.log1p(r)) + 0.5 * r * r + (m0 - m1) ** 2 / (2.0 * s1 * s1)
 
 
 def _normal_logprob(x, m, s):
@@ -27,10 +34,15 @@ def _normal_logprob(x, m, s):
 
 
 def _weights_and_temperature_loss(q, epsilon, temperature):
-    tempered = q.detach() / temperature
+    # temperature * (epsilon + mean logsumexp(q / T) - log N), with the maximum over the samples taken off BEFORE the division:
+    # (q - max) / T has the rounding of one subtraction where q / T - max / T loses |q / T| ulps, and T * (max / T) = max is a constant
+    # of the loss, so neither the value nor the gradient wrt T is a difference of numbers of size |q / T| (fbl_mpo_loss: the same text)
+    q = q.detach()
+    qmax = q.max(dim=0).values
+    tempered = (q - qmax) / temperature
     weights = F.softmax(tempered, dim=0).detach()
-    lse = torch.logsumexp(tempered, dim=0)
-    loss = temperature * (epsilon + lse.mean() - math.log(q.shape[0]))
+    lse = torch.log(torch.exp(tempered).mean(dim=0))              # logsumexp(q / T) - max / T - log N  (<= 0)
+    loss = temperature * (epsilon + lse.mean()) + qmax.mean()
     return weights, loss
 
 

@@ -55,6 +55,12 @@ typedef struct fbl_mpo_args {
   float* workspace;                      /* [fbl_mpo_workspace_floats] batch-sum accumulators: ZERO before the first call, left zero by
                                             every call (two launches: rows -> sums; one wavefront -> duals, loss, statistics, clean-up) */
 } fbl_mpo_args;
+/* Float32 forms (the same text as dmpo/losses.py; tests/test_gpu_learner_fp64.py checks them against float64):
+ *   stddev KL   with r = (ts - os) / os:  KL = (r - log1p(r)) + r^2 / 2  [= log(os/ts) + ts^2 / (2 os^2) - 1/2, which keeps no digit at
+ *               epsilon_stddev = 1e-7], r - log1p(r) as the series r^2 (1/2 - r/3 + ...) below |r| = 1/32;  d KL / d os = -r (2 + r) / os.
+ *   E-step      weights softmax((q - max_n q) / T): the maximum is taken off before the division.  Temperature loss
+ *               T (eps + mean_b log(mean_n exp((q - max) / T))) + mean_b max, its gradient sigmoid (eps + mean_b [that logarithm - sum_n w
+ *               (q - max) / T]): sums of small numbers, never differences of numbers of size |q / T|.  The penalty branch likewise. */
 int fbl_mpo_loss(const fbl_mpo_args* a, void* stream);
 size_t fbl_mpo_workspace_floats(int B, int D);
 
@@ -71,7 +77,7 @@ int fbl_adam(float* param, const float* grad, float* exp_avg, float* exp_avg_sq,
 
 /* Lay `ntensor` gradient tensors (src[k], device pointers in HOST arrays; NULL = zeros) out in the flat buffer: tensor k occupies
  * flat[end[k-1] .. end[k]).  norms != NULL: also accumulate the squared norm of every Adam segment (seg_end as in fbl_adam; segment
- * boundaries must be tensor boundaries) into the optimizer's `norms` / `step` pair, exactly as fbl_adam's own norm pass would --
+ * ends must be tensor ends: anything else is refused) into the optimizer's `norms` / `step` pair, exactly as fbl_adam's own norm pass would --
  * call it ONCE per update, then fbl_adam with norms_ready = 1.  ntensor <= 96.  One launch. */
 int fbl_gather_flat(const float* const* src, const int64_t* end, int ntensor, float* flat, int nseg, const int64_t* seg_end,
                     float* norms, int32_t* step, void* stream);

@@ -41,6 +41,20 @@ def test_learner_library_exports_header_symbols():
     assert fused.source_hash().encode() in lib.fbl_version()          # the binary names the sources it was built from
 
 
+def test_learner_gather_refuses_a_segment_end_inside_a_tensor():
+    """fbl_gather_flat attributes a chunk that lies inside one tensor to the Adam segment of the chunk's first element, which is right only
+    when every segment ends where a tensor ends: any other layout is an error, decided on the host before anything is launched (so no GPU is
+    needed, and the pointers below are never read)."""
+    from flybody_amd.dmpo import fused
+    L = fused.lib()
+    ends = (C.c_int64*3)(1000, 3000, 3005); src = (C.c_void_p*3)(64, 64, None)
+    fake = C.c_void_p(64)
+    call = lambda seg: L.fbl_gather_flat(src, ends, 3, fake, len(seg), (C.c_int64*len(seg))(*seg), fake, fake, None)
+    for seg in ([2999, 3005], [1000, 3001, 3005], [1, 3005]):
+        assert call(seg) != 0 and b'segment end' in L.fbl_last_error(), seg
+    assert call([1000, 3004]) != 0 and b'bad segments' in L.fbl_last_error()          # (the last end must be the total, as before)
+
+
 def test_model_load_and_argument_validation(walk_arrays):
     from flybody_amd import engine
     M = engine.Model(walk_arrays)
