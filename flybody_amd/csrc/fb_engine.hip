@@ -39,7 +39,7 @@ struct fb_model {
   std::map<std::string, const BlobEntry*> idx;
   // host-side derived tables
   int nq, nv, nbody, njnt, ngeom, nsite, nu, na, ntendon, npair, nM, nsubstep, nobsjnt, napp, nforce, ntouch;
-  int task_id;                           // 0 walk_imitation, 1 flight_imitation, 2 walk_on_ball
+  int task_id;                           // FB_TASK_* (fb_types.hpp)
   std::vector<int> body_nsub, body_depth, body_chlen, body_chain, body_common, dof_depth, dof_ndesc, lvl_dof, lvl_start, adh_act;
   std::vector<int> wrap_qadr, act_wn, act_wdof, act_lenadr; std::vector<double> act_wcoef;
   std::vector<int> pair_word, pair_body, plane_geoms;
@@ -505,7 +505,7 @@ static int model_load_impl(fb_model* m, size_t n) {
 
 extern "C" void fb_model_destroy(fb_model* m) { delete m; }
 
-// Width of the observation vector (engine.observation_layout; fb_step.hpp writes it): the walker's own observables, 7 per reference frame
+// Width of the observation vector (engine.observation_layout; fb_task.hpp: d_pack_obs writes it): the walker's own observables, 7 per reference frame
 // of the imitation tasks (nref = future_steps + 1 of them) and, for walk_on_ball, the ball's velocity
 static int obs_width(const fb_model* m, int nref, bool ball) {
   return 3 + m->na + 3*m->napp + (ball ? 3 : 0) + 3*m->nforce + 3 + 2*m->nobsjnt + 7*nref + m->ntouch + 3 + 3;
@@ -1297,7 +1297,7 @@ extern "C" int fb_batch_set_reference(fb_batch* b, const double* ref_qpos, const
   int max_steps = (int)floor(time_limit / m->d("opt_control_timestep")[0] + 0.5) + 1;
   int snippet = T - future_steps - 1;
   int episode_steps = max_steps < snippet ? max_steps : snippet;
-  if (m->task_id == 1) {          // flight_imitation.py:101-105
+  if (m->task_id == FB_TASK_FLIGHT_IMITATION) {          // flight_imitation.py:101-105
     int lim = max_steps - 1;
     episode_steps = (T < lim ? T : lim) - (future_steps + 1);
   }
@@ -1320,7 +1320,7 @@ extern "C" int fb_batch_set_reference(fb_batch* b, const double* ref_qpos, const
 extern "C" int fb_batch_set_time_limit(fb_batch* b, double time_limit) {
   if (!b || !(time_limit > 0)) return fail("fb_batch_set_time_limit: bad arguments");
   const fb_model* m = b->m;
-  if (m->task_id != 2) return fail("fb_batch_set_time_limit: only the walk_on_ball task has no reference trajectory");
+  if (m->task_id != FB_TASK_WALK_ON_BALL) return fail("fb_batch_set_time_limit: only the walk_on_ball task has no reference trajectory");
   HIPCHK(hipSetDevice(b->device));
   if (alloc_obs(b, obs_width(m, 0, true))) return -1;
   return with_model(b, [&](auto& M) {
@@ -1354,7 +1354,7 @@ extern "C" int fb_batch_set_walk_dataset(fb_batch* b, const fb_walk_dataset* ds)
     return fail("fb_batch_set_walk_dataset: null argument");
   if (ds->n_traj <= 0 || ds->n_select <= 0 || ds->n_joints < 0 || ds->n_sites < 0) return fail("fb_batch_set_walk_dataset: bad sizes");
   const fb_model* m = b->m;
-  if (m->task_id != 0) return fail("fb_batch_set_walk_dataset: not a walk_imitation model");
+  if (m->task_id != FB_TASK_WALK_IMITATION) return fail("fb_batch_set_walk_dataset: not a walk_imitation model");
   for (int k = 0; k < ds->n_joints; k++) if (ds->joint_ids[k] < 0 || ds->joint_ids[k] >= m->njnt) return fail("fb_batch_set_walk_dataset: joint id out of range");
   for (int k = 0; k < ds->n_sites; k++) if (ds->site_ids[k] < 0 || ds->site_ids[k] >= m->nsite) return fail("fb_batch_set_walk_dataset: site id out of range");
   for (int k = 0; k < ds->n_select; k++) {
@@ -1386,7 +1386,7 @@ extern "C" int fb_batch_set_flight_dataset(fb_batch* b, const fb_flight_dataset*
   if (!b || !ds || !ds->traj_offset || !ds->qpos || !ds->qvel || !ds->select) return fail("fb_batch_set_flight_dataset: null argument");
   if (ds->n_traj <= 0 || ds->n_select <= 0 || ds->future_steps < 0) return fail("fb_batch_set_flight_dataset: bad sizes");
   const fb_model* m = b->m;
-  if (m->task_id != 1) return fail("fb_batch_set_flight_dataset: not a flight_imitation model");
+  if (m->task_id != FB_TASK_FLIGHT_IMITATION) return fail("fb_batch_set_flight_dataset: not a flight_imitation model");
   for (int k = 0; k < ds->n_select; k++) {
     int t = ds->select[k];
     if (t < 0 || t >= ds->n_traj) return fail("fb_batch_set_flight_dataset: selected trajectory out of range");
@@ -1486,7 +1486,7 @@ static int launch(fb_batch* b, int mode, const float* action, const int* ids, in
 // the tables a control step reads are set: a reference (or dataset / time limit) and, with `wbpg`, flight's pattern generator
 static int check_ready(const fb_batch* b, const char* fn, bool wbpg) {
   if (!b->have_ref) return fail(std::string(fn) + ": call fb_batch_set_reference first");
-  if (wbpg && b->m->task_id == 1 && !b->have_wbpg) return fail(std::string(fn) + ": flight task needs fb_batch_set_wbpg first");
+  if (wbpg && b->m->task_id == FB_TASK_FLIGHT_IMITATION && !b->have_wbpg) return fail(std::string(fn) + ": flight task needs fb_batch_set_wbpg first");
   return 0;
 }
 

@@ -153,7 +153,7 @@ def _check(L, rc):
 
 
 def observation_layout(model: 'Model', future_steps: int, ball: bool = False):
-    """({observable: (offset, size, shape)}, width) of the packed observation vector (fb_step.hpp writes it).  The buffer is in
+    """({observable: (offset, size, shape)}, width) of the packed observation vector (fb_task.hpp: d_pack_obs writes it).  The buffer is in
     sorted-key order (tasks/task_utils.py:12); walk_on_ball (ball=True) has no reference observables, its ball's velocity instead."""
     na, napp, nforce, nobsj, ntouch = (model.dim(k) for k in ('na', 'napp', 'nforce', 'nobsjnt', 'ntouch'))
     nf = 0 if ball else future_steps + 1
