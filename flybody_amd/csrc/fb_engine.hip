@@ -580,9 +580,10 @@ __device__ __forceinline__ const DevModel<real>& model_of_env(const DevModel<rea
 // MODELS: the kernels of a grouped batch (k_group_step, k_group_reset; G = the assignment).  The workgroup's LDS tables and the launch-wide
 // quantities (substep count, dimensions, workspace layout) come from element 0 -- the models of a group agree in all of them -- and the
 // model proper is bound once the environment is known: per launch on the per-wave path, per ticket under the substep scheduler.
-template <typename real, bool FORCES = false, bool MODELS = false>
+// LAW: the step kernel with a substep control law (k_step_law; L = the law's coefficients, qpos addresses and output, fb_law.hpp).
+template <typename real, bool FORCES = false, bool MODELS = false, bool LAW = false>
 __device__ __forceinline__ void fly_kernel(const DevModel<real>* Mp, const Batch<real>& B, const float* action, const int* env_ids, int mode, int nsub, int nslot,
-                                           const ForceArgs<real> F = ForceArgs<real>(), const GroupArgs G = GroupArgs()) {
+                                           const ForceArgs<real> F = ForceArgs<real>(), const GroupArgs G = GroupArgs(), const LawArgs<real> L = LawArgs<real>()) {
   // per-wave (per-environment) hot arrays
   constexpr int EPB = LdsCfg<real>::EPB;
   __shared__ real s_pool[EPB][LdsCfg<real>::POOL];          // [factor row | Delassus matrix | solve vector] of each environment
@@ -695,9 +696,11 @@ __device__ __forceinline__ void fly_kernel(const DevModel<real>* Mp, const Batch
 #endif
       const real *qf_ = nullptr, *xf_ = nullptr;
       if constexpr (FORCES) { qf_ = F.qfrc_applied + (size_t)env*M.nv; xf_ = F.xfrc_applied + (size_t)env*6*M.nbody; }
-      const bool was_reset = d_run<real, FORCES>(Me, w, env, mode, nsub, nslot, (int*)nullptr, action ? action + (size_t)env*M.nact : nullptr, obs, B.reward + env,
+      const real* lc_ = nullptr; real* lo_ = nullptr;
+      if constexpr (LAW) { lc_ = L.coef + (L.per_env ? (size_t)env*LAW_NROW*M.nv : (size_t)0); lo_ = L.out + (size_t)env*M.nv; }
+      const bool was_reset = d_run<real, FORCES, LAW>(Me, w, env, mode, nsub, nslot, (int*)nullptr, action ? action + (size_t)env*M.nact : nullptr, obs, B.reward + env,
                                    B.discount + env, B.step_type + env, lane, (round == 0 ? 1 : 0) | (round == nunit - 1 ? 2 : 0) | (tkhalf == 1 ? 4 : 0) | (tkhalf == 2 ? 8 : 0) | (late ? 16 : 0),
-                                   -1, qf_, xf_);
+                                   -1, qf_, xf_, lc_, L.qadr, lo_);
       if constexpr (MODELS) { if (bad_id && lane == 0) { atomicOr(w.istate() + IS_WARN, (int)WARN_MODEL_ID); atomicOr(w.istate() + IS_WARN_EVER, (int)WARN_MODEL_ID); } }
 #ifndef FB_EMULATE
       // Release.  What the next holder of this environment (a wave of the SAME XCD: environments are bound to XCDs) must see is this
@@ -745,8 +748,10 @@ __device__ __forceinline__ void fly_kernel(const DevModel<real>* Mp, const Batch
   } else if (lane == 0) { w.istate()[IS_PRIO] = 0; if (mode == MODE_STEP || mode == MODE_RESET) w.istate()[IS_WARN] = 0; }
   const real *qf_ = nullptr, *xf_ = nullptr;
   if constexpr (FORCES) { qf_ = F.qfrc_applied + (size_t)env*M.nv; xf_ = F.xfrc_applied + (size_t)env*6*M.nbody; }
-  d_run<real, FORCES>(Me, w, env, only >= 0 ? (int)MODE_STEP : mode, nsub, nslot, only >= 0 ? (int*)nullptr : B.sched, action ? action + (size_t)env*M.nact : nullptr, obs, B.reward + env,
-        B.discount + env, B.step_type + env, lane, -1, only, qf_, xf_);
+  const real* lc_ = nullptr; real* lo_ = nullptr;
+  if constexpr (LAW) { lc_ = L.coef + (L.per_env ? (size_t)env*LAW_NROW*M.nv : (size_t)0); lo_ = L.out + (size_t)env*M.nv; }
+  d_run<real, FORCES, LAW>(Me, w, env, only >= 0 ? (int)MODE_STEP : mode, nsub, nslot, only >= 0 ? (int*)nullptr : B.sched, action ? action + (size_t)env*M.nact : nullptr, obs, B.reward + env,
+        B.discount + env, B.step_type + env, lane, -1, only, qf_, xf_, lc_, L.qadr, lo_);
   if constexpr (MODELS) { if (bad_id && lane == 0) { atomicOr(w.istate() + IS_WARN, (int)WARN_MODEL_ID); atomicOr(w.istate() + IS_WARN_EVER, (int)WARN_MODEL_ID); } }
   if (only >= 0) {
     SYNC();
@@ -785,6 +790,34 @@ __global__ void __launch_bounds__(FB_WAVE*LdsCfg<real>::EPB, LdsCfg<real>::WAVES
 template <typename real>
 __global__ void __launch_bounds__(FB_WAVE*LdsCfg<real>::EPB, LdsCfg<real>::WAVES_PER_SIMD) k_step_forces(const DevModel<real>* Mp, Batch<real> B, const float* action, const int* env_ids, int mode, int nsub, int nslot, ForceArgs<real> F) {
   fly_kernel<real, true>(Mp, B, action, env_ids, mode, nsub, nslot, F);
+}
+
+// The step kernel with a substep control law (fb_law.hpp): the forces kernel with the law stage compiled in as well -- setting a law allocates
+// the force arrays -- under k_fly's launch bounds and on its LDS layout, ticket scheduler included.  The law is one more kernel argument.
+template <typename real>
+__global__ void __launch_bounds__(FB_WAVE*LdsCfg<real>::EPB, LdsCfg<real>::WAVES_PER_SIMD) k_step_law(const DevModel<real>* Mp, Batch<real> B, const float* action, const int* env_ids, int mode, int nsub, int nslot, ForceArgs<real> F, LawArgs<real> L) {
+  fly_kernel<real, true, false, true>(Mp, B, action, env_ids, mode, nsub, nslot, F, GroupArgs(), L);
+}
+
+// Ends episodes from the device (fb_batch_end_episode): one thread per environment.  Where the mask is set and the environment's last
+// step was MID, the step becomes LAST with the caller's discount and the next control step auto-resets the environment, exactly as after a
+// LAST the step kernel decided itself.  FIRST and already-LAST environments are left alone.
+__global__ void k_end_episode(int* iarena, unsigned nint, unsigned istate, int* step_type, float* discount, const uint8_t* mask, const float* disc, int n) {
+  const int e = blockIdx.x*FB_WAVE + threadIdx.x;
+  if (e >= n || !mask[e]) return;
+  int* is = iarena + (size_t)e*nint + istate;
+  if (is[IS_STEP_TYPE] != 1) return;
+  is[IS_STEP_TYPE] = 2; is[IS_RESET_NEXT] = 1;
+  step_type[e] = 2; discount[e] = disc ? disc[e] : 0.0f;
+}
+
+// Zeroes rows [words] of 32-bit words each: row ids[k] of `base`, one workgroup per listed row (fb_batch_reset of some environments
+// clears their FB_QFRC_LAW rows; the ids are on the device already).
+__global__ void k_zero_rows(uint32_t* base, const int* ids, int n, unsigned words) {
+  const int k = blockIdx.x;
+  if (k >= n) return;
+  uint32_t* row = base + (size_t)ids[k]*words;
+  for (unsigned i = threadIdx.x; i < words; i += FB_WAVE) row[i] = 0u;
 }
 
 // The kernels of a grouped batch (fb_batch_create_group): the same device code with the per-environment model compiled in, under k_fly's
@@ -936,6 +969,10 @@ struct fb_batch {
   double* inv_qfrc = nullptr; double* inv_cforce = nullptr;      // fb_batch_inverse results (FB_QFRC_INVERSE / FB_CONTACT_FORCE), allocated on the first call
   void *qfrc_applied = nullptr, *xfrc_applied = nullptr;         // applied forces (FB_QFRC_APPLIED / FB_XFRC_APPLIED) at the batch's precision: both allocated by the first
                                                                  // fb_batch_set / fb_batch_device_ptr of either, freed by fb_batch_clear_forces; allocated = k_step_forces steps the batch
+  // substep control law (fb_batch_set_control_law, fb_law.hpp): coefficients [law_rows][5][nv] (FB_CONTROL_LAW) and output [n_env][nv] (FB_QFRC_LAW) at the
+  // batch's precision, qpos addresses [nv]; set = k_step_law steps the batch.  law_owns_forces: the law allocated the force arrays itself (no caller
+  // touched them), so clearing the law frees them too and the batch is back on k_fly
+  void *law_coef = nullptr, *law_out = nullptr; int* law_qadr = nullptr; int law_rows = 0; bool law_owns_forces = false;
 };
 
 template <typename real, typename T, typename P>
@@ -1231,7 +1268,10 @@ static int batch_create_impl(fb_batch* b) {
           int nbg = 0, nbgf = 0;
           HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nbg, (k_group_step<real, false>), FB_WAVE*LdsCfg<real>::EPB, 0));
           HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nbgf, (k_group_step<real, true>), FB_WAVE*LdsCfg<real>::EPB, 0));
-          b->slots = std::min(std::min(nb, nbf), std::min(nbg, nbgf))*prop.multiProcessorCount*LdsCfg<real>::EPB;
+          // ... and the kernel of a control law (k_step_law: tests/test_law_resources.py)
+          int nbl = 0;
+          HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nbl, k_step_law<real>, FB_WAVE*LdsCfg<real>::EPB, 0));
+          b->slots = std::min(std::min(std::min(nb, nbf), std::min(nbg, nbgf)), nbl)*prop.multiProcessorCount*LdsCfg<real>::EPB;
           return 0; })) return -1;
     unsigned* dmask; unsigned hmask = 0;
     HIPCHK(hipMalloc((void**)&dmask, sizeof(unsigned))); HIPCHK(hipMemset(dmask, 0, sizeof(unsigned)));
@@ -1277,7 +1317,7 @@ extern "C" void fb_batch_destroy(fb_batch* b) {
   if (!b) return;
   (void)hipSetDevice(b->device);
   for (void* p : b->allocs) (void)hipFree(p);
-  void* frees_[] = {b->rarena, b->iarena, b->obs, b->reward, b->discount, b->step_type, b->d_ids, b->sched, b->cost, b->order, b->ref_qpos, b->ref_qvel, b->dM, b->tick, b->done, b->sched_err, b->park, b->probe_word, b->torder, b->ik_err, b->ik_steps, b->ik_buf, b->inv_qfrc, b->inv_cforce, b->qfrc_applied, b->xfrc_applied, b->env_model};
+  void* frees_[] = {b->rarena, b->iarena, b->obs, b->reward, b->discount, b->step_type, b->d_ids, b->sched, b->cost, b->order, b->ref_qpos, b->ref_qvel, b->dM, b->tick, b->done, b->sched_err, b->park, b->probe_word, b->torder, b->ik_err, b->ik_steps, b->ik_buf, b->inv_qfrc, b->inv_cforce, b->qfrc_applied, b->xfrc_applied, b->env_model, b->law_coef, b->law_out, b->law_qadr};
   for (void* p : frees_) (void)hipFree(p);
 
   if (b->ev0) (void)hipEventDestroy(b->ev0);
@@ -1308,7 +1348,7 @@ extern "C" int fb_batch_set_reference(fb_batch* b, const double* ref_qpos, const
     HIPCHK(hipMalloc(&b->ref_qvel, v.size()*sizeof(real)));
     HIPCHK(hipMemcpy(b->ref_qpos, q.data(), q.size()*sizeof(real), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(b->ref_qvel, v.data(), v.size()*sizeof(real), hipMemcpyHostToDevice));
-    if (alloc_obs(b, obs_width(m, future_steps + 1, false))) return -1;
+    if (alloc_obs(b, obs_width(m, m->task_id == FB_TASK_TEMPLATE ? 0 : future_steps + 1, false))) return -1;      // (template_task: the reference is the start pose only, no reference observables)
     M.ref_qpos = (const real*)b->ref_qpos; M.ref_qvel = (const real*)b->ref_qvel; M.T = T;
     M.future_steps = future_steps; M.episode_steps = episode_steps; M.nobs = b->nobs;
     M.terminal_com_dist = (real)terminal_com_dist; M.time_limit = (real)time_limit;
@@ -1412,7 +1452,7 @@ extern "C" int fb_batch_set_flight_dataset(fb_batch* b, const fb_flight_dataset*
   });
 }
 
-// the k_fly / k_fly_reset / k_step_forces launch of launch()
+// the k_fly / k_fly_reset / k_step_forces / k_step_law launch of launch()
 template <typename real>
 static void launch_fly(fb_batch* b, int mode, const float* action, const int* ids, int n, int nsub, hipStream_t st, bool tickets, const int* tord) {
   constexpr int EPB = LdsCfg<real>::EPB;
@@ -1428,6 +1468,11 @@ static void launch_fly(fb_batch* b, int mode, const float* action, const int* id
     else hipLaunchKernelGGL((k_group_step<real, false>), dim3((n + EPB - 1)/EPB), dim3(FB_WAVE*EPB), 0, st, dM, B, action, ids, mode, nsub, n, F, G);
   }
   else if (mode == MODE_RESET) hipLaunchKernelGGL((k_fly_reset<real>), dim3((n + EPB - 1)/EPB), dim3(FB_WAVE*EPB), 0, st, dM, B, ids, nsub, n);
+  else if (b->law_coef) {
+    const ForceArgs<real> F = {(const real*)b->qfrc_applied, (const real*)b->xfrc_applied};
+    const LawArgs<real> L = {(const real*)b->law_coef, b->law_qadr, (real*)b->law_out, b->law_rows > 1 || b->n_env == 1 ? 1 : 0};
+    hipLaunchKernelGGL((k_step_law<real>), dim3((n + EPB - 1)/EPB), dim3(FB_WAVE*EPB), 0, st, dM, B, action, ids, mode, nsub, n, F, L);
+  }
   else if (b->qfrc_applied) {
     const ForceArgs<real> F = {(const real*)b->qfrc_applied, (const real*)b->xfrc_applied};
     hipLaunchKernelGGL((k_step_forces<real>), dim3((n + EPB - 1)/EPB), dim3(FB_WAVE*EPB), 0, st, dM, B, action, ids, mode, nsub, n, F);
@@ -1498,8 +1543,12 @@ extern "C" int fb_batch_reset(fb_batch* b, const int32_t* env_ids, int n, void* 
     if (n <= 0 || n > b->n_env) return fail("fb_batch_reset: bad n");
     for (int k = 0; k < n; k++) if (env_ids[k] < 0 || env_ids[k] >= b->n_env) return fail("fb_batch_reset: env id out of range");
     HIPCHK(hipMemcpyAsync(b->d_ids, env_ids, n*sizeof(int), hipMemcpyHostToDevice, (hipStream_t)stream));
+    if (b->law_out) {                                   // a reset skips the law: FB_QFRC_LAW of the reset environments is zero (k_fly_reset knows no law)
+      hipLaunchKernelGGL(k_zero_rows, dim3(n), dim3(FB_WAVE), 0, (hipStream_t)stream, (uint32_t*)b->law_out, (const int*)b->d_ids, n, (unsigned)(b->m->nv*real_size(b)/4));
+    }
     return launch(b, MODE_RESET, nullptr, b->d_ids, n, 0, stream);
   }
+  if (b->law_out) HIPCHK(hipMemsetAsync(b->law_out, 0, (size_t)b->n_env*b->m->nv*real_size(b), (hipStream_t)stream));
   return launch(b, MODE_RESET, nullptr, nullptr, b->n_env, 0, stream);
 }
 
@@ -1553,6 +1602,7 @@ extern "C" int fb_batch_stage(fb_batch* b, int stage_word, const float* action, 
   if (!b || stage_word < 0) return fail("fb_batch_stage: bad arguments");
   if (check_ready(b, "fb_batch_stage", false)) return -1;
   if (b->n_models() > 1) return fail("fb_batch_stage: single-stage profiling runs k_fly, which steps one model; this batch is a group of " + std::to_string(b->n_models()) + " models (fb_batch_create_group)");
+  if (b->law_coef) return fail("fb_batch_stage: single-stage profiling runs k_fly, which knows no control law; call fb_batch_set_control_law(batch, NULL) first");
   if (b->qfrc_applied) return fail("fb_batch_stage: single-stage profiling runs k_fly, which knows no applied forces; call fb_batch_clear_forces first");
   HIPCHK(hipSetDevice(b->device));
   const size_t pool = with_model(b, [](auto& M) { return sizeof(M.timestep)*LdsCfg<decltype(M.timestep)>::POOL; });
@@ -1567,6 +1617,7 @@ extern "C" int fb_batch_ik(fb_batch* b, const fb_ik_config* cfg, const double* t
   if (!b || !cfg || !target_xpos) return fail("fb_batch_ik: null argument");
   if (b->precision != 64) return fail("fb_batch_ik: inverse kinematics needs an FP64 batch (precision 64)");
   if (b->n_models() > 1) return fail("fb_batch_ik: per-model inverse kinematics is not supported: this batch is a group of " + std::to_string(b->n_models()) + " models (fb_batch_create_group)");
+  if (b->law_coef) return fail("fb_batch_ik: the IK kernel knows no control law, and its position-stage outputs would not be the law kernel's; call fb_batch_set_control_law(batch, NULL) first");
   const fb_model* m = b->m;
   const int ns = cfg->n_site, nj = cfg->n_joint, n = b->n_env;
   if (ns < 1 || !cfg->site_ids || !cfg->include) return fail("fb_batch_ik: at least one site (and its include mask) is required");
@@ -1640,6 +1691,7 @@ extern "C" int fb_batch_inverse(fb_batch* b, int flags, void* stream) {
   if (b->precision != 64) return fail("fb_batch_inverse: inverse dynamics needs an FP64 batch (precision 64)");
   if (flags & ~FB_INV_DISCRETE) return fail("fb_batch_inverse: unknown flags");
   if (b->n_models() > 1) return fail("fb_batch_inverse: per-model inverse dynamics is not supported: this batch is a group of " + std::to_string(b->n_models()) + " models (fb_batch_create_group)");
+  if (b->law_coef) return fail("fb_batch_inverse: the inverse knows no control law: qfrc_inverse would count the law's force as external; call fb_batch_set_control_law(batch, NULL) first");
   FB_GUARD_BEGIN
   const int n = b->n_env, nv = b->m->nv;
   HIPCHK(hipSetDevice(b->device));
@@ -1719,6 +1771,8 @@ static int field_desc(fb_batch* b, int field, FieldDesc* f) {
     case FB_QFRC_APPLIED: *f = {REAL_ARRAY, 0, (size_t)m->nv, b->qfrc_applied, no_frc}; break;
     case FB_XFRC_APPLIED: *f = {REAL_ARRAY, 0, (size_t)6*m->nbody, b->xfrc_applied, no_frc}; break;
     case FB_ENV_MODEL: *f = {I32_ARRAY, 0, 1, b->env_model, no_grp}; break;
+    case FB_QFRC_LAW: *f = {REAL_ARRAY, 0, (size_t)m->nv, b->law_out, "fb_batch_get: no control law (fb_batch_set_control_law sets one)"}; break;
+    case FB_CONTROL_LAW: return fail("FB_CONTROL_LAW is [n_rows][5][nv], not one row per environment: read and write it through fb_batch_device_ptr, set it with fb_batch_set_control_law");
     default: return fail("unknown field");
   }
   return 0;
@@ -1743,6 +1797,7 @@ static int alloc_forces(fb_batch* b) {
 
 extern "C" int fb_batch_clear_forces(fb_batch* b) {
   if (!b) return fail("fb_batch_clear_forces: null batch");
+  if (b->law_coef) return fail("fb_batch_clear_forces: a control law is set, and its kernel (k_step_law) reads the force arrays; call fb_batch_set_control_law(batch, NULL) first");
   HIPCHK(hipSetDevice(b->device));
   HIPCHK(hipDeviceSynchronize());                      // (a launch in flight may still read the arrays)
   (void)hipFree(b->qfrc_applied); (void)hipFree(b->xfrc_applied);
@@ -1753,6 +1808,87 @@ extern "C" int fb_batch_clear_forces(fb_batch* b) {
 extern "C" int fb_batch_forces_active(const fb_batch* b) {
   if (!b) return fail("fb_batch_forces_active: null batch");
   return b->qfrc_applied ? 1 : 0;
+}
+
+// ------------------------------------------------------------------ substep control law (fb_law.hpp)
+extern "C" int fb_batch_set_control_law(fb_batch* b, const fb_control_law* law) {
+  if (!b) return fail("fb_batch_set_control_law: null batch");
+  FB_GUARD_BEGIN
+  HIPCHK(hipSetDevice(b->device));
+  if (!law) {
+    HIPCHK(hipDeviceSynchronize());                    // (a launch in flight may still read the law)
+    (void)hipFree(b->law_coef); (void)hipFree(b->law_out); (void)hipFree(b->law_qadr);
+    b->law_coef = b->law_out = nullptr; b->law_qadr = nullptr; b->law_rows = 0;
+    if (b->law_owns_forces) { b->law_owns_forces = false; return fb_batch_clear_forces(b); }
+    return 0;
+  }
+  if (b->n_models() > 1) return fail("fb_batch_set_control_law: a control law in a grouped batch is not supported: this batch is a group of " + std::to_string(b->n_models()) +
+                                     " models (fb_batch_create_group); give every model a batch of its own (fb_batch_create)");
+  const fb_model* m = b->m;
+  const int nv = m->nv, n = b->n_env, nr = law->n_rows;
+  if (nr != 1 && nr != n) return fail("fb_batch_set_control_law: n_rows must be 1 (one law for the batch) or n_env = " + std::to_string(n) + ", got " + std::to_string(nr));
+  const double* rows[LAW_NROW] = {law->bias, law->act_gain, law->pos_gain, law->pos_ref, law->vel_gain};
+  const char* names[LAW_NROW] = {"bias", "act_gain", "pos_gain", "pos_ref", "vel_gain"};
+  // qpos address of every hinge's dof; pos_gain must be zero everywhere else (the free root's and a ball's dofs have no scalar position)
+  const int *djnt = m->i("dof_jntid"), *jt = m->i("jnt_type"), *jqa = m->i("jnt_qposadr");
+  std::vector<int> qadr(nv, 0);
+  for (int i = 0; i < nv; i++) if (jt[djnt[i]] == JNT_HINGE) qadr[i] = jqa[djnt[i]];
+  for (int r = 0; r < LAW_NROW; r++) {
+    if (!rows[r]) continue;
+    for (size_t k = 0; k < (size_t)nr*nv; k++) {
+      if (!std::isfinite(rows[r][k])) return fail(std::string("fb_batch_set_control_law: ") + names[r] + " of dof " + std::to_string(k % nv) + " (row " + std::to_string(k/nv) + ") is not finite");
+      if (r == LAW_POS_GAIN && rows[r][k] != 0 && jt[djnt[k % nv]] != JNT_HINGE)
+        return fail("fb_batch_set_control_law: pos_gain of dof " + std::to_string(k % nv) + " (row " + std::to_string(k/nv) + ") is not zero, but the dof belongs to a " +
+                    (jt[djnt[k % nv]] == JNT_FREE ? "free" : "ball") + " joint, which has no scalar position; position feedback is for hinge dofs only");
+    }
+  }
+  const bool had_forces = b->qfrc_applied != nullptr;
+  if (alloc_forces(b)) return -1;
+  if (!had_forces) b->law_owns_forces = true;
+  HIPCHK(hipDeviceSynchronize());
+  // Everything the new law needs is allocated and filled first and swapped in last: a failure on the way leaves the batch as it was, the
+  // previous law included (a block of another row count is a new block; the old one is freed after the swap).
+  const size_t rs = real_size(b);
+  const bool reuse = b->law_coef && b->law_rows == nr;
+  void *coef = reuse ? b->law_coef : nullptr, *out = b->law_out; int* qa = b->law_qadr;
+  auto undo = [&](const char* why) {
+    if (!reuse) (void)hipFree(coef);
+    if (!b->law_out) (void)hipFree(out);
+    if (!b->law_qadr) (void)hipFree(qa);
+    if (!had_forces && !b->law_coef) { b->law_owns_forces = false; (void)fb_batch_clear_forces(b); }
+    (void)hipGetLastError();
+    return fail(std::string("fb_batch_set_control_law: ") + why);
+  };
+  if (!coef && hipMalloc(&coef, (size_t)nr*LAW_NROW*nv*rs) != hipSuccess) { coef = nullptr; return undo("device allocation failed"); }
+  if (!qa && hipMalloc((void**)&qa, nv*sizeof(int)) != hipSuccess) { qa = nullptr; return undo("device allocation failed"); }
+  if (!out && (hipMalloc(&out, (size_t)n*nv*rs) != hipSuccess || hipMemset(out, 0, (size_t)n*nv*rs) != hipSuccess)) return undo("device allocation failed");
+  if (hipMemcpy(qa, qadr.data(), nv*sizeof(int), hipMemcpyHostToDevice) != hipSuccess) return undo("copy to the device failed");
+  const int rc = with_model(b, [&](auto& M) {
+    std::vector<decltype(M.timestep)> tmp((size_t)nr*LAW_NROW*nv, 0);
+    for (int e = 0; e < nr; e++) for (int r = 0; r < LAW_NROW; r++) if (rows[r])
+      for (int i = 0; i < nv; i++) tmp[((size_t)e*LAW_NROW + r)*nv + i] = (decltype(M.timestep))rows[r][(size_t)e*nv + i];
+    return hipMemcpy(coef, tmp.data(), tmp.size()*sizeof(tmp[0]), hipMemcpyHostToDevice) == hipSuccess ? 0 : -1;
+  });
+  if (rc || hipDeviceSynchronize() != hipSuccess) return undo("copy to the device failed");
+  void* old = reuse ? nullptr : b->law_coef;
+  b->law_coef = coef; b->law_rows = nr; b->law_out = out; b->law_qadr = qa;
+  (void)hipFree(old);
+  return 0;
+  FB_GUARD_END
+}
+
+extern "C" int fb_batch_control_law_active(const fb_batch* b) {
+  if (!b) return fail("fb_batch_control_law_active: null batch");
+  return b->law_coef ? 1 : 0;
+}
+
+extern "C" int fb_batch_end_episode(fb_batch* b, const uint8_t* mask_dev, const float* discount_dev, void* stream) {
+  if (!b || !mask_dev) return fail("fb_batch_end_episode: null argument");
+  HIPCHK(hipSetDevice(b->device));
+  hipLaunchKernelGGL(k_end_episode, dim3((b->n_env + FB_WAVE - 1)/FB_WAVE), dim3(FB_WAVE), 0, (hipStream_t)stream, b->iarena, (unsigned)b->off.nint, (unsigned)b->off.istate,
+                     b->step_type, b->discount, mask_dev, discount_dev, b->n_env);
+  HIPCHK(hipGetLastError());
+  return 0;
 }
 
 // a REAL_ARENA field of every environment, between the arena (the batch's precision) and FP64 rows [n_env][width] on the host
@@ -1833,6 +1969,8 @@ extern "C" int fb_batch_set(fb_batch* b, int field, const void* src, size_t byte
   } else if (f.kind == INT_ARENA) {
     if (bytes != (size_t)n*f.width*sizeof(int)) return fail("fb_batch_set: size mismatch");
     HIPCHK(hipMemcpy2D((char*)b->iarena + f.off*4, (size_t)b->off.nint*4, src, f.width*4, f.width*4, n, hipMemcpyHostToDevice));
+  } else if (field == FB_QFRC_LAW) {
+    return fail("fb_batch_set: FB_QFRC_LAW is read-only (the law stage writes it; fb_batch_set_control_law sets the law)");
   } else if (f.kind == REAL_ARRAY) {
     // applied forces: validated on the host (size, finite), then both arrays exist and k_step_forces steps the batch
     const char* name = field == FB_QFRC_APPLIED ? "FB_QFRC_APPLIED" : "FB_XFRC_APPLIED";
@@ -1842,6 +1980,7 @@ extern "C" int fb_batch_set(fb_batch* b, int field, const void* src, size_t byte
     for (size_t k = 0; k < (size_t)n*f.width; k++)
       if (!std::isfinite(v[k])) return fail(std::string("fb_batch_set: ") + name + " of environment " + std::to_string(k/f.width) + " is not finite");
     if (alloc_forces(b)) return -1;
+    b->law_owns_forces = false;
     void* dev = field == FB_QFRC_APPLIED ? b->qfrc_applied : b->xfrc_applied;
     return with_model(b, [&](auto& M) {
       const std::vector<decltype(M.timestep)> tmp(v, v + (size_t)n*f.width);
@@ -1870,7 +2009,12 @@ extern "C" void* fb_batch_device_ptr(fb_batch* b, int field) {
     case FB_ENV_MODEL: return b->env_model;            // (null on a batch made by fb_batch_create)
     case FB_QFRC_APPLIED: case FB_XFRC_APPLIED:        // (allocates both arrays on first use: the batch is stepped by k_step_forces from then on)
       if (hipSetDevice(b->device) != hipSuccess || alloc_forces(b)) return nullptr;
+      b->law_owns_forces = false;
       return field == FB_QFRC_APPLIED ? b->qfrc_applied : b->xfrc_applied;
+    case FB_QPOS: case FB_QVEL:                        // rows of the arena: environment e's row starts e x (fb_batch_row's row_bytes of the real arena) further on
+      return (char*)b->rarena + (size_t)(field == FB_QPOS ? b->off.qpos : b->off.qvel)*real_size(b);
+    case FB_QFRC_LAW: return b->law_out;               // (null while no law is set)
+    case FB_CONTROL_LAW: return b->law_coef;
     default: return nullptr;
   }
 }

@@ -5,6 +5,7 @@
 #include "fb_math.hpp"
 #include "fb_smooth.hpp"
 #include "fb_forces.hpp"
+#include "fb_law.hpp"
 #include "fb_collide.hpp"
 #include "fb_constraint.hpp"
 #include "fb_task.hpp"
@@ -415,10 +416,13 @@ template <typename real> FB_STAGE_C void s_post(const DevModel<real>& M_, const 
 // Returns true when the call was an auto-reset (the step is complete then).
 // FORCES (k_step_forces): qfrc_app / xfrc_app = the environment's rows of the applied-force arrays (fb_forces.hpp); every substep and a forward
 // evaluation read them, the forward pass of a reset does not.
-template <typename real, bool FORCES = false>
+// LAW (k_step_law): law_coef / law_qadr / law_out = the environment's coefficient block, the qpos addresses and its row of FB_QFRC_LAW
+// (fb_law.hpp); read and written where the forces are read, zeroed by the forward pass of a reset.
+template <typename real, bool FORCES = false, bool LAW = false>
 __device__ __forceinline__ bool d_run(const DevModel<real>& M, const WS<real>& w, int env, int mode, int nsub_arg, int nslot, int* sched, const float* action,
                       float* obs, float* reward, float* discount, int* step_type, int lane, int tk = -1, int only = -1,
-                      const real* qfrc_app = nullptr, const real* xfrc_app = nullptr) {
+                      const real* qfrc_app = nullptr, const real* xfrc_app = nullptr,
+                      const real* law_coef = nullptr, const int* law_qadr = nullptr, real* law_out = nullptr) {
   // every selector of the stage machine is wave-uniform: say so (v_readfirstlane), otherwise the interpreter's state lives in
   // VGPRs + saved exec masks across every stage call and counts against the register budget of all stages
   mode = uniform_int(mode); nsub_arg = uniform_int(nsub_arg); tk = uniform_int(tk); only = uniform_int(only);
@@ -476,6 +480,10 @@ __device__ __forceinline__ bool d_run(const DevModel<real>& M, const WS<real>& w
         // only.  The constraint projection, the factor's first consumer, follows.  Nothing LDS-resident crosses a launch
         // boundary any more (the factor and the Delassus matrix used to be parked in the global row between control steps).
         PROF_BEGIN();
+        if constexpr (LAW) {                                                                               // lx (= this substep's qfrc_actuator) += u, FB_QFRC_LAW = u
+          if (!resetting) s_control_law(M, wc, law_coef, law_qadr, law_out, lane);
+          else for (int i = lane; i < M.nv; i += FB_WAVE) law_out[i] = 0;
+        }
         if constexpr (FORCES) { if (!resetting) s_applied_forces(M, wc, qfrc_app, xfrc_app, lane); }      // lx += qfrc_applied + J' xfrc_applied
         for (int i = lane; i < M.nv; i += FB_WAVE) {
           real f = w.qfrc_passive()[i] - w.qfrc_bias()[i] + w.lx()[i];          // lx = qfrc_actuator (assembled there by ST_ACT)

@@ -62,7 +62,7 @@ template <typename real> FBD void d_pack_obs(const DevModel<real>& M, const WS<r
     obs[o + M.nobsjnt + k] = (float)w.qvel()[M.jnt_dofadr[j]];
   }
   o += 2*M.nobsjnt;
-  int nf = (M.task == FB_TASK_WALK_ON_BALL) ? 0 : M.future_steps + 1;        // walk_on_ball has no reference observables
+  int nf = (M.task == FB_TASK_WALK_ON_BALL || M.task == FB_TASK_TEMPLATE) ? 0 : M.future_steps + 1;        // walk_on_ball and template_task have no reference observables
   const RefView<real> rv = ref_view(M, w);
   for (int k = lane; k < nf; k += FB_WAVE) {
     real rr[7]; ref_root(rv, step + k, rr);
@@ -295,6 +295,15 @@ template <typename real> FBD Outcome<real> d_ball_post(const DevModel<real>& M, 
   return {r, term, false};
 }
 
+// ------------------------------------------------------------------ template_task (fly_envs.py:194-247, tasks/template_task.py)
+// The starting point for a user's own walking task: walk_imitation's walker and physics without a reference trajectory.  Episode init
+// (d_template_init) IS d_walk_init's inference branch -- the root pose from row 0 of the "reference" (the factory's init_qpos), every
+// other joint at qpos0, d_start_walker -- and the host refuses a dataset for this task (fb_batch_set_walk_dataset), so M.ds_qpos is null
+// and d_task_init sends the task through d_walk_init itself: s_init keeps its code.  before_step (d_template_pre) is d_walk_pre.
+// reward 1, termination on a physics error only (template_task.py:75-84, base.py:222-225); what a user builds on it is written from
+// PyTorch (BatchedFlyEnv reward_fn / termination_fn, fb_batch_end_episode)
+template <typename real> FBD Outcome<real> d_template_post(const PostHead<real>& h) { return {(real)1, physics_error(h.qn), false}; }
+
 // ------------------------------------------------------------------ flight_imitation
 // episode init (flight_imitation.py:112-144): root pose / linear velocity from the reference, wings from the wing-beat pattern
 // generator (flybody/tasks/pattern_generators.py:131-203, one state machine per environment) at a per-episode phase
@@ -412,17 +421,18 @@ template <typename real> FBD Outcome<real> d_flight_post(const DevModel<real>& M
 // ------------------------------------------------------------------ one dispatch per hook
 // env.reset(), before the forward pass with actuation disabled that follows it (dm_control Physics.after_reset)
 template <typename real> FBD void d_task_init(const DevModel<real>& M, const WS<real>& w, int env, int lane) {
-  if (M.task == FB_TASK_FLIGHT_IMITATION) d_flight_init(M, w, env, lane); else if (M.task == FB_TASK_WALK_ON_BALL) d_ball_init(M, w, lane); else d_walk_init(M, w, env, lane);
+  if (M.task == FB_TASK_FLIGHT_IMITATION) d_flight_init(M, w, env, lane); else if (M.task == FB_TASK_WALK_ON_BALL) d_ball_init(M, w, lane); else d_walk_init(M, w, env, lane);      // (template_task: the walker's inference branch)
 }
 template <typename real> FBD void d_task_pre(const DevModel<real>& M, const WS<real>& w, const float* action, int lane) {
-  if (M.task == FB_TASK_FLIGHT_IMITATION) d_flight_pre(M, w, action, lane); else d_walk_pre(M, w, action, lane);      // (walk_on_ball: the walker's)
+  if (M.task == FB_TASK_FLIGHT_IMITATION) d_flight_pre(M, w, action, lane); else d_walk_pre(M, w, action, lane);      // (walk_on_ball, template_task: the walker's)
 }
 // first: the environment was reset in this call (s_init and the forward pass ran instead of a control step)
 template <typename real> FBD void d_task_post(const DevModel<real>& M, const WS<real>& w, bool first, float* obs, float* reward, float* discount, int* step_type, int lane) {
   Outcome<real> out = {0, false, false};
   if (!first) {
     const PostHead<real> h = d_post_begin(M, w, lane);
-    if (M.task == FB_TASK_FLIGHT_IMITATION) out = d_flight_post(M, w, h, lane); else if (M.task == FB_TASK_WALK_ON_BALL) out = d_ball_post(M, w, h, lane); else out = d_walk_post(M, w, h, lane);
+    if (M.task == FB_TASK_FLIGHT_IMITATION) out = d_flight_post(M, w, h, lane); else if (M.task == FB_TASK_WALK_ON_BALL) out = d_ball_post(M, w, h, lane);
+    else if (M.task == FB_TASK_TEMPLATE) out = d_template_post(h); else out = d_walk_post(M, w, h, lane);
   }
   d_post_end(M, w, first, out, obs, reward, discount, step_type, lane);
 }

@@ -47,7 +47,7 @@ enum { TRN_JOINT = 0, TRN_TENDON = 3, TRN_BODY = 5 };
 enum { DYN_NONE = 0, DYN_FILTER = 2, DYN_FILTEREXACT = 3 };
 enum { CN_LIMIT = 0, CN_FRICTIONLESS = 1, CN_ELLIPTIC = 2 };
 // DevModel::task, the model blob's task_id (mjcf_compile.py writes it); the hooks of a task: fb_task.hpp
-enum { FB_TASK_WALK_IMITATION = 0, FB_TASK_FLIGHT_IMITATION = 1, FB_TASK_WALK_ON_BALL = 2 };
+enum { FB_TASK_WALK_IMITATION = 0, FB_TASK_FLIGHT_IMITATION = 1, FB_TASK_WALK_ON_BALL = 2, FB_TASK_TEMPLATE = 3 };
 // istate slots
 enum { IS_STEP = 0, IS_RESET_NEXT = 1, IS_STEP_TYPE = 2, IS_NCON = 3, IS_NEFC = 4, IS_NITER = 5, IS_NLIMIT = 6, IS_NCAND = 7,
        IS_WB_STEP = 8, IS_WB_FREQ = 9, IS_EPISODE = 10, IS_DS_OFF = 11, IS_DS_LEN = 12, IS_EPSTEPS = 13, IS_PRIO = 14, IS_WARN = 15, IS_WARN_EVER = 16,

@@ -40,7 +40,10 @@ FIELDS = dict(
     REWARD_FACTORS=(26, _F64, 5), GEOM_XPOS=(27, _F64, (3, 'ngeom')), GEOM_XMAT=(28, _F64, (9, 'ngeom')), CVEL=(29, _F64, (6, 'nbody')),
     STEP_TICKS=(30, _I32, 1), LAUNCH_ORDER=(31, _I32, 1), WARN=(32, _I32, 1), WARN_EVER=(33, _I32, 1), SIZE_STATS=(34, _I32, 4),
     SITE_XPOS=(35, _F64, (3, 'nsite')), IK_ERR=(36, _F64, 2), IK_STEPS=(37, _I32, 2), QFRC_INVERSE=(38, _F64, 'nv'),
-    CONTACT_FORCE=(39, _F64, 3*MAXCON), QFRC_APPLIED=(40, _F64, 'nv'), XFRC_APPLIED=(41, _F64, (6, 'nbody')), ENV_MODEL=(42, _I32, 1))
+    CONTACT_FORCE=(39, _F64, 3*MAXCON), QFRC_APPLIED=(40, _F64, 'nv'), XFRC_APPLIED=(41, _F64, (6, 'nbody')), ENV_MODEL=(42, _I32, 1),
+    QFRC_LAW=(43, _F64, 'nv'), CONTROL_LAW=(44, _F64, (5, 'nv')))
+TASK_IDS = dict(walk_imitation=0, flight_imitation=1, walk_on_ball=2, template_task=3)      # FB_TASK_* (csrc/fb_types.hpp)
+LAW_ROWS = ('bias', 'act_gain', 'pos_gain', 'pos_ref', 'vel_gain')                          # rows of CONTROL_LAW (csrc/fb_law.hpp)
 # bits of WARN / WARN_EVER (include/flybody_engine.h): the caps MuJoCo reports as nconmax / njmax warnings, and iteration limits
 WARN_BITS = dict(CONTACT_CAP=1, EFC_CAP=2, SOLVER_MAXITER=4, CCD_MAXITER=8, SCHED_WAIT=16, SOLVER_FALLBACK=32, MODEL_ID=64)
 
@@ -125,6 +128,10 @@ def load_library(lib_path: Optional[str] = None) -> C.CDLL:
     if hasattr(L, 'fb_batch_create_group'):
         L.fb_batch_create_group.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
         L.fb_batch_n_models.argtypes = [C.c_void_p]
+    if hasattr(L, 'fb_batch_set_control_law'):
+        L.fb_batch_set_control_law.argtypes = [C.c_void_p, C.c_void_p]
+        L.fb_batch_control_law_active.argtypes = [C.c_void_p]
+        L.fb_batch_end_episode.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     _libs[path] = L
     return L
 
@@ -154,9 +161,10 @@ def _check(L, rc):
 
 def observation_layout(model: 'Model', future_steps: int, ball: bool = False):
     """({observable: (offset, size, shape)}, width) of the packed observation vector (fb_task.hpp: d_pack_obs writes it).  The buffer is in
-    sorted-key order (tasks/task_utils.py:12); walk_on_ball (ball=True) has no reference observables, its ball's velocity instead."""
+    sorted-key order (tasks/task_utils.py:12); walk_on_ball (ball=True) has no reference observables, its ball's velocity instead;
+    template_task (the model's task id) has neither."""
     na, napp, nforce, nobsj, ntouch = (model.dim(k) for k in ('na', 'napp', 'nforce', 'nobsjnt', 'ntouch'))
-    nf = 0 if ball else future_steps + 1
+    nf = 0 if ball or model.dim('task_id') == TASK_IDS['template_task'] else future_steps + 1
     sizes = collections.OrderedDict([
         ('accelerometer', (3,)), ('actuator_activation', (na,)), ('appendages_pos', (3*napp,)), ('ball_qvel', (3 if ball else 0,)),
         ('force', (3*nforce,)),
@@ -172,6 +180,11 @@ class _IKConfig(C.Structure):
     """fb_ik_config (include/flybody_engine.h)."""
     _fields_ = [('n_site', C.c_int32), ('n_joint', C.c_int32), ('site_ids', C.c_void_p), ('joint_ids', C.c_void_p), ('include', C.c_void_p),
                 ('reg_strength', C.c_double), ('lr', C.c_double), ('beta', C.c_double), ('progress_threshold', C.c_double), ('max_steps', C.c_int32)]
+
+
+class _ControlLaw(C.Structure):
+    """fb_control_law (include/flybody_engine.h)."""
+    _fields_ = [(k, C.c_void_p) for k in LAW_ROWS] + [('n_rows', C.c_int32)]
 
 
 class Model:
@@ -367,8 +380,56 @@ class Batch:
         The arrays are caller-owned inputs: they persist until changed and nothing clears them on a reset (unlike MuJoCo)."""
         return self.L.fb_batch_forces_active(self.h) == 1
 
+    def set_control_law(self, bias=None, act_gain=None, pos_gain=None, pos_ref=None, vel_gain=None):
+        """A substep control law (fb_batch_set_control_law, csrc/fb_law.hpp): in every physics substep and forward evaluation
+            u = bias + act_gain*qfrc_actuator - pos_gain*(qpos[hinge of the dof] - pos_ref) - vel_gain*qvel
+        is added to the generalised forces, with this substep's actuator force.  Every row is [nv] (one law for the batch) or
+        [n_env, nv]; None is zeros.  pos_gain must be zero on dofs that are no hinge's.  u of the last substep: get('QFRC_LAW')."""
+        nv = self.model.dim('nv')
+        rows = [None if r is None else np.asarray(r, np.float64) for r in (bias, act_gain, pos_gain, pos_ref, vel_gain)]
+        per_env = any(r is not None and r.ndim == 2 and r.shape[0] == self.n_env and self.n_env > 1 for r in rows)
+        shape = (self.n_env if per_env else 1, nv)
+        keep = []
+        for name, r in zip(LAW_ROWS, rows):
+            if r is not None:
+                try:
+                    r = np.ascontiguousarray(np.broadcast_to(r.reshape((1, nv)) if r.size == nv else r, shape))
+                except ValueError:
+                    raise ValueError(f'control law row {name} has shape {r.shape}; expected [{nv}] or [{self.n_env}, {nv}]') from None
+            keep.append(r)
+        law = _ControlLaw(*(None if r is None else r.ctypes.data for r in keep), shape[0])
+        _check(self.L, self.L.fb_batch_set_control_law(self.h, C.byref(law)))
+        self._law_rows = shape[0]
+
+    def clear_control_law(self):
+        """Remove the control law: the batch is stepped by the kernel it had before (fb_batch_set_control_law(batch, NULL)).  Zero-copy
+        views of CONTROL_LAW / QFRC_LAW are dangling afterwards."""
+        _check(self.L, self.L.fb_batch_set_control_law(self.h, None))
+
+    @property
+    def control_law_active(self) -> bool:
+        return self.L.fb_batch_control_law_active(self.h) == 1
+
+    @property
+    def control_law_rows(self) -> int:
+        """Rows of the law that is set: 1 (one for the batch) or n_env; 0 without a law."""
+        return self._law_rows if self.control_law_active else 0
+
+    def end_episode(self, mask_dev_ptr: int, discount_dev_ptr: int = 0, stream=None):
+        """End the episodes of the environments whose byte in the device mask [n_env] is non-zero and whose last step was MID
+        (fb_batch_end_episode): they turn LAST with the float32 discount [n_env] behind discount_dev_ptr (0: discount 0) and the next
+        control step auto-resets them.  Asynchronous on `stream`."""
+        _check(self.L, self.L.fb_batch_end_episode(self.h, C.c_void_p(mask_dev_ptr), C.c_void_p(discount_dev_ptr) if discount_dev_ptr else None, stream))
+
     def synchronize(self, stream=None):
         _check(self.L, self.L.fb_batch_synchronize(self.h, stream))
+
+    def row_bytes(self, which: int = 0) -> int:
+        """Bytes of one environment's workspace row (which = 0 real arena, 1 int arena): the stride between the environments' rows behind
+        device_ptr('QPOS') / device_ptr('QVEL').  No copy, no synchronisation."""
+        n = C.c_size_t(0)
+        _check(self.L, self.L.fb_batch_row(self.h, which, 0, None, 0, 0, C.byref(n)))
+        return n.value
 
     def row(self, which: int, env: int, data: Optional[np.ndarray] = None) -> np.ndarray:
         """Profiling: the raw workspace row of one environment as bytes (which = 0 real arena, 1 int arena); data: write it back."""

@@ -89,6 +89,7 @@ class _TrajGenerator:
 class _Task:
     def __init__(self, owner):
         self._traj_generator = _TrajGenerator(owner)
+        self.prev_action = None            # the batched action the kernel was given last (after the action corruptor; fruitfly.py:532-544)
 
 
 class _Physics:
@@ -105,7 +106,8 @@ class BatchedFlyEnv:
                  wbpg_tables=None, seed: int = 0, traj_loader=None, env_id_base: int = 0, force_actuators: bool = False,
                  use_wings: Optional[bool] = None, use_legs: Optional[bool] = None, dyntype_filterexact: bool = False,
                  use_mouth: bool = False, use_antennae: bool = False, adhesion_filter: Optional[float] = None, dense: Optional[bool] = None,
-                 control_callback=None, models=None, env_model=None, resample_on_reset: bool = False):
+                 control_callback=None, models=None, env_model=None, resample_on_reset: bool = False, claw_friction: Optional[float] = None,
+                 init_qpos=None, reward_fn=None, termination_fn=None, action_corruptor=None, random_state=None):
         """models: a list of array dicts (flybody_amd.randomization.vary_model / sample_models) that the batch steps side by side --
         per-environment physics models, engine.ModelGroup; they replace the task's compiled model (the first one answers the specs) and
         must share its tree.  env_model: the initial assignment [n_env] (default: e % len(models)); env_model() is its device view.
@@ -113,16 +115,29 @@ class BatchedFlyEnv:
         seeded with `seed` (a torch op on the device, no host sync), so that their auto-reset starts the next episode under it.
         control_callback: a callable f(env) run before every CONTROL step of step() and step_tensor() -- the batched analogue of
         MuJoCo's mjcb_control, typically writing applied_forces() from the batch's state.  It runs once per control step, not once
-        per physics substep: what it writes holds for all substeps of that step."""
+        per physics substep: what it writes holds for all substeps of that step.  Feedback at the physics rate is a control law
+        (set_control_law, flybody_amd.control_laws): per-dof gains that the step kernel evaluates in every substep.
+        reward_fn(env) -> float tensor [n_env] and termination_fn(env) -> bool tensor [n_env], or (bool tensor, float32 discount tensor):
+        a task written in PyTorch on top of the kernel's.  After the step kernel, on the same stream and without a host sync, the
+        reward view becomes where(step_type == FIRST, 0, reward_fn(env)) and the environments the mask names end their episode
+        (Batch.end_episode: LAST with that discount, default 0; auto-reset by the next step).  A control step runs, in this order:
+        control_callback, action_corruptor, the kernel, reward_fn, termination_fn + end_episode, model resampling.
+        action_corruptor(action, random_state): applied to the batched action (the tensor of step_tensor, the [n_env, nact] array of
+        step) before the kernel sees it; task.prev_action holds what the kernel was given.
+        template_task only: init_qpos, the root pose [7] an episode starts from (default qpos0[:7]); claw_friction."""
         from . import model_zoo
         self.task_name = task
+        if task != 'template_task' and (claw_friction is not None or init_qpos is not None):
+            raise ValueError(f'claw_friction and init_qpos belong to template_task; {task} takes its claw friction from its compiled model and '
+                             'its start pose from its reference')
         # FruitFly._build's configuration space (fruitfly.py:123-386): the compiled tables come from the shipped assets, the
         # variant cache, or a fresh compile of the reference XML (model_zoo.get_model)
         compiled_filter = 0.0 if task == 'flight_imitation' else 0.01
         same_layout = (joint_filter > 0) == (compiled_filter > 0)
         cfg = model_zoo.task_config(task, force_actuators=force_actuators, use_wings=use_wings, use_legs=use_legs,
                                     joint_filter=None if same_layout else joint_filter, adhesion_filter=adhesion_filter,
-                                    dyntype_filterexact=dyntype_filterexact, use_mouth=use_mouth, use_antennae=use_antennae)
+                                    dyntype_filterexact=dyntype_filterexact, use_mouth=use_mouth, use_antennae=use_antennae,
+                                    claw_friction=claw_friction)
         arrays = model_zoo.get_model(cfg)
         if same_layout and joint_filter > 0 and joint_filter != compiled_filter:
             # a different filter TIME CONSTANT keeps the activation layout: patch the table instead of recompiling
@@ -169,6 +184,14 @@ class BatchedFlyEnv:
         elif task == 'walk_on_ball':
             self.batch.set_time_limit(time_limit)             # fly_envs.py:177: 2 s; no reference trajectory
             qp = qv = None
+        elif task == 'template_task':
+            # no reference trajectory either: the "reference" is the start pose (fb_task.hpp: the walker's inference init reads row 0)
+            if traj_loader is not None:
+                raise ValueError('template_task takes no reference dataset')
+            root = np.asarray(arrays['qpos0'][:7] if init_qpos is None else init_qpos, float)
+            if root.shape != (7,) or not np.isfinite(root).all():
+                raise ValueError('init_qpos must be a finite root pose [7]: position, then unit quaternion')
+            qp, qv = np.tile(root, (2, 1)), np.zeros((2, 6))
         elif traj_loader is not None:
             # training mode (fly_envs.py:131-135): the whole dataset lives on the GPU, every environment picks its snippet there
             ds = traj_loader.dataset
@@ -184,7 +207,9 @@ class BatchedFlyEnv:
         self.layout, self.nobs = observation_layout(self.model, future_steps, ball=(task == 'walk_on_ball'))
         self._torch_views = None
         self.control_callback = control_callback
-        self._force_views = None
+        self.reward_fn, self.termination_fn, self.action_corruptor = reward_fn, termination_fn, action_corruptor
+        self.random_state = random_state if random_state is not None else np.random.RandomState(seed)
+        self._force_views = None; self._law_views = None; self._end_args = None; self._state_views = None
         self._model_view = None; self._model_gen = None; self._seed = seed
         if (env_model is not None or resample_on_reset) and models is None:
             raise ValueError('env_model / resample_on_reset need models=[...]')
@@ -239,6 +264,24 @@ class BatchedFlyEnv:
                                      step_type=view('STEP_TYPE', (self.n_env,), torch.int32))
         return self._torch_views
 
+    def state_views(self):
+        """Zero-copy torch views dict(qpos=[n_env, nq], qvel=[n_env, nv]) of the physics state at the batch's precision, for rewards and
+        terminations computed on the device (reward_fn / termination_fn).  They are strided windows of the engine's arena: read them
+        after a step; writing between steps is Batch.set without its checks."""
+        if self._state_views is None:
+            import torch
+            f64 = self.batch.precision == 64
+            es = 8 if f64 else 4
+            row = self.batch.row_bytes(0)
+
+            def view(name, width):
+                iface = {'shape': (self.n_env, width), 'strides': (row, es), 'typestr': '<f8' if f64 else '<f4',
+                         'data': (self.batch.device_ptr(name), False), 'version': 2}
+                holder = type('DevBuf', (), {'__cuda_array_interface__': iface})()
+                return torch.as_tensor(holder, device=f'cuda:{self.device}')
+            self._state_views = dict(qpos=view('QPOS', self.model.dim('nq')), qvel=view('QVEL', self.model.dim('nv')))
+        return self._state_views
+
     def applied_forces(self):
         """Zero-copy torch views of the engine's external-force inputs, MuJoCo's qfrc_applied and xfrc_applied:
         dict(qfrc_applied=[n_env, nv], xfrc_applied=[n_env, nbody, 6]) at the batch's precision (float64 / float32); a body's row is
@@ -287,6 +330,70 @@ class BatchedFlyEnv:
         self._force_views = None
         self.batch.clear_forces()
 
+    # ---- substep control law (flybody_amd.control_laws, csrc/fb_law.hpp) ------------------------
+    def set_control_law(self, law):
+        """Feedback at the physics rate: `law` (control_laws.ControlLaw, rows [nv] or [n_env, nv]) is evaluated by the step kernel in
+        every substep, with that substep's actuator force.  The batch is stepped by the kernel that carries the law stage from now on."""
+        self._law_views = None
+        self.batch.set_control_law(**law.rows())
+
+    def control_law(self):
+        """Zero-copy torch views of the law on the device: the five rows bias / act_gain / pos_gain / pos_ref / vel_gain, each [n_rows, nv]
+        at the batch's precision -- write per-environment gains between steps without a host copy (pos_gain stays zero on dofs that are
+        no hinge's; values written here are not validated) -- and qfrc_law [n_env, nv], the law's force in the last substep (read-only)."""
+        if not self.batch.control_law_active:
+            raise engine.EngineError('no control law is set (set_control_law)')
+        if self._law_views is None:
+            import torch
+            dt = torch.float64 if self.batch.precision == 64 else torch.float32
+            nv = self.model.dim('nv')
+
+            def view(name, shape):
+                iface = {'shape': tuple(shape), 'typestr': '<f8' if dt == torch.float64 else '<f4', 'data': (self.batch.device_ptr(name), False), 'version': 2}
+                holder = type('DevBuf', (), {'__cuda_array_interface__': iface})()
+                return torch.as_tensor(holder, device=f'cuda:{self.device}')
+            n_rows = self.batch.control_law_rows
+            block = view('CONTROL_LAW', (n_rows, len(engine.LAW_ROWS), nv))
+            self._law_views = dict({k: block[:, r] for r, k in enumerate(engine.LAW_ROWS)}, qfrc_law=view('QFRC_LAW', (self.n_env, nv)))
+        return self._law_views
+
+    def clear_control_law(self):
+        """Remove the law; earlier control_law() views are dropped.  The batch returns to the kernel it had before the law."""
+        self._law_views = None
+        self.batch.clear_control_law()
+        if not self.batch.forces_active:
+            self._force_views = None
+
+    # ---- the parts of a control step around the kernel ------------------------------------------
+    @property
+    def _hooks_after(self) -> bool:
+        return self.reward_fn is not None or self.termination_fn is not None or self.resample_on_reset
+
+    def _corrupt(self, action):
+        if self.action_corruptor is not None:
+            action = self.action_corruptor(action, self.random_state)
+        return action
+
+    def _after_kernel(self, stream):
+        """reward_fn, termination_fn + end_episode, model resampling: torch ops and one small kernel on the step's stream, no host sync."""
+        import torch
+        v = self.torch_views()
+        if self.reward_fn is not None:
+            r = self.reward_fn(self).to(torch.float32)
+            v['reward'].copy_(torch.where(v['step_type'] == int(StepType.FIRST), torch.zeros_like(r), r))
+        if self.termination_fn is not None:
+            t = self.termination_fn(self)
+            t, disc = t if isinstance(t, tuple) else (t, None)
+            mask = t.to(torch.uint8).contiguous()
+            disc = None if disc is None else disc.to(torch.float32).contiguous()
+            if tuple(mask.shape) != (self.n_env,) or (disc is not None and tuple(disc.shape) != (self.n_env,)):
+                raise ValueError(f'termination_fn must return a bool tensor [{self.n_env}], or (that, a discount tensor [{self.n_env}]); got '
+                                 f'{tuple(mask.shape)}' + ('' if disc is None else f' and {tuple(disc.shape)}'))
+            self._end_args = (mask, disc)
+            self.batch.end_episode(mask.data_ptr(), 0 if disc is None else disc.data_ptr(), stream)
+        if self.resample_on_reset:
+            self._resample_models()
+
     def reset_all(self):
         import torch
         self.batch.reset(stream=torch.cuda.current_stream().cuda_stream)
@@ -300,9 +407,13 @@ class BatchedFlyEnv:
         assert tuple(action.shape) == (self.n_env, self.model.dim('nact'))
         if self.control_callback is not None:
             self.control_callback(self)
-        self.batch.step_ptr(action.data_ptr(), torch.cuda.current_stream().cuda_stream)
-        if self.resample_on_reset:
-            self._resample_models()
+        if self.action_corruptor is not None:
+            action = self._corrupt(action).to(torch.float32).contiguous()
+        self.task.prev_action = action
+        stream = torch.cuda.current_stream().cuda_stream
+        self.batch.step_ptr(action.data_ptr(), stream)
+        if self._hooks_after:
+            self._after_kernel(stream)
         self._time += self.control_timestep()
         return self.torch_views()
 
@@ -332,12 +443,15 @@ class BatchedFlyEnv:
     def step(self, action) -> TimeStep:
         import torch
         a = np.broadcast_to(np.asarray(action, np.float32), (self.n_env, self.model.dim('nact')))
-        t = torch.from_numpy(np.array(a, np.float32, copy=True)).to(f'cuda:{self.device}')
         if self.control_callback is not None:
             self.control_callback(self)
-        self.batch.step_ptr(t.data_ptr(), torch.cuda.current_stream().cuda_stream)
-        if self.resample_on_reset:
-            self._resample_models()
+        a = np.array(self._corrupt(a), np.float32, copy=True)
+        self.task.prev_action = a
+        t = torch.from_numpy(a).to(f'cuda:{self.device}')
+        stream = torch.cuda.current_stream().cuda_stream
+        self.batch.step_ptr(t.data_ptr(), stream)
+        if self._hooks_after:
+            self._after_kernel(stream)
         torch.cuda.synchronize()
         ts = self._timestep()
         self._time = 0.0 if ts.first() else self._time + self.control_timestep()
@@ -376,6 +490,33 @@ def walk_on_ball(force_actuators: bool = False, disable_wings: bool = True, rand
     return BatchedFlyEnv(n_env=n_env, device=device, precision=precision, terminal_com_dist=float('inf'), joint_filter=0.01,
                          future_steps=0, time_limit=2.0, task='walk_on_ball', force_actuators=force_actuators,
                          use_wings=not disable_wings, seed=seed, models=models, env_model=env_model, resample_on_reset=resample_on_reset)
+
+
+def template_task(random_state=None, force_actuators: bool = False, disable_wings: bool = True, joint_filter: float = 0.01,
+                  adhesion_filter: float = 0.007, time_limit: float = 1.0, mjcb_control=None, observables_options=None,
+                  action_corruptor=None, claw_friction: float = 1.0, n_env: int = 1, device: int = 0, precision: int = 64, seed: int = 0,
+                  init_qpos=None, reward_fn=None, termination_fn=None) -> BatchedFlyEnv:
+    """The starting point for a walking task of your own: same keyword surface as flybody/fly_envs.py:194-247, plus n_env / device /
+    precision / seed, init_qpos (the root pose [7] an episode starts from; default: standing at z = 0.1278) and the PyTorch hooks
+    reward_fn / termination_fn of BatchedFlyEnv.  The kernel's own task returns reward 1 and ends an episode at the time limit or on
+    a physics error; the observation is the walker's ten observables.
+    mjcb_control: a control_laws.ControlLaw, evaluated in every physics substep (BatchedFlyEnv.set_control_law).  A Python callable
+    cannot run inside the step kernel: it raises TypeError; BatchedFlyEnv(control_callback=f) runs one once per control step."""
+    from .control_laws import ControlLaw
+    if observables_options is not None:
+        raise NotImplementedError('template_task: observables_options is not supported (the observation layout is compiled into the kernel)')
+    if mjcb_control is not None and not isinstance(mjcb_control, ControlLaw):
+        raise TypeError('template_task: mjcb_control takes a flybody_amd.control_laws.ControlLaw, which the step kernel evaluates in every '
+                        'physics substep; a Python callable cannot run there -- pass it as control_callback to BatchedFlyEnv (or set '
+                        'env.control_callback), which runs it once per control step')
+    env = BatchedFlyEnv(n_env=n_env, device=device, precision=precision, terminal_com_dist=float('inf'), joint_filter=joint_filter,
+                        future_steps=0, time_limit=time_limit, task='template_task', force_actuators=force_actuators,
+                        use_wings=not disable_wings, adhesion_filter=adhesion_filter, seed=seed, claw_friction=claw_friction,
+                        init_qpos=init_qpos, reward_fn=reward_fn, termination_fn=termination_fn, action_corruptor=action_corruptor,
+                        random_state=random_state)
+    if mjcb_control is not None:
+        env.set_control_law(mjcb_control)
+    return env
 
 
 def flight_imitation(ref_path: Optional[str] = None, wpg_pattern_path: Optional[str] = None, force_actuators: bool = False,

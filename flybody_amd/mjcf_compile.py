@@ -277,6 +277,18 @@ def walk_imitation_config(joint_filter: float = 0.01) -> TaskConfig:
     return TaskConfig(name='walk_imitation', joint_filter=joint_filter)
 
 
+def template_task_config(joint_filter: float = 0.01, claw_friction: float = 1.0) -> TaskConfig:
+    # fly_envs.py:194-247, tasks/template_task.py: walk_imitation's Walking configuration under another task id
+    return TaskConfig(name='template_task', joint_filter=joint_filter, claw_friction=claw_friction)
+
+
+def mix_pair_friction(f1, f2):
+    """contact.friction[5] of a geom pair from the two geoms' friction[3]: the element-wise maximum (both priorities equal), laid out
+    as tangent1, tangent2, spin, roll1, roll2."""
+    f = np.maximum(f1, f2)
+    return np.array([f[0], f[0], f[1], f[2], f[2]], float)
+
+
 def walk_on_ball_config() -> TaskConfig:
     # fly_envs.py:158-191, tasks/walk_on_ball.py:15-48, tasks/arenas/ball.py
     return TaskConfig(name='walk_on_ball', floor=False, tethered=True, ball=((-0.05, 0.0, -0.419), 0.454, 0.0025),
@@ -1034,7 +1046,7 @@ class FlyCompiler:
         act_order = [names_act[i] for i in self.action_to_ctrl]
         m['wing_action_idx'] = np.array([k for k, n in enumerate(act_order) if 'wing' in n], int)
         m['user_action_idx'] = np.array(len(act_order) if cfg.num_user_actions else -1)
-        m['task_id'] = np.array({'walk_imitation': 0, 'flight_imitation': 1, 'walk_on_ball': 2}[cfg.name])
+        m['task_id'] = np.array({'walk_imitation': 0, 'flight_imitation': 1, 'walk_on_ball': 2, 'template_task': 3}[cfg.name])
         m['com_offset'] = np.array([-0.03697732, 0.00029205, -0.0142447])     # tasks/task_utils.py:237
         m['notes'] = np.array(self.notes)
         m['config_name'] = np.array(cfg.name)
@@ -1086,7 +1098,7 @@ class FlyCompiler:
                 a, b = (i, j) if gi['type'] <= gj['type'] else (j, i)
                 ga, gb = geoms[a], geoms[b]
                 condim = max(ga['condim'], gb['condim'])
-                friction = np.maximum(ga['friction'], gb['friction'])
+                friction = mix_pair_friction(ga['friction'], gb['friction'])
                 # solmix = 1 for both -> equal-weight average
                 solref = 0.5 * (ga['solref'] + gb['solref'])
                 solimp = 0.5 * (ga['solimp'] + gb['solimp'])
@@ -1094,8 +1106,7 @@ class FlyCompiler:
                 pairs.append((a, b, condim, friction, solref, solimp, margin, gap))
         m['pair_geom1'] = np.array([p[0] for p in pairs], int); m['pair_geom2'] = np.array([p[1] for p in pairs], int)
         m['pair_condim'] = np.array([p[2] for p in pairs], int)
-        # friction laid out as MuJoCo contact.friction[5]: tangent1, tangent2, spin, roll1, roll2
-        m['pair_friction'] = np.array([[p[3][0], p[3][0], p[3][1], p[3][2], p[3][2]] for p in pairs], float)
+        m['pair_friction'] = np.array([p[3] for p in pairs], float).reshape(len(pairs), 5)      # contact.friction[5] (mix_pair_friction)
         m['pair_solref'] = np.array([p[4] for p in pairs], float); m['pair_solimp'] = np.array([p[5] for p in pairs], float)
         m['pair_margin'] = np.array([p[6] for p in pairs], float); m['pair_gap'] = np.array([p[7] for p in pairs], float)
         # bounding radius per geom

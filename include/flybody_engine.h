@@ -81,6 +81,10 @@ enum {
                             world frame, applied at the body's centre of mass (xipos); the world body's row is ignored */
   FB_ENV_MODEL = 42,     /* [n_env] int32: index into the models of fb_batch_create_group that the environment is stepped with (see below);
                             fails on a batch made by fb_batch_create */
+  FB_QFRC_LAW = 43,      /* [n_env][nv] physics real: the generalised force u of the control law in the environment's last substep (or forward
+                            evaluation); zero after a reset (read-only; allocated by fb_batch_set_control_law) */
+  FB_CONTROL_LAW = 44,   /* [n_rows][5][nv] physics real: the law's coefficient block, rows bias, act_gain, pos_gain, pos_ref, vel_gain
+                            (fb_batch_device_ptr only: torch rewrites gains between steps without a host copy) */
   FB_NFIELD
 };
 
@@ -197,7 +201,10 @@ int fb_batch_set(fb_batch* b, int field, const void* src_host, size_t bytes);
 
 /* Device pointer of a field (e.g. to wrap FB_OBS in a torch tensor without a copy): FB_OBS, FB_REWARD, FB_DISCOUNT, FB_STEP_TYPE, and the
  * applied-force arrays FB_QFRC_APPLIED / FB_XFRC_APPLIED at the batch's precision (allocating them: see fb_batch_clear_forces), and FB_ENV_MODEL of a
- * grouped batch.  NULL otherwise. */
+ * grouped batch, FB_QFRC_LAW and FB_CONTROL_LAW while a control law is set.  FB_QPOS and FB_QVEL (physics real) point into the batch's
+ * arena: environment e's row starts e x row_bytes further on, row_bytes as fb_batch_row(b, 0, ...) reports it -- for rewards and
+ * terminations computed on the device (fb_batch_end_episode); writing there between steps is fb_batch_set without its checks.
+ * NULL otherwise. */
 void* fb_batch_device_ptr(fb_batch* b, int field);
 int fb_batch_synchronize(fb_batch* b, void* stream);
 
@@ -280,6 +287,37 @@ int fb_batch_inverse(fb_batch* b, int flags, void* stream);
  * Both precisions.  fb_batch_forces_active: 1 while the arrays are allocated, 0 otherwise. */
 int fb_batch_clear_forces(fb_batch* b);
 int fb_batch_forces_active(const fb_batch* b);
+
+/* Substep control laws.  A law is five rows per dof, evaluated by the step kernel in EVERY physics substep of fb_batch_step and
+ * fb_batch_substep, and in fb_batch_forward:
+ *     u[i] = bias[i] + act_gain[i]*qfrc_actuator[i] - pos_gain[i]*(qpos[adr(i)] - pos_ref[i]) - vel_gain[i]*qvel[i]
+ *     qfrc_smooth = qfrc_passive - qfrc_bias + qfrc_actuator + u + qfrc_applied + J' xfrc_applied
+ * adr(i) is the qpos address of dof i's hinge.  It is what MuJoCo's mjcb_control does when it writes qfrc_applied from the state, for the
+ * laws that are diagonal in the dofs: joint springs and dampers, motor noise, assistive torques.
+ * qfrc_actuator is THIS substep's actuator force.  MuJoCo runs the callback before it computes the actuator forces, so a callback that
+ * reads qfrc_actuator sees the previous substep's; the current one is used here because "act_gain = g" then means exactly "every motor
+ * is (1 + g) times as strong", which can be checked against a model whose gains, biases and force ranges are scaled.
+ * Rows: n_rows = 1 (one law for the batch) or n_env (one per environment), each row [nv] FP64, converted to the batch's precision; a
+ * null row is zeros; all values must be finite; pos_gain must be zero on every dof that is not a hinge's (free root, ball joints): the
+ * call fails naming the dof.  u of the last substep is readable as FB_QFRC_LAW; the forward pass of a reset (fb_batch_reset and the
+ * auto-reset) skips the law, as it skips the applied forces, and leaves FB_QFRC_LAW zero.  FB_QFRC_ACTUATOR stays the actuators' own.
+ * Setting a law allocates the applied-force arrays as their first access does, and the batch is stepped by a third step kernel
+ * (k_step_law: the forces kernel plus the law stage; an all-zero law gives the forces kernel's results).  fb_batch_set_control_law(b, NULL)
+ * clears the law and returns the batch to the kernel it had: the forces kernel if the caller touched the force arrays, the plain one
+ * otherwise.  Refused: a grouped batch (give every model a batch of its own); fb_batch_stage, fb_batch_ik and fb_batch_inverse while a law
+ * is set (clear it first); fb_batch_clear_forces while a law is set.  The coefficient block on the device is FB_CONTROL_LAW
+ * (fb_batch_device_ptr); values written there are not validated -- a non-finite one ends the episode through the blow-up guard.
+ * fb_batch_control_law_active: 1 while a law is set. */
+typedef struct { const double *bias, *act_gain, *pos_gain, *pos_ref, *vel_gain; int n_rows; } fb_control_law;
+int fb_batch_set_control_law(fb_batch* b, const fb_control_law* law);
+int fb_batch_control_law_active(const fb_batch* b);
+
+/* Ends episodes from the device, for rewards and terminations computed outside the kernel (e.g. in PyTorch).  One thread per
+ * environment, asynchronous on `stream`: where mask_dev[e] != 0 and the environment's last step type is MID, FB_STEP_TYPE becomes LAST,
+ * FB_DISCOUNT becomes discount_dev[e] (0 when discount_dev is NULL) and the next fb_batch_step auto-resets the environment, exactly as
+ * after a LAST the step kernel decided.  Environments that are FIRST or already LAST are left as the kernel left them.  mask_dev:
+ * [n_env] bytes, discount_dev: [n_env] float32, both device pointers.  Every task. */
+int fb_batch_end_episode(fb_batch* b, const uint8_t* mask_dev, const float* discount_dev, void* stream);
 
 /* Per-environment physics models in one batch (domain randomisation).  fb_batch_create_group creates n_env environments that share ONE
  * tree and differ in real-valued constants: environment e is stepped with models[FB_ENV_MODEL[e]].  The models must be compatible with
