@@ -682,7 +682,6 @@ __device__ __forceinline__ void fly_kernel(const DevModel<real>* Mp, const Batch
       bool bad_id;
       const DevModel<real>& Me = model_of_env<real, MODELS>(Mp, M, G, env, bad_id);
       const WS<real> w = ws_env(Me, B.rarena, B.iarena, env, s_pool, wave, &s_tab);
-      float* obs = B.obs ? B.obs + (size_t)env*B.nobs : nullptr;
 #ifdef FB_EMULATE
       // (host emulation, test infrastructure: every ticket starts from a POISONED LDS pool -- whatever a stage left there for a later ticket,
       //  against the claim that nothing LDS-resident crosses a ticket boundary, turns the state into NaN and fails the parity tests)
@@ -694,14 +693,21 @@ __device__ __forceinline__ void fly_kernel(const DevModel<real>* Mp, const Batch
 #if defined(FB_PROFILE) && !defined(FB_EMULATE)
       const long long tw1_ = wall_clock64();       // (tools/ticket_trace.py) per environment: wait for the predecessor, first start, last end, busy ticks
 #endif
-      const real *qf_ = nullptr, *xf_ = nullptr;
-      if constexpr (FORCES) { qf_ = F.qfrc_applied + (size_t)env*M.nv; xf_ = F.xfrc_applied + (size_t)env*6*M.nbody; }
-      const real* lc_ = nullptr; real* lo_ = nullptr;
-      if constexpr (LAW) { lc_ = L.coef + (L.per_env ? (size_t)env*LAW_NROW*M.nv : (size_t)0); lo_ = L.out + (size_t)env*M.nv; }
-      const bool was_reset = d_run<real, FORCES, LAW>(Me, w, env, mode, nsub, nslot, (int*)nullptr, action ? action + (size_t)env*M.nact : nullptr, obs, B.reward + env,
-                                   B.discount + env, B.step_type + env, lane, (round == 0 ? 1 : 0) | (round == nunit - 1 ? 2 : 0) | (tkhalf == 1 ? 4 : 0) | (tkhalf == 2 ? 8 : 0) | (late ? 16 : 0),
-                                   -1, qf_, xf_, lc_, L.qadr, lo_);
-      if constexpr (MODELS) { if (bad_id && lane == 0) { atomicOr(w.istate() + IS_WARN, (int)WARN_MODEL_ID); atomicOr(w.istate() + IS_WARN_EVER, (int)WARN_MODEL_ID); } }
+      // the stages read a copy of the descriptor, by reference, and the step's rows are formed where a stage takes them: neither stays in
+      // registers across the stage calls (fb_step.hpp: d_run)
+      const WS<real> wc = w;
+      auto io = [&]() {
+        StepIO<real> o = {action ? action + (size_t)env*M.nact : nullptr, B.obs ? B.obs + (size_t)env*B.nobs : nullptr, B.reward + env, B.discount + env, B.step_type + env,
+                          nullptr, nullptr, nullptr, nullptr, nullptr};
+        if constexpr (FORCES) { o.qfrc_app = F.qfrc_applied + (size_t)env*M.nv; o.xfrc_app = F.xfrc_applied + (size_t)env*6*M.nbody; }
+        if constexpr (LAW) { o.law_coef = L.coef + (L.per_env ? (size_t)env*LAW_NROW*M.nv : (size_t)0); o.law_qadr = L.qadr; o.law_out = L.out + (size_t)env*M.nv; }
+        return o;
+      };
+      const bool was_reset = d_run<real, FORCES, LAW>(Me, wc, io, env, mode, nsub, nslot, (int*)nullptr, lane,
+                                   (round == 0 ? 1 : 0) | (round == nunit - 1 ? 2 : 0) | (tkhalf == 1 ? 4 : 0) | (tkhalf == 2 ? 8 : 0) | (late ? 16 : 0), -1);
+      if constexpr (MODELS) {
+        if (bad_id && lane == 0) { int* is_ = ws_uniform(wc, Me).istate(); atomicOr(is_ + IS_WARN, (int)WARN_MODEL_ID); atomicOr(is_ + IS_WARN_EVER, (int)WARN_MODEL_ID); }
+      }
 #ifndef FB_EMULATE
       // Release.  What the next holder of this environment (a wave of the SAME XCD: environments are bound to XCDs) must see is this
       // wave's global stores.  On gfx942 / gfx950 the vector L1 is write-through and an XCD has ONE L2, so "visible to the XCD" =
@@ -712,7 +718,7 @@ __device__ __forceinline__ void fly_kernel(const DevModel<real>* Mp, const Batch
       // launch: the stream reaches every XCD) and the scheduler is switched off otherwise.
 #ifdef FB_PROFILE
       if (lane == 0) {
-        long long* pp_ = (long long*)w.prof(); const long long tw2_ = wall_clock64();
+        long long* pp_ = (long long*)ws_uniform(wc, Me).prof(); const long long tw2_ = wall_clock64();
         if (round == 0) { pp_[52] = 0; pp_[53] = tw0_; pp_[55] = 0; }
         pp_[52] += tw1_ - tw0_; pp_[54] = tw2_; pp_[55] += tw2_ - tw1_;
       }
@@ -730,7 +736,6 @@ __device__ __forceinline__ void fly_kernel(const DevModel<real>* Mp, const Batch
   bool bad_id;
   const DevModel<real>& Me = model_of_env<real, MODELS>(Mp, M, G, env, bad_id);
   const WS<real> w = ws_env(Me, B.rarena, B.iarena, env, s_pool, wave, &s_tab);
-  float* obs = B.obs ? B.obs + (size_t)env*B.nobs : nullptr;
 #if defined(FB_PROFILE) && !defined(FB_EMULATE)
   long long t0_ = clock64(), r0_ = wall_clock64();
 #endif
@@ -746,21 +751,27 @@ __device__ __forceinline__ void fly_kernel(const DevModel<real>* Mp, const Batch
     for (int i = lane; i < LdsCfg<real>::POOL; i += FB_WAVE) w.lLD[i] = pk[i];
     SYNC();
   } else if (lane == 0) { w.istate()[IS_PRIO] = 0; if (mode == MODE_STEP || mode == MODE_RESET) w.istate()[IS_WARN] = 0; }
-  const real *qf_ = nullptr, *xf_ = nullptr;
-  if constexpr (FORCES) { qf_ = F.qfrc_applied + (size_t)env*M.nv; xf_ = F.xfrc_applied + (size_t)env*6*M.nbody; }
-  const real* lc_ = nullptr; real* lo_ = nullptr;
-  if constexpr (LAW) { lc_ = L.coef + (L.per_env ? (size_t)env*LAW_NROW*M.nv : (size_t)0); lo_ = L.out + (size_t)env*M.nv; }
-  d_run<real, FORCES, LAW>(Me, w, env, only >= 0 ? (int)MODE_STEP : mode, nsub, nslot, only >= 0 ? (int*)nullptr : B.sched, action ? action + (size_t)env*M.nact : nullptr, obs, B.reward + env,
-        B.discount + env, B.step_type + env, lane, -1, only, qf_, xf_, lc_, L.qadr, lo_);
-  if constexpr (MODELS) { if (bad_id && lane == 0) { atomicOr(w.istate() + IS_WARN, (int)WARN_MODEL_ID); atomicOr(w.istate() + IS_WARN_EVER, (int)WARN_MODEL_ID); } }
+  const WS<real> wc = w;                  // (as on the ticket path: the stages' copy of the descriptor, the step's rows formed where they are used)
+  auto io = [&]() {
+    StepIO<real> o = {action ? action + (size_t)env*M.nact : nullptr, B.obs ? B.obs + (size_t)env*B.nobs : nullptr, B.reward + env, B.discount + env, B.step_type + env,
+                      nullptr, nullptr, nullptr, nullptr, nullptr};
+    if constexpr (FORCES) { o.qfrc_app = F.qfrc_applied + (size_t)env*M.nv; o.xfrc_app = F.xfrc_applied + (size_t)env*6*M.nbody; }
+    if constexpr (LAW) { o.law_coef = L.coef + (L.per_env ? (size_t)env*LAW_NROW*M.nv : (size_t)0); o.law_qadr = L.qadr; o.law_out = L.out + (size_t)env*M.nv; }
+    return o;
+  };
+  d_run<real, FORCES, LAW>(Me, wc, io, env, only >= 0 ? (int)MODE_STEP : mode, nsub, nslot, only >= 0 ? (int*)nullptr : B.sched, lane, -1, only);
+  if constexpr (MODELS) {
+    if (bad_id && lane == 0) { int* is_ = ws_uniform(wc, Me).istate(); atomicOr(is_ + IS_WARN, (int)WARN_MODEL_ID); atomicOr(is_ + IS_WARN_EVER, (int)WARN_MODEL_ID); }
+  }
   if (only >= 0) {
     SYNC();
     FB_GLOBAL real* pk = (FB_GLOBAL real*)(B.park + (size_t)env*LdsCfg<real>::POOL);
-    for (int i = lane; i < LdsCfg<real>::POOL; i += FB_WAVE) pk[i] = w.lLD[i];
+    const FB_LDS real* pool = ws_uniform(wc, Me).lLD;
+    for (int i = lane; i < LdsCfg<real>::POOL; i += FB_WAVE) pk[i] = pool[i];
     return;
   }
 #if defined(FB_PROFILE) && !defined(FB_EMULATE)
-  if (lane == 0) { long long* pp_ = (long long*)w.prof(); pp_[29] += clock64() - t0_; pp_[30] += wall_clock64() - r0_; pp_[28] = r0_; /* start tick (replaces the env_post phase counter) */ }
+  if (lane == 0) { long long* pp_ = (long long*)ws_uniform(wc, Me).prof(); pp_[29] += clock64() - t0_; pp_[30] += wall_clock64() - r0_; pp_[28] = r0_; /* start tick (replaces the env_post phase counter) */ }
 #endif
   // how long this environment's control step took: the next launch starts the slow environments first (k_order)
   if (mode == MODE_STEP && B.cost && lane == 0) {

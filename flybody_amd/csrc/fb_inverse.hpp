@@ -60,7 +60,7 @@ __device__ __forceinline__ void inverse_kernel(const DevModel<real>* Mp, real* r
   s_crb(M, wc, lane);
   s_collision(M, wc, lane);
   s_make_constraint(M, wc, lane);
-  s_velocity(M, wc, lane);
+  s_velocity(M, wc, false, (int*)nullptr, 0, lane);
   const int nv = M.nv;
   // ---- the continuous acceleration, in the solve vector lx (the LDS pool is free behind the velocity stage)
   FB_LDS real* Q = w.lx();
@@ -69,8 +69,8 @@ __device__ __forceinline__ void inverse_kernel(const DevModel<real>* Mp, real* r
     // rounding of M qacc and its solve does not enter the result
     for (int i = lane; i < nv; i += FB_WAVE) Q[i] = M.timestep*M.dof_damping[i]*w.qacc()[i];
     SYNC();
-    d_factor(M, wc, (const FB_GLOBAL real*)w.qM(), (const FB_GLOBAL real*)nullptr, (real)0, w.lLD, Q, lane);
-    d_solve(M, wc, w.lLD, Q, true, lane);
+    d_factor_plain(M, wc, lane);          // (x = the solve vector lx = Q, no damping)
+    d_solve(M, wc, true, lane);
     for (int i = lane; i < nv; i += FB_WAVE) Q[i] += w.qacc()[i];
   } else {
     for (int i = lane; i < nv; i += FB_WAVE) Q[i] = w.qacc()[i];

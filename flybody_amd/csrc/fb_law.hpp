@@ -33,13 +33,15 @@ struct LawArgs {
 
 // lx[i] += u[i], FB_QFRC_LAW[i] = u[i]; coef_ / out_ = the environment's block and row.  One lane per dof, two passes for nv = 108; every
 // row is read coalesced at clamped indices, then selected (one round of loads per pass).
+// `zero` (the forward pass of a reset): no law, the row is zeroed.
 template <typename real>
-__device__ FB_NOINLINE void s_control_law(const DevModel<real>& M_, const WS<real>& w_, const real* coef_, const int* qadr_, real* out_, int lane) {
+__device__ FB_NOINLINE void s_control_law(const DevModel<real>& M_, const WS<real>& w_, const real* coef_, const int* qadr_, real* out_, bool zero, int lane) {
   const DevModel<real>& M = as_constant(M_); const WS<real> w = ws_uniform(w_, M);
   const FB_GLOBAL real* cf = (const FB_GLOBAL real*)uniform_p(coef_);
   const FB_GLOBAL int* qa = (const FB_GLOBAL int*)uniform_p(qadr_);
   FB_GLOBAL real* out = (FB_GLOBAL real*)uniform_p(out_);
   const int nv = M.nv;
+  if (uniform_int(zero ? 1 : 0) != 0) { for (int i = lane; i < nv; i += FB_WAVE) out[i] = 0; return; }
 #pragma unroll
   for (int q = 0; q < (FB_MAXNV + FB_WAVE - 1)/FB_WAVE; q++) {
     const int i = lane + q*FB_WAVE; const bool ok = i < nv; const int is = ok ? i : 0;

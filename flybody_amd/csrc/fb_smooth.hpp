@@ -698,8 +698,7 @@ FBD real fac_pull(real* row, const FB_LDS real* pc, const FB_LDS real* pd, const
 }
 
 template <typename real>
-FB_STAGE_FS void d_factor_tail(const DevModel<real>& M_, const WS<real>& w_, const FB_GLOBAL real* qM, const FB_GLOBAL real* diag_add, real hscale,
-                              FB_LDS real* RM, FB_LDS real* x, int lane);
+FB_STAGE_FS void d_factor_tail(const DevModel<real>& M_, const WS<real>& w_, bool damp, int lane);
 
 // The factorisation carries a right-hand side along: x (LDS, nv reals) leaves as L^-T x.  The leaf-to-root half of a solve visits
 // the levels in the order of the elimination and pulls through the same LDS words as the row updates (row entry, 1/D, and the
@@ -716,12 +715,34 @@ FB_STAGE_FS void d_factor_tail(const DevModel<real>& M_, const WS<real>& w_, con
 // level costs each row one scalar coefficient and depth(i) + 1 LDS reads + FMAs at consecutive addresses -- no work list, no
 // per-entry address arithmetic.  Rows still leave unnormalised with 1/D in the diagonal slot (d_factor_tail normalises them and
 // forms the trunk's Schur complement exactly as before).
-template <typename real>
-FB_STAGE_FS void d_factor(const DevModel<real>& M_, const WS<real>& w_, const FB_GLOBAL real* qM, const FB_GLOBAL real* diag_add, real hscale,
-                         FB_LDS real* RM, FB_LDS real* x, int lane) {
+//
+// The stage finds its own operands (the step kernel's interpreter keeps no descriptor in registers for them, fb_step.hpp): M is the
+// environment's qM, the factor goes to the LDS pool's factor row, x is the solve vector lx; `damp` (wave-uniform) adds h D to the diagonal.
+// RHS: the stage first ASSEMBLES its right-hand side in lx, as the interpreter did in front of the call --
+//   damp = false: qfrc_smooth = lx = qfrc_passive - qfrc_bias + lx     (lx holds qfrc_actuator [+ law + applied forces] on entry)
+//   damp = true:  lx = qfrc_smooth + qfrc_constraint                   (the Euler step's right-hand side)
+// d_factor is the step kernel's stage, d_factor_plain the one of a caller that brings x itself (k_inverse).
+template <typename real, bool RHS>
+FBD void d_factor_rows(const DevModel<real>& M_, const WS<real>& w_, bool damp_, int lane) {
   const DevModel<real>& M = as_constant(M_); const WS<real> w = ws_uniform(w_, M);
-  qM = uniform_p(qM); diag_add = uniform_p(diag_add); RM = uniform_p(RM); x = uniform_p(x);
+  const bool damp = uniform_int(damp_ ? 1 : 0) != 0;
+  const FB_GLOBAL real* qM = (const FB_GLOBAL real*)w.qM();
+  const FB_GLOBAL real* diag_add = damp ? M.dof_damping.p : (const FB_GLOBAL real*)nullptr;
+  const real hscale = damp ? M.timestep : (real)0;
+  FB_LDS real* RM = w.lLD; FB_LDS real* x = w.lx();
   PROF_BEGIN();
+  if constexpr (RHS) {
+    if (damp) {
+      for (int i = lane; i < M.nv; i += FB_WAVE) x[i] = w.qfrc_smooth()[i] + w.qfrc_constraint()[i];
+    } else {
+      for (int i = lane; i < M.nv; i += FB_WAVE) {
+        real f = w.qfrc_passive()[i] - w.qfrc_bias()[i] + x[i];
+        w.qfrc_smooth()[i] = f; x[i] = f;
+      }
+    }
+    SYNC();
+    PROF(24);
+  }
   const int nv = uniform_int(M.nv), nT = uniform_int(M.ntrunk), nlevel = uniform_int(M.nlevel);
   const FB_LDS uint32_t* gm = w.lgm();          // locals: a fence must not force reloading them from the WS struct
   const FB_LDS uint32_t* gk = w.lgk();
@@ -805,17 +826,24 @@ FB_STAGE_FS void d_factor(const DevModel<real>& M_, const WS<real>& w_, const FB
   PROF_RESET();
   // the rows are dead from here on (every one was published, unnormalised, on its own level): the trunk and the normalisation run
   // as a function of their own, with their own register allocation
-  d_factor_tail(M, w_, qM, diag_add, hscale, RM, x, lane);
+  d_factor_tail(M, w_, damp, lane);
 }
+template <typename real>
+FB_STAGE_FS void d_factor(const DevModel<real>& M_, const WS<real>& w_, bool damp, int lane) { d_factor_rows<real, true>(M_, w_, damp, lane); }
+template <typename real>
+FB_STAGE_FS void d_factor_plain(const DevModel<real>& M_, const WS<real>& w_, int lane) { d_factor_rows<real, false>(M_, w_, false, lane); }
 
 // Second half of the factorisation: the dense Schur complement of the trunk rows (the free joint), the normalisation of
 // the published rows and the small dense LDL of the trunk.  Reads the unnormalised rows from LDS; its only inputs besides
 // them are the packed work words (re-read from the model) and the trunk rows of M.
 template <typename real>
-FB_STAGE_FS void d_factor_tail(const DevModel<real>& M_, const WS<real>& w_, const FB_GLOBAL real* qM, const FB_GLOBAL real* diag_add, real hscale,
-                              FB_LDS real* RM, FB_LDS real* x, int lane) {
+FB_STAGE_FS void d_factor_tail(const DevModel<real>& M_, const WS<real>& w_, bool damp_, int lane) {
   const DevModel<real>& M = as_constant(M_); const WS<real> w = ws_uniform(w_, M);
-  qM = uniform_p(qM); diag_add = uniform_p(diag_add); RM = uniform_p(RM); x = uniform_p(x);
+  const bool damp = uniform_int(damp_ ? 1 : 0) != 0;
+  const FB_GLOBAL real* qM = (const FB_GLOBAL real*)w.qM();
+  const FB_GLOBAL real* diag_add = damp ? M.dof_damping.p : (const FB_GLOBAL real*)nullptr;
+  const real hscale = damp ? M.timestep : (real)0;
+  FB_LDS real* RM = w.lLD; FB_LDS real* x = w.lx();
   PROF_BEGIN();
   const int nv = uniform_int(M.nv), nT = uniform_int(M.ntrunk);
   int fd[2], jt[2];
@@ -935,9 +963,9 @@ FB_STAGE_FS void d_factor_tail(const DevModel<real>& M_, const WS<real>& w_, con
 // x <- M^-1 x using the factorisation (everything in LDS).  half = true: x already holds L^-T x (d_factor carried it along), only
 // D^-1 and L^-1 are applied.
 template <typename real>
-FB_STAGE_FS void d_solve(const DevModel<real>& M_, const WS<real>& w_, const FB_LDS real* RM, FB_LDS real* x, bool half, int lane) {
+FB_STAGE_FS void d_solve(const DevModel<real>& M_, const WS<real>& w_, bool half, int lane) {
   const DevModel<real>& M = as_constant(M_); const WS<real> w = ws_uniform(w_, M);
-  RM = uniform_p(RM); x = uniform_p(x);
+  const FB_LDS real* RM = w.lLD; FB_LDS real* x = w.lx();          // the factor row and the solve vector of the environment's LDS pool
   PROF_BEGIN();
   const int nv = uniform_int(M.nv), nT = uniform_int(M.ntrunk), nlevel = uniform_int(M.nlevel);
   const FB_LDS uint32_t* gk = w.lgk();

@@ -362,7 +362,7 @@ enum { ST_PRE = 32, ST_POST = 33 };
 // Every stage of the step is compiled as a function of its own: the register allocator then works on one stage at a
 // time instead of on the whole state machine (measured: the fully inlined kernel is ~25% slower).  A stage receives the
 // model (constant memory) and a copy of the workspace descriptor; it moves the descriptor's pointers back to SGPRs.
-// trailing-wave priority thresholds, in 32nds of the launch's environments (see ST_SUBEND)
+// trailing-wave priority thresholds, in 32nds of the launch's environments (s_velocity)
 #define FB_PRIO_T1 16
 #define FB_PRIO_T2 28
 #define FB_PRIO_T3 31
@@ -376,13 +376,44 @@ FB_STAGE_WRAP(s_com_pos, d_com_pos(M, w, lane))
 FB_STAGE_WRAP(s_crb, d_crb(M, w, lane))
 FB_STAGE_WRAP(s_collision, d_collision(M, w, lane))
 FB_STAGE_WRAP(s_make_constraint, d_make_constraint(M, w, lane))
-FB_STAGE_WRAP(s_project_constraint, d_project_constraint(M, w, lane))
-template <typename real> FB_STAGE_C void s_velocity(const DevModel<real>& M_, const WS<real>& w_, int lane) {
+// (the projection's stage keeps the smooth acceleration first: the solve that precedes it left M^-1 qfrc_smooth in lx, and every lane of it is fenced)
+template <typename real> FB_STAGE_C void s_project_constraint(const DevModel<real>& M_, const WS<real>& w_, int parts, int lane) {
+  const DevModel<real>& M = as_constant(M_); const WS<real> w = ws_uniform(w_, M);
+  parts = uniform_int(parts);                                                            // (MODE_STAGE: 1 = the copy, 2 = the projection; the step passes 3)
+  if (parts & 1) {
+    for (int i = lane; i < M.nv; i += FB_WAVE) w.qacc_smooth()[i] = w.lx()[i];
+    SYNC();
+  }
+  if (parts & 2) d_project_constraint(M, w, lane); }
+// The velocity stage closes a substep: with `acc` the sensors it completes are added to the control step's accumulators, and with a progress
+// counter (`ctr`, null: none) the wave counts itself in and gets its issue priority for the next substep (returned, -1: none; see ST_COLL in d_run).
+template <typename real> FB_STAGE_C int s_velocity(const DevModel<real>& M_, const WS<real>& w_, bool acc, int* ctr_, int nslot, int lane) {
   const DevModel<real>& M = as_constant(M_); const WS<real> w = ws_uniform(w_, M);
   FB_LDS real* Lv = w.lLD + vel_off_v(M); FB_LDS real* X = w.lLD + vel_off_x(M);        // body velocities / per-body wrenches (fb_smooth.hpp)
   real ab[2][6];                                                                         // bias accelerations of the lane's two bodies
-  d_com_vel(M, w, Lv, ab, lane); d_passive(M, w, Lv, X, lane); d_rne_bias(M, w, Lv, X, ab, lane); d_sensor_vel(M, w, lane); }
+  d_com_vel(M, w, Lv, ab, lane); d_passive(M, w, Lv, X, lane); d_rne_bias(M, w, Lv, X, ab, lane); d_sensor_vel(M, w, lane);
+  int prio = -1;
+  if (uniform_int(acc ? 1 : 0) != 0) {
+    if (lane < FB_NSENS) w.sens_acc()[lane] += w.sens()[lane];
+    SYNC();
+  }
+  int* ctr = uniform_p(ctr_);
+  if (ctr) {
+    nslot = uniform_int(nslot);
+    int before = 0;
+    if (lane == 0) before = atomicAdd(ctr, 1);
+    before = uniform_int(before);
+    prio = (32*before < FB_PRIO_T1*nslot) ? 0 : (32*before < FB_PRIO_T2*nslot ? 1 : (32*before < FB_PRIO_T3*nslot ? 2 : 3));
+    if (lane == 0) w.istate()[IS_PRIO] = prio;
+  }
+  return prio; }
 FB_STAGE_WRAP(s_actuation, d_actuation(M, w, lane))
+// a pass without controls (the forward pass of a reset): no actuator forces, no activation derivatives
+template <typename real> FB_STAGE_C void s_actuation_zero(const DevModel<real>& M_, const WS<real>& w_, int lane) {
+  const DevModel<real>& M = as_constant(M_); const WS<real> w = ws_uniform(w_, M);
+  for (int i = lane; i < M.nv; i += FB_WAVE) { w.qfrc_actuator()[i] = 0; w.lx()[i] = 0; }
+  for (int i = lane; i < M.na; i += FB_WAVE) w.act_dot()[i] = 0;
+  SYNC(); }
 FB_STAGE_WRAP(s_constraint_b, d_constraint_b(M, w, lane))
 FB_STAGE_WRAP(s_sensor_acc, d_sensor_acc(M, w, lane))
 FB_STAGE_WRAP(s_integrate, d_integrate(M, w, lane))
@@ -399,12 +430,6 @@ template <typename real> FB_STAGE_C void s_pre(const DevModel<real>& M_, const W
 template <typename real> FB_STAGE_C void s_post(const DevModel<real>& M_, const WS<real>& w_, bool resetting, float* obs, float* reward, float* discount, int* step_type, int lane) {
   const DevModel<real>& M = as_constant(M_); const WS<real> w = ws_uniform(w_, M);
   // The flag and the environment's output rows are wave-uniform like the descriptor: SGPRs (otherwise the 12-per-CU FP64 build spills more than 503b35d's s_post did).
-  // d_run's registers around a stage call are allocated from what the stage clobbers: the registers 503b35d's s_post used and this one does not are declared clobbered,
-  // so that every step kernel keeps that commit's code (profiles/isa_task_hooks.txt; nothing is emitted).  Drop them with the next change that re-measures the step kernels.
-#ifndef FB_EMULATE
-  if constexpr (sizeof(real) == 4) asm volatile("" ::: "s64", "s65", "s66", "s67", "s68", "s69", "v45", "v46", "v47", "v56", "v57", "v58");
-  else if (!FB_F64_DENSE) asm volatile("" ::: "v186", "v187", "v188", "v189");
-#endif
   d_task_post(M, w, uniform_int(resetting) != 0, uniform_p(obs), uniform_p(reward), uniform_p(discount), uniform_p(step_type), lane); }
 
 // tk < 0: the whole call (all substeps of a control step, or what `mode` says).  tk >= 0: ONE substep of a control step handed out by
@@ -414,18 +439,25 @@ template <typename real> FB_STAGE_C void s_post(const DevModel<real>& M_, const 
 // LDS-resident is alive at that boundary -- the factor of M is dead, the right-hand side of the Euler solve is assembled from the global row --
 // so the two halves may run on different waves (k_fly hands the last substeps of a step out in halves).
 // Returns true when the call was an auto-reset (the step is complete then).
-// FORCES (k_step_forces): qfrc_app / xfrc_app = the environment's rows of the applied-force arrays (fb_forces.hpp); every substep and a forward
-// evaluation read them, the forward pass of a reset does not.
-// LAW (k_step_law): law_coef / law_qadr / law_out = the environment's coefficient block, the qpos addresses and its row of FB_QFRC_LAW
-// (fb_law.hpp); read and written where the forces are read, zeroed by the forward pass of a reset.
-template <typename real, bool FORCES = false, bool LAW = false>
-__device__ __forceinline__ bool d_run(const DevModel<real>& M, const WS<real>& w, int env, int mode, int nsub_arg, int nslot, int* sched, const float* action,
-                      float* obs, float* reward, float* discount, int* step_type, int lane, int tk = -1, int only = -1,
-                      const real* qfrc_app = nullptr, const real* xfrc_app = nullptr,
-                      const real* law_coef = nullptr, const int* law_qadr = nullptr, real* law_out = nullptr) {
+// io: a callable that returns the step's StepIO (fb_types.hpp) -- the action, the output rows and, for the kernels that have them, the environment's rows of the applied-force arrays
+// (FORCES, k_step_forces, fb_forces.hpp: every substep and a forward evaluation read them, the forward pass of a reset does not) and its
+// coefficient block, the qpos addresses and its row of FB_QFRC_LAW (LAW, k_step_law, fb_law.hpp: read and written where the forces are read,
+// zeroed by the forward pass of a reset).
+//
+// The interpreter keeps NO descriptor of its own: `wc` (a copy of the caller's descriptor, in memory) is handed to the stages by reference,
+// the rows of `io` are formed where a stage that takes them is called, and every pass over the environment's data sits inside a stage -- the right-hand sides of the two solves in d_factor, the
+// qacc_smooth copy in s_project_constraint, the sensor accumulation and the progress count in s_velocity, the zero fill of a reset's pass in
+// s_actuation_zero.  Code that ran inline between the calls kept the descriptor's pointers alive across EVERY call, in scalar registers the
+// kernel does not have: they were saved to vector lanes, and those to scratch, around each stage.
+template <typename real, bool FORCES = false, bool LAW = false, typename IO>
+__device__ __forceinline__ bool d_run(const DevModel<real>& M, const WS<real>& wc, const IO& io, int env, int mode, int nsub_arg, int nslot, int* sched,
+                      int lane, int tk = -1, int only = -1) {
   // every selector of the stage machine is wave-uniform: say so (v_readfirstlane), otherwise the interpreter's state lives in
   // VGPRs + saved exec masks across every stage call and counts against the register budget of all stages
   mode = uniform_int(mode); nsub_arg = uniform_int(nsub_arg); tk = uniform_int(tk); only = uniform_int(only);
+#if defined(FB_PROFILE) && !defined(FB_EMULATE)
+  const WS<real> w = ws_uniform(wc, M);          // (the PROF() markers add to the environment's counters)
+#endif
   const bool tk_first = tk < 0 || (tk & 1), tk_last = tk < 0 || (tk & 2), tk_half_a = tk >= 0 && (tk & 4), tk_half_b = tk >= 0 && (tk & 8);
   // Round 6 (+0.5 %, profiles/r6/ab_stage_priority.txt): issue priority by STAGE CLASS.  The stages that are chains of memory round trips with a few hundred
   // instructions between them (actuation, factorisations, solves, sensors, integration, kinematics, inertias, constraint rows, velocities) run at
@@ -434,19 +466,18 @@ __device__ __forceinline__ bool d_run(const DevModel<real>& M, const WS<real>& w
 #define ST_LAT() FB_SETPRIO(base_prio_ > FB_LAT_PRIO ? base_prio_ : FB_LAT_PRIO)
 #define ST_ISS() FB_SETPRIO(base_prio_)
   int parts = 15;
-  bool resetting = (mode == MODE_RESET) || (mode == MODE_STEP && tk_first && uniform_int(w.istate()[IS_RESET_NEXT]) != 0);
+  bool resetting = (mode == MODE_RESET) || (mode == MODE_STEP && tk_first && uniform_int(ws_uniform(wc, M).istate()[IS_RESET_NEXT]) != 0);
   bool env_logic = (mode == MODE_STEP) || (mode == MODE_RESET);
   bool actuate = true, damp = false, half = false;
   int nsub = uniform_int(tk >= 0 ? 1 : ((mode == MODE_SUBSTEP) ? nsub_arg : M.nsubstep)), sub = 0;
   int pc, ret = ST_DONE, fret = ST_DONE;
-  const WS<real> wc = w;                  // the stages are separate functions: they read this copy, `w` itself stays in registers
   if (only >= 0) {
     // one stage of a control step (profiling): the host walks the stage sequence of d_run itself
     resetting = false; env_logic = true; nsub = 1;
     damp = (only >> 8) & 1; half = (only >> 9) & 1; parts = (only >> 12) & 15; if (parts == 0) parts = 15;
     pc = only & 0xff;
-    if (pc == ST_PRE) { s_pre(M, wc, action, lane); return false; }
-    if (pc == ST_POST) { s_post(M, wc, false, obs, reward, discount, step_type, lane); return false; }
+    if (pc == ST_PRE) { s_pre(M, wc, io().action, lane); return false; }
+    if (pc == ST_POST) { const StepIO<real> o = io(); s_post(M, wc, false, o.obs, o.reward, o.discount, o.step_type, lane); return false; }
   } else
   if (resetting) {
     s_init(M, wc, env, lane);
@@ -455,7 +486,7 @@ __device__ __forceinline__ bool d_run(const DevModel<real>& M, const WS<real>& w
     pc = ST_KIN;
   } else {
     PROF_BEGIN();
-    if (mode == MODE_STEP && tk_first) s_pre(M, wc, action, lane);
+    if (mode == MODE_STEP && tk_first) s_pre(M, wc, io().action, lane);
     PROF(27);
     pc = (nsub > 0) ? (tk_half_b ? ST_EULER_PRE : ST_ACT) : ST_DONE;
   }
@@ -467,11 +498,7 @@ __device__ __forceinline__ bool d_run(const DevModel<real>& M, const WS<real>& w
         PROF_BEGIN();
         ST_LAT();
         if (actuate) s_actuation(M, wc, lane);      // (leaves qfrc_actuator in the solve vector lx as well as in the global row)
-        else {
-          for (int i = lane; i < M.nv; i += FB_WAVE) { w.qfrc_actuator()[i] = 0; w.lx()[i] = 0; }
-          for (int i = lane; i < M.na; i += FB_WAVE) w.act_dot()[i] = 0;
-          SYNC();
-        }
+        else s_actuation_zero(M, wc, lane);
         PROF(P_ACT);
         pc = ST_ACC_PRE; break; }
       case ST_ACC_PRE: {
@@ -479,36 +506,22 @@ __device__ __forceinline__ bool d_run(const DevModel<real>& M, const WS<real>& w
         // now, and the factorisation carries it along (d_factor: x leaves as L^-T x), so the solve is its root-to-leaf half
         // only.  The constraint projection, the factor's first consumer, follows.  Nothing LDS-resident crosses a launch
         // boundary any more (the factor and the Delassus matrix used to be parked in the global row between control steps).
-        PROF_BEGIN();
-        if constexpr (LAW) {                                                                               // lx (= this substep's qfrc_actuator) += u, FB_QFRC_LAW = u
-          if (!resetting) s_control_law(M, wc, law_coef, law_qadr, law_out, lane);
-          else for (int i = lane; i < M.nv; i += FB_WAVE) law_out[i] = 0;
-        }
-        if constexpr (FORCES) { if (!resetting) s_applied_forces(M, wc, qfrc_app, xfrc_app, lane); }      // lx += qfrc_applied + J' xfrc_applied
-        for (int i = lane; i < M.nv; i += FB_WAVE) {
-          real f = w.qfrc_passive()[i] - w.qfrc_bias()[i] + w.lx()[i];          // lx = qfrc_actuator (assembled there by ST_ACT)
-          w.qfrc_smooth()[i] = f; w.lx()[i] = f;
-        }
-        SYNC();
-        PROF(24);
+        // (qfrc_smooth = lx = qfrc_passive - qfrc_bias + lx is the first thing that factorisation does: d_factor, damp = false)
+        if constexpr (LAW) { const StepIO<real> o = io(); s_control_law(M, wc, o.law_coef, o.law_qadr, o.law_out, resetting, lane); }                                    // lx (= this substep's qfrc_actuator) += u, FB_QFRC_LAW = u (a reset: zeroed)
+        if constexpr (FORCES) { if (!resetting) { const StepIO<real> o = io(); s_applied_forces(M, wc, o.qfrc_app, o.xfrc_app, lane); } }                     // lx += qfrc_applied + J' xfrc_applied
         damp = false; fret = ST_ACC_SOLVE; pc = ST_FACTOR; break; }
       case ST_ACC_SOLVE:
         half = true; ret = ST_ACC_POST; pc = ST_SOLVE; break;
       case ST_SOLVE: {
         PROF_BEGIN();
-        d_solve(M, wc, w.lLD, w.lx(), half, lane);
+        d_solve(M, wc, half, lane);
         PROF(P_ACC);
         half = false;
         pc = ret; break; }
       case ST_ACC_POST: {
         PROF_BEGIN();
-        if (parts & 1) {
-          for (int i = lane; i < M.nv; i += FB_WAVE) w.qacc_smooth()[i] = w.lx()[i];
-          SYNC();
-        }
-        PROF(24);
         ST_ISS();
-        if (parts & 2) s_project_constraint(M, wc, lane);
+        s_project_constraint(M, wc, parts & 3, lane);               // (qacc_smooth = lx first)
         PROF(P_PROJ);
         pc = ST_CONSTR_A; break; }
       case ST_CONSTR_A: {
@@ -522,20 +535,17 @@ __device__ __forceinline__ bool d_run(const DevModel<real>& M, const WS<real>& w
         pc = ST_SENS; break; }
       case ST_SENS: {
         PROF_BEGIN();
-        if constexpr (FORCES) s_sensor_acc_forces(M, wc, resetting ? (const real*)nullptr : xfrc_app, lane);
+        if constexpr (FORCES) s_sensor_acc_forces(M, wc, resetting ? (const real*)nullptr : io().xfrc_app, lane);
         else s_sensor_acc(M, wc, lane);
         PROF(P_SENS);
         pc = (single_pass || tk_half_a) ? ST_DONE : ST_EULER_PRE; break; }
       case ST_EULER_PRE: {
         // the factor of M is dead after the constraint solve: its LDS slot is reused for M + h*D
-        PROF_BEGIN();
-        for (int i = lane; i < M.nv; i += FB_WAVE) w.lx()[i] = w.qfrc_smooth()[i] + w.qfrc_constraint()[i];
-        SYNC();
-        PROF(24);
+        // (lx = qfrc_smooth + qfrc_constraint is the first thing that factorisation does: d_factor, damp = true)
         damp = true; fret = ST_EULER_SOLVE; pc = ST_FACTOR; break; }
       case ST_FACTOR: {
         PROF_BEGIN();
-        d_factor(M, wc, (const FB_GLOBAL real*)w.qM(), damp ? M.dof_damping.p : (const FB_GLOBAL real*)nullptr, damp ? M.timestep : (real)0, w.lLD, w.lx(), lane);
+        d_factor(M, wc, damp, lane);
         PROF(P_FACTOR);
         pc = fret; break; }
       case ST_EULER_SOLVE:
@@ -562,25 +572,19 @@ __device__ __forceinline__ bool d_run(const DevModel<real>& M, const WS<real>& w
         ST_LAT();
         if (parts & 2) s_make_constraint(M, wc, lane);
         PROF(P_MAKEC);
-        if (parts & 4) s_velocity(M, wc, lane);
+        // The stage closes the substep (s_velocity): the sensors go to the control step's accumulators, and -- tail-aware issue priority --
+        // the launch ends when its slowest environment ends, and every environment is resident from the start, so a wave that trails
+        // the others is on the critical path.  Each wave counts itself into the substep's progress counter; the more waves were there
+        // before it, the higher its priority for the next substep.
+        if (parts & 4) {
+          const bool closes = !single_pass;
+          const int prio = uniform_int(s_velocity(M, wc, closes && env_logic, (closes && sched && sub < FB_NSCHED) ? sched + sub : (int*)nullptr, nslot, lane));
+          if (prio >= 0) FB_SETPRIO(prio);
+        }
         PROF(P_VEL);
         pc = single_pass ? ST_ACT : ST_SUBEND; break; }
       case ST_SUBEND: {
-        PROF_BEGIN();
-        if (env_logic) { if (lane < FB_NSENS) w.sens_acc()[lane] += w.sens()[lane]; SYNC(); }
-        // Tail-aware issue priority.  The launch ends when its slowest environment ends, and every environment is resident
-        // from the start, so a wave that trails the others is on the critical path.  Each wave counts itself into the
-        // substep's progress counter; the more waves were there before it, the higher its priority for the next substep.
-        if (sched && sub < FB_NSCHED) {
-          int before = 0;
-          if (lane == 0) before = atomicAdd(sched + sub, 1);
-          before = uniform_int(before);
-          int prio = (32*before < FB_PRIO_T1*nslot) ? 0 : (32*before < FB_PRIO_T2*nslot ? 1 : (32*before < FB_PRIO_T3*nslot ? 2 : 3));
-          if (lane == 0) w.istate()[IS_PRIO] = prio;
-          FB_SETPRIO(prio);
-        }
         sub++;
-        PROF(26);
         pc = (sub < nsub) ? ST_ACT : ST_DONE; break; }
       default: pc = ST_DONE;
     }
@@ -588,7 +592,7 @@ __device__ __forceinline__ bool d_run(const DevModel<real>& M, const WS<real>& w
   }
   if (only >= 0) return false;
   PROF_BEGIN();
-  if (env_logic && (tk_last || resetting)) s_post(M, wc, resetting, obs, reward, discount, step_type, lane);
+  if (env_logic && (tk_last || resetting)) { const StepIO<real> o = io(); s_post(M, wc, resetting, o.obs, o.reward, o.discount, o.step_type, lane); }
   PROF(28);
   return resetting;
 }

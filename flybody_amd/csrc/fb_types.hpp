@@ -271,3 +271,14 @@ struct WS {
   FB_WS_INT(X)
 #undef X
 };
+
+// What a control step reads and writes OUTSIDE the environment's row: the action, the output rows, and the rows of the applied-force and
+// control-law arrays (null where the kernel has none).  Two or three stage calls per control step need them: the interpreter (fb_step.hpp:
+// d_run) gets a callable that FORMS them from the kernel's arguments and the environment id where such a call is made, instead of ten
+// pointers that would sit in its registers across every stage call.
+template <typename real>
+struct StepIO {
+  const float* action; float* obs; float* reward; float* discount; int* step_type;
+  const real* qfrc_app; const real* xfrc_app;                           // fb_forces.hpp
+  const real* law_coef; const int* law_qadr; real* law_out;             // fb_law.hpp
+};

@@ -54,7 +54,8 @@ ST = dict(ACT=0, ACC_PRE=1, SOLVE=2, ACC_SOLVE=3, ACC_POST=4, CONSTR_A=5, CONSTR
 
 def stage_sequence(nsubstep: int):
     """[(name, stage word)] of one control step: the task's before_step hook, `nsubstep` x (mj_step2, integration, mj_step1 in
-    dm_control's legacy order, fb_step.hpp d_run), the task's after_step hook."""
+    dm_control's legacy order, fb_step.hpp d_run), the task's after_step hook.  smooth_rhs / euler_rhs / substep_end keep their places in the
+    walk, but the passes they were named after run inside factor_M / factor_M_hD / velocity (tools/stage_profile.py)."""
     DAMP, HALF, P = 1 << 8, 1 << 9, lambda m: m << 12
     sub = [('actuation', ST['ACT']), ('smooth_rhs', ST['ACC_PRE']), ('factor_M', ST['FACTOR']), ('solve_smooth', ST['SOLVE'] | HALF),
            ('qacc_smooth_copy', ST['ACC_POST'] | P(1)), ('project_constraint', ST['ACC_POST'] | P(2)), ('constraint_solve', ST['CONSTR_A']),

@@ -12,6 +12,16 @@ Two halves:
               share of FP64 arithmetic instructions, wave-cycles and wait share, bytes fetched / written, and the ISA-level scratch
               instruction count of the stage function (tools/resource_report.py).
 
+Attribution of the small passes since the stage machine keeps no descriptor of its own (fb_step.hpp: d_run): they run INSIDE the stage that
+consumes or produces their data, so their counters are that stage's --
+  the right-hand side of the smooth solve (qfrc_smooth = lx = passive - bias + lx)   -> factor_M      (was smooth_rhs)
+  the right-hand side of the Euler solve (lx = qfrc_smooth + qfrc_constraint)        -> factor_M_hD   (was euler_rhs)
+  the sensor accumulation and the progress count / IS_PRIO of the substep scheduler  -> velocity      (was substep_end)
+  the zero fill of a reset's pass without controls                                   -> actuation (s_actuation_zero)
+smooth_rhs now holds the control-law and applied-force stages only (nothing for k_fly), euler_rhs and substep_end launch an empty stage;
+qacc_smooth_copy is still a launch of its own (the copy at the head of s_project_constraint, part mask 1).  Tables older than this note
+have the passes under their old names.
+
   python tools/stage_profile.py run OUT_DIR [--envs 4096] [--steps 2] [--dense]
   python tools/stage_profile.py report OUT_DIR [--dense] > profiles/r4/stage_lanes.txt
 """
