@@ -8,6 +8,8 @@
 #include <hip/hip_runtime.h>
 #endif
 #include <algorithm>
+#include <array>
+#include <climits>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -576,6 +578,43 @@ __device__ __forceinline__ const DevModel<real>& model_of_env(const DevModel<rea
   } else { (void)Mp; (void)G; (void)env; bad = false; return M0; }
 }
 
+// The rows of one environment's step (StepIO, fb_types.hpp), formed from the kernel's arguments: action and outputs, FORCES: the two force
+// rows, LAW: the law's rows.  The sizes are those of the launch's model M (element 0 of a group: its models agree in them).
+template <typename real, bool FORCES, bool LAW>
+__device__ __forceinline__ StepIO<real> step_io(const DevModel<real>& M, const Batch<real>& B, const float* action, const ForceArgs<real>& F, const LawArgs<real>& L, int env) {
+  StepIO<real> o = {action ? action + (size_t)env*M.nact : nullptr, B.obs ? B.obs + (size_t)env*B.nobs : nullptr, B.reward + env, B.discount + env, B.step_type + env,
+                    nullptr, nullptr, nullptr, nullptr, nullptr};
+  if constexpr (FORCES) { o.qfrc_app = F.qfrc_applied + (size_t)env*M.nv; o.xfrc_app = F.xfrc_applied + (size_t)env*6*M.nbody; }
+  if constexpr (LAW) { o.law_coef = L.coef + (L.per_env ? (size_t)env*LAW_NROW*M.nv : (size_t)0); o.law_qadr = L.qadr; o.law_out = L.out + (size_t)env*M.nv; }
+  return o;
+}
+
+// An environment of a grouped batch whose model id was out of range (model_of_env: `bad`) was stepped with the clamped id: say so.
+template <typename real>
+__device__ __forceinline__ void flag_bad_model(const DevModel<real>& Me, const WS<real>& wc, bool bad_id, int lane) {
+  if (bad_id && lane == 0) { int* is_ = ws_uniform(wc, Me).istate(); atomicOr(is_ + IS_WARN, (int)WARN_MODEL_ID); atomicOr(is_ + IS_WARN_EVER, (int)WARN_MODEL_ID); }
+}
+
+// The substep scheduler's counter of an environment's completed units (fly_kernel), read and published past the vector L1: a relaxed
+// agent-scope load by lane 0, broadcast to the wave (d: the caller's last value, what the other lanes pass in -- starting them from zero
+// here moves every step kernel's code), and a relaxed agent-scope atomic MAX.  Neither orders anything: acquire and release are in the
+// protocol's text.  (Host emulation: plain memory.)
+__device__ __forceinline__ int done_load(const int* done, int lane, int d) {
+#ifndef FB_EMULATE
+  if (lane == 0) d = __hip_atomic_load(done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#else
+  if (lane == 0) d = *done;
+#endif
+  return uniform_int(__shfl(d, 0, FB_WAVE));
+}
+__device__ __forceinline__ void done_publish_max(int* done, int v) {
+#ifndef FB_EMULATE
+  __hip_atomic_fetch_max(done, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#else
+  *done = max(*done, v);
+#endif
+}
+
 // FORCES: the step kernel with applied forces (k_step_forces; F = the batch's two force arrays, fb_forces.hpp).  k_fly and k_fly_reset instantiate it false.
 // MODELS: the kernels of a grouped batch (k_group_step, k_group_reset; G = the assignment).  The workgroup's LDS tables and the launch-wide
 // quantities (substep count, dimensions, workspace layout) come from element 0 -- the models of a group agree in all of them -- and the
@@ -643,12 +682,7 @@ __device__ __forceinline__ void fly_kernel(const DevModel<real>* Mp, const Batch
       const long long tw0_ = wall_clock64();
 #endif
       for (int spins = 0; spins < FB_SCHED_SPIN_CAP; spins++) {
-#ifndef FB_EMULATE
-        if (lane == 0) d = __hip_atomic_load(B.done + env, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#else
-        if (lane == 0) d = B.done[env];
-#endif
-        d = uniform_int(__shfl(d, 0, FB_WAVE));
+        d = done_load(B.done + env, lane, d);
         if (d >= round) break;
         late = 3;
 #ifndef FB_EMULATE
@@ -668,11 +702,7 @@ __device__ __forceinline__ void fly_kernel(const DevModel<real>* Mp, const Batch
           // ticket of this environment is skipped at once (d > round) instead of spinning to the cap again.)
           atomicOr(is_ + IS_WARN, WARN_SCHED_WAIT); atomicOr(is_ + IS_WARN_EVER, WARN_SCHED_WAIT);
           atomicAdd(B.sched_err, 1);
-#ifndef FB_EMULATE
-          __hip_atomic_fetch_max(B.done + env, nunit + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#else
-          B.done[env] = max(B.done[env], nunit + 2);
-#endif
+          done_publish_max(B.done + env, nunit + 2);
         }
         continue;
       }
@@ -696,19 +726,10 @@ __device__ __forceinline__ void fly_kernel(const DevModel<real>* Mp, const Batch
       // the stages read a copy of the descriptor, by reference, and the step's rows are formed where a stage takes them: neither stays in
       // registers across the stage calls (fb_step.hpp: d_run)
       const WS<real> wc = w;
-      auto io = [&]() {
-        StepIO<real> o = {action ? action + (size_t)env*M.nact : nullptr, B.obs ? B.obs + (size_t)env*B.nobs : nullptr, B.reward + env, B.discount + env, B.step_type + env,
-                          nullptr, nullptr, nullptr, nullptr, nullptr};
-        if constexpr (FORCES) { o.qfrc_app = F.qfrc_applied + (size_t)env*M.nv; o.xfrc_app = F.xfrc_applied + (size_t)env*6*M.nbody; }
-        if constexpr (LAW) { o.law_coef = L.coef + (L.per_env ? (size_t)env*LAW_NROW*M.nv : (size_t)0); o.law_qadr = L.qadr; o.law_out = L.out + (size_t)env*M.nv; }
-        return o;
-      };
+      auto io = [&]() { return step_io<real, FORCES, LAW>(M, B, action, F, L, env); };
       const bool was_reset = d_run<real, FORCES, LAW>(Me, wc, io, env, mode, nsub, nslot, (int*)nullptr, lane,
                                    (round == 0 ? 1 : 0) | (round == nunit - 1 ? 2 : 0) | (tkhalf == 1 ? 4 : 0) | (tkhalf == 2 ? 8 : 0) | (late ? 16 : 0), -1);
-      if constexpr (MODELS) {
-        if (bad_id && lane == 0) { int* is_ = ws_uniform(wc, Me).istate(); atomicOr(is_ + IS_WARN, (int)WARN_MODEL_ID); atomicOr(is_ + IS_WARN_EVER, (int)WARN_MODEL_ID); }
-      }
-#ifndef FB_EMULATE
+      if constexpr (MODELS) flag_bad_model(Me, wc, bad_id, lane);
       // Release.  What the next holder of this environment (a wave of the SAME XCD: environments are bound to XCDs) must see is this
       // wave's global stores.  On gfx942 / gfx950 the vector L1 is write-through and an XCD has ONE L2, so "visible to the XCD" =
       // "acknowledged by the L2" = vmcnt(0); the workgroup-scope release fence keeps the compiler from sinking stores below it, the
@@ -716,19 +737,18 @@ __device__ __forceinline__ void fly_kernel(const DevModel<real>* Mp, const Batch
       // buffer_wbl2: a write-back of the WHOLE L2 to memory per ticket, for readers (other XCDs) that by construction do not
       // exist.  The hardware facts this leans on are checked where they can be (fb_batch_create: architecture, all XCDs visible;
       // launch: the stream reaches every XCD) and the scheduler is switched off otherwise.
-#ifdef FB_PROFILE
+#if defined(FB_PROFILE) && !defined(FB_EMULATE)
       if (lane == 0) {
         long long* pp_ = (long long*)ws_uniform(wc, Me).prof(); const long long tw2_ = wall_clock64();
         if (round == 0) { pp_[52] = 0; pp_[53] = tw0_; pp_[55] = 0; }
         pp_[52] += tw1_ - tw0_; pp_[54] = tw2_; pp_[55] += tw2_ - tw1_;
       }
 #endif
+#ifndef FB_EMULATE
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
       asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-      if (lane == 0) __hip_atomic_fetch_max(B.done + env, was_reset ? nunit + 1 : round + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // (MAX: an abandon mark stays)
-#else
-      if (lane == 0) B.done[env] = max(B.done[env], was_reset ? nunit + 1 : round + 1);
 #endif
+      if (lane == 0) done_publish_max(B.done + env, was_reset ? nunit + 1 : round + 1);      // (MAX: an abandon mark stays)
     }
     return;
   }
@@ -752,17 +772,9 @@ __device__ __forceinline__ void fly_kernel(const DevModel<real>* Mp, const Batch
     SYNC();
   } else if (lane == 0) { w.istate()[IS_PRIO] = 0; if (mode == MODE_STEP || mode == MODE_RESET) w.istate()[IS_WARN] = 0; }
   const WS<real> wc = w;                  // (as on the ticket path: the stages' copy of the descriptor, the step's rows formed where they are used)
-  auto io = [&]() {
-    StepIO<real> o = {action ? action + (size_t)env*M.nact : nullptr, B.obs ? B.obs + (size_t)env*B.nobs : nullptr, B.reward + env, B.discount + env, B.step_type + env,
-                      nullptr, nullptr, nullptr, nullptr, nullptr};
-    if constexpr (FORCES) { o.qfrc_app = F.qfrc_applied + (size_t)env*M.nv; o.xfrc_app = F.xfrc_applied + (size_t)env*6*M.nbody; }
-    if constexpr (LAW) { o.law_coef = L.coef + (L.per_env ? (size_t)env*LAW_NROW*M.nv : (size_t)0); o.law_qadr = L.qadr; o.law_out = L.out + (size_t)env*M.nv; }
-    return o;
-  };
+  auto io = [&]() { return step_io<real, FORCES, LAW>(M, B, action, F, L, env); };
   d_run<real, FORCES, LAW>(Me, wc, io, env, only >= 0 ? (int)MODE_STEP : mode, nsub, nslot, only >= 0 ? (int*)nullptr : B.sched, lane, -1, only);
-  if constexpr (MODELS) {
-    if (bad_id && lane == 0) { int* is_ = ws_uniform(wc, Me).istate(); atomicOr(is_ + IS_WARN, (int)WARN_MODEL_ID); atomicOr(is_ + IS_WARN_EVER, (int)WARN_MODEL_ID); }
-  }
+  if constexpr (MODELS) flag_bad_model(Me, wc, bad_id, lane);
   if (only >= 0) {
     SYNC();
     FB_GLOBAL real* pk = (FB_GLOBAL real*)(B.park + (size_t)env*LdsCfg<real>::POOL);
@@ -786,29 +798,24 @@ __device__ __forceinline__ void fly_kernel(const DevModel<real>* Mp, const Batch
 // The kernels proper.  k_fly: control steps, forward passes and single stages.  k_fly_reset: the (partial) resets of fb_batch_reset under a
 // name of their own -- same device code with the mode folded in -- so that a kernel trace of k_fly holds control steps only (the staggered
 // pre-roll of bench.py resets 1/235 of the batch between any two steps: 236 short launches that used to be averaged into the step kernel).
-template <typename real>
-__global__ void __launch_bounds__(FB_WAVE*LdsCfg<real>::EPB, LdsCfg<real>::WAVES_PER_SIMD) k_fly(const DevModel<real>* Mp, Batch<real> B, const float* action, const int* env_ids, int mode, int nsub, int nslot) {
-  fly_kernel<real>(Mp, B, action, env_ids, mode, nsub, nslot);
-}
-template <typename real>
-__global__ void __launch_bounds__(FB_WAVE*LdsCfg<real>::EPB, LdsCfg<real>::WAVES_PER_SIMD) k_fly_reset(const DevModel<real>* Mp, Batch<real> B, const int* env_ids, int nsub, int nslot) {
-  fly_kernel<real>(Mp, B, nullptr, env_ids, (int)MODE_RESET, nsub, nslot);
-}
+// Every step kernel runs under the same launch bounds (one wave per environment on k_fly's LDS layout: the residency batch_create_impl and
+// launch_fly count on) and begins with the same arguments, a feature's own behind them; the reset kernels take neither action nor mode.
+#define FB_STEP_KERNEL __global__ void __launch_bounds__(FB_WAVE*LdsCfg<real>::EPB, LdsCfg<real>::WAVES_PER_SIMD)
+#define FB_STEP_PARAMS const DevModel<real>* Mp, Batch<real> B, const float* action, const int* env_ids, int mode, int nsub, int nslot
+#define FB_STEP_ARGS Mp, B, action, env_ids, mode, nsub, nslot
+#define FB_RESET_PARAMS const DevModel<real>* Mp, Batch<real> B, const int* env_ids, int nsub, int nslot
+#define FB_RESET_ARGS Mp, B, nullptr, env_ids, (int)MODE_RESET, nsub, nslot
+template <typename real> FB_STEP_KERNEL k_fly(FB_STEP_PARAMS) { fly_kernel<real>(FB_STEP_ARGS); }
+template <typename real> FB_STEP_KERNEL k_fly_reset(FB_RESET_PARAMS) { fly_kernel<real>(FB_RESET_ARGS); }
 
 // The step kernel with external forces (fb_forces.hpp): the same device code with the applied-force stage compiled in, under k_fly's launch bounds
 // and on its LDS layout, ticket scheduler included.  The two arrays are an extra kernel argument, so k_fly's own arguments stay where they are.
 // launch() uses it for control steps, substeps and forward evaluations while the batch's force arrays are allocated.
-template <typename real>
-__global__ void __launch_bounds__(FB_WAVE*LdsCfg<real>::EPB, LdsCfg<real>::WAVES_PER_SIMD) k_step_forces(const DevModel<real>* Mp, Batch<real> B, const float* action, const int* env_ids, int mode, int nsub, int nslot, ForceArgs<real> F) {
-  fly_kernel<real, true>(Mp, B, action, env_ids, mode, nsub, nslot, F);
-}
+template <typename real> FB_STEP_KERNEL k_step_forces(FB_STEP_PARAMS, ForceArgs<real> F) { fly_kernel<real, true>(FB_STEP_ARGS, F); }
 
 // The step kernel with a substep control law (fb_law.hpp): the forces kernel with the law stage compiled in as well -- setting a law allocates
 // the force arrays -- under k_fly's launch bounds and on its LDS layout, ticket scheduler included.  The law is one more kernel argument.
-template <typename real>
-__global__ void __launch_bounds__(FB_WAVE*LdsCfg<real>::EPB, LdsCfg<real>::WAVES_PER_SIMD) k_step_law(const DevModel<real>* Mp, Batch<real> B, const float* action, const int* env_ids, int mode, int nsub, int nslot, ForceArgs<real> F, LawArgs<real> L) {
-  fly_kernel<real, true, false, true>(Mp, B, action, env_ids, mode, nsub, nslot, F, GroupArgs(), L);
-}
+template <typename real> FB_STEP_KERNEL k_step_law(FB_STEP_PARAMS, ForceArgs<real> F, LawArgs<real> L) { fly_kernel<real, true, false, true>(FB_STEP_ARGS, F, GroupArgs(), L); }
 
 // Ends episodes from the device (fb_batch_end_episode): one thread per environment.  Where the mask is set and the environment's last
 // step was MID, the step becomes LAST with the caller's discount and the next control step auto-resets the environment, exactly as after a
@@ -835,13 +842,15 @@ __global__ void k_zero_rows(uint32_t* base, const int* ids, int n, unsigned word
 // launch bounds and on its LDS layout, ticket scheduler included; with and without the applied-force stage, and the reset under a name of its
 // own as above.  The assignment is an extra kernel argument.  launch_fly uses them while the batch holds more than one model, so the
 // kernels above keep their arguments and their code.
-template <typename real, bool FORCES>
-__global__ void __launch_bounds__(FB_WAVE*LdsCfg<real>::EPB, LdsCfg<real>::WAVES_PER_SIMD) k_group_step(const DevModel<real>* Mp, Batch<real> B, const float* action, const int* env_ids, int mode, int nsub, int nslot, ForceArgs<real> F, GroupArgs G) {
-  fly_kernel<real, FORCES, true>(Mp, B, action, env_ids, mode, nsub, nslot, F, G);
-}
+template <typename real, bool FORCES> FB_STEP_KERNEL k_group_step(FB_STEP_PARAMS, ForceArgs<real> F, GroupArgs G) { fly_kernel<real, FORCES, true>(FB_STEP_ARGS, F, G); }
+template <typename real> FB_STEP_KERNEL k_group_reset(FB_RESET_PARAMS, GroupArgs G) { fly_kernel<real, false, true>(FB_RESET_ARGS, ForceArgs<real>(), G); }
+
+// The kernels launch_fly chooses among for a control step.  Same launch bounds and LDS layout, so the same residency
+// (tests/test_step_kernel_resources.py); batch_create_impl takes the scheduler's resident-slot count as the minimum over this list all
+// the same.  A new step kernel is one more entry.
 template <typename real>
-__global__ void __launch_bounds__(FB_WAVE*LdsCfg<real>::EPB, LdsCfg<real>::WAVES_PER_SIMD) k_group_reset(const DevModel<real>* Mp, Batch<real> B, const int* env_ids, int nsub, int nslot, GroupArgs G) {
-  fly_kernel<real, false, true>(Mp, B, nullptr, env_ids, (int)MODE_RESET, nsub, nslot, ForceArgs<real>(), G);
+static std::array<const void*, 5> step_kernels() {
+  return {(const void*)k_fly<real>, (const void*)k_step_forces<real>, (const void*)k_step_law<real>, (const void*)k_group_step<real, false>, (const void*)k_group_step<real, true>};
 }
 
 // Launch order for the next control step: environments sorted by the duration of their last step, longest first (counting
@@ -1269,20 +1278,13 @@ static int batch_create_impl(fb_batch* b) {
     hipDeviceProp_t prop; HIPCHK(hipGetDeviceProperties(&prop, b->device));
     if (with_model(b, [&](auto& M) {
           using real = decltype(M.timestep);
-          int nb = 0;
-          HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_fly<real>, FB_WAVE*LdsCfg<real>::EPB, 0));
-          // launch_fly may launch k_step_forces instead (applied forces): same launch bounds and LDS layout, so the same residency
-          // (tests/test_forces_resources.py); the slot count that decides for tickets is the smaller of the two all the same
-          int nbf = 0;
-          HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nbf, k_step_forces<real>, FB_WAVE*LdsCfg<real>::EPB, 0));
-          // ... and the kernels of a grouped batch (k_group_step, k_group_reset: tests/test_model_group_resources.py)
-          int nbg = 0, nbgf = 0;
-          HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nbg, (k_group_step<real, false>), FB_WAVE*LdsCfg<real>::EPB, 0));
-          HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nbgf, (k_group_step<real, true>), FB_WAVE*LdsCfg<real>::EPB, 0));
-          // ... and the kernel of a control law (k_step_law: tests/test_law_resources.py)
-          int nbl = 0;
-          HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nbl, k_step_law<real>, FB_WAVE*LdsCfg<real>::EPB, 0));
-          b->slots = std::min(std::min(std::min(nb, nbf), std::min(nbg, nbgf)), nbl)*prop.multiProcessorCount*LdsCfg<real>::EPB;
+          // launch_fly may launch any kernel of step_kernels(): the slot count that decides for tickets is the smallest of theirs
+          int nb = INT_MAX, nbk = 0;
+          for (const void* k : step_kernels<real>()) {
+            HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nbk, k, FB_WAVE*LdsCfg<real>::EPB, 0));
+            nb = std::min(nb, nbk);
+          }
+          b->slots = nb*prop.multiProcessorCount*LdsCfg<real>::EPB;
           return 0; })) return -1;
     unsigned* dmask; unsigned hmask = 0;
     HIPCHK(hipMalloc((void**)&dmask, sizeof(unsigned))); HIPCHK(hipMemset(dmask, 0, sizeof(unsigned)));
@@ -1463,32 +1465,28 @@ extern "C" int fb_batch_set_flight_dataset(fb_batch* b, const fb_flight_dataset*
   });
 }
 
-// the k_fly / k_fly_reset / k_step_forces / k_step_law launch of launch()
+// the step kernel launch of launch(): one of step_kernels(), or for a reset k_fly_reset / k_group_reset
 template <typename real>
 static void launch_fly(fb_batch* b, int mode, const float* action, const int* ids, int n, int nsub, hipStream_t st, bool tickets, const int* tord) {
   constexpr int EPB = LdsCfg<real>::EPB;
-  const DevModel<real>* dM = (const DevModel<real>*)b->dM;
+  const DevModel<real>* dM = (const DevModel<real>*)b->dM;          // (a grouped batch: the array of the group's model structs)
   Batch<real> B = {(real*)b->rarena, b->iarena, b->obs, b->reward, b->discount, b->step_type, b->n_env, b->nobs, b->use_prio ? b->sched : nullptr, b->cost,
                    tickets ? b->tick : nullptr, b->done, b->nq, b->sched_err, tord, (real*)b->park};
+  const ForceArgs<real> F = {(const real*)b->qfrc_applied, (const real*)b->xfrc_applied};
+  const LawArgs<real> L = {(const real*)b->law_coef, b->law_qadr, (real*)b->law_out, b->law_rows > 1 || b->n_env == 1 ? 1 : 0};
+  const GroupArgs G = {b->env_model, b->n_models()};
+  const dim3 grid((n + EPB - 1)/EPB), block(FB_WAVE*EPB);
+  auto go = [&](auto kernel, auto... args) { hipLaunchKernelGGL(kernel, grid, block, 0, st, dM, B, args...); };
   if (b->n_models() > 1) {
-    // a grouped batch: the kernels that bind the model per environment (dM is the array of the group's model structs)
-    const GroupArgs G = {b->env_model, b->n_models()};
-    const ForceArgs<real> F = {(const real*)b->qfrc_applied, (const real*)b->xfrc_applied};
-    if (mode == MODE_RESET) hipLaunchKernelGGL((k_group_reset<real>), dim3((n + EPB - 1)/EPB), dim3(FB_WAVE*EPB), 0, st, dM, B, ids, nsub, n, G);
-    else if (b->qfrc_applied) hipLaunchKernelGGL((k_group_step<real, true>), dim3((n + EPB - 1)/EPB), dim3(FB_WAVE*EPB), 0, st, dM, B, action, ids, mode, nsub, n, F, G);
-    else hipLaunchKernelGGL((k_group_step<real, false>), dim3((n + EPB - 1)/EPB), dim3(FB_WAVE*EPB), 0, st, dM, B, action, ids, mode, nsub, n, F, G);
+    // a grouped batch: the kernels that bind the model per environment
+    if (mode == MODE_RESET) go(k_group_reset<real>, ids, nsub, n, G);
+    else if (b->qfrc_applied) go(k_group_step<real, true>, action, ids, mode, nsub, n, F, G);
+    else go(k_group_step<real, false>, action, ids, mode, nsub, n, F, G);
   }
-  else if (mode == MODE_RESET) hipLaunchKernelGGL((k_fly_reset<real>), dim3((n + EPB - 1)/EPB), dim3(FB_WAVE*EPB), 0, st, dM, B, ids, nsub, n);
-  else if (b->law_coef) {
-    const ForceArgs<real> F = {(const real*)b->qfrc_applied, (const real*)b->xfrc_applied};
-    const LawArgs<real> L = {(const real*)b->law_coef, b->law_qadr, (real*)b->law_out, b->law_rows > 1 || b->n_env == 1 ? 1 : 0};
-    hipLaunchKernelGGL((k_step_law<real>), dim3((n + EPB - 1)/EPB), dim3(FB_WAVE*EPB), 0, st, dM, B, action, ids, mode, nsub, n, F, L);
-  }
-  else if (b->qfrc_applied) {
-    const ForceArgs<real> F = {(const real*)b->qfrc_applied, (const real*)b->xfrc_applied};
-    hipLaunchKernelGGL((k_step_forces<real>), dim3((n + EPB - 1)/EPB), dim3(FB_WAVE*EPB), 0, st, dM, B, action, ids, mode, nsub, n, F);
-  }
-  else hipLaunchKernelGGL((k_fly<real>), dim3((n + EPB - 1)/EPB), dim3(FB_WAVE*EPB), 0, st, dM, B, action, ids, mode, nsub, n);
+  else if (mode == MODE_RESET) go(k_fly_reset<real>, ids, nsub, n);
+  else if (b->law_coef) go(k_step_law<real>, action, ids, mode, nsub, n, F, L);
+  else if (b->qfrc_applied) go(k_step_forces<real>, action, ids, mode, nsub, n, F);
+  else go(k_fly<real>, action, ids, mode, nsub, n);
 }
 
 static int launch(fb_batch* b, int mode, const float* action, const int* ids, int n, int nsub, void* stream) {

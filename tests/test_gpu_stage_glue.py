@@ -3,7 +3,11 @@ the stage calls sits inside a stage now.  That is a restatement 
 every kernel built from the interpreter must give the PARENT commit's results to the bit.  tests/golden/stage_glue_parent_c197808.npz was
 recorded on an MI355X from libraries built from c197808, with this file's recorder:
 
-    python tests/test_gpu_stage_glue.py LIB,LIB_DENSE OUT        (LIB,LIB_DENSE alone: compare with the committed file, exit status 1 = differs)
+    python tests/test_gpu_stage_glue.py LIB,LIB_DENSE OUT        (LIB,LIB_DENSE alone: compare with the committed files, exit status 1 = differs)
+
+OUT is named like the committed record whose cases are to be recorded (RECORDS).  The second record, step_variants_parent_59dad35.npz, was
+made the same way from libraries built from 59dad35, when the step kernels' rows, model-id flagging, parameter lists and launches were each
+stated once: the variants the first record holds at FP64 only, at FP32, and the grouped kernel with forces.
 
 What the file holds, per case: after the reset and after every control step, REWARD and STEP_TYPE in full and one 64-bit digest PER
 ENVIRONMENT of QPOS, QVEL, ACT and OBS (the words of the row, each times an odd constant of its position, summed modulo 2^64: a change of any one
@@ -18,7 +22,9 @@ Cases (each a few seconds):
                                   k_fly, k_fly_reset, both copies of the interpreter, the auto-reset branch, the last-substep epilogue, the
                                   zero-fill pass of a reset
   forces_64, law_64, group_64     32 environments x 6 steps: k_step_forces (qfrc_applied + xfrc_applied), k_step_law (a per-environment law),
-                                  k_group_step / k_group_reset (two models), the same two schedulers"""
+                                  k_group_step / k_group_reset (two models), the same two schedulers
+  forces_32, law_32, group_32,    (second record) the same at FP32, and a two-model group WITH the forces of forces_64: k_group_step<true>
+  group_forces_64"""
 import os
 import sys
 
@@ -27,6 +33,7 @@ import pytest
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLDEN = os.path.join(HERE, 'golden', 'stage_glue_parent_c197808.npz')
+GOLDEN_VARIANTS = os.path.join(HERE, 'golden', 'step_variants_parent_59dad35.npz')
 pytestmark = pytest.mark.gpu
 
 DIGESTED = ('QPOS', 'QVEL', 'ACT', 'OBS')
@@ -91,19 +98,19 @@ def _plain(lib, precision):
     return _roll(B, 12, seed=3, events={6: _host_reset, 8: _forward})
 
 
-def _small(lib, kind):
+def _small(lib, kind, precision=64):
     from flybody_amd import engine
     from flybody_amd.randomization import vary_model
     from flybody_amd.reference import default_walking_reference
     a = _arrays(); n = 32
     qp, qv = default_walking_reference()
     rng = np.random.default_rng(9)
-    model = engine.Model(a, lib_path=lib) if kind != 'group' else \
+    model = engine.Model(a, lib_path=lib) if 'group' not in kind else \
         engine.ModelGroup([a, vary_model(a, friction_scale=0.5, gain_scale=0.8, damping_scale=1.5)], lib_path=lib)
-    B = engine.Batch(model, n, precision=64)
+    B = engine.Batch(model, n, precision=precision)
     B.set_reference(qp, qv, terminal_com_dist=TERMINAL_COM_DIST)
     nv, nb = len(a['dof_damping']), len(a['body_mass'])
-    if kind == 'forces':
+    if 'forces' in kind:
         w = float(np.sum(a['body_mass']))*9.81
         xf = np.zeros((n, nb, 6)); xf[:, 1:, :3] = rng.normal(size=(n, nb - 1, 3))*w*0.02; xf[:, 1:, 3:] = rng.normal(size=(n, nb - 1, 3))*w*1e-3
         B.set('XFRC_APPLIED', xf.reshape(n, -1)); B.set('QFRC_APPLIED', rng.normal(size=(n, nv))*w*1e-3)
@@ -114,14 +121,19 @@ def _small(lib, kind):
         B.set_control_law(bias=rng.normal(size=(n, nv))*k*0.03, act_gain=rng.uniform(-0.3, 0.3, (n, nv)), pos_gain=rng.uniform(0, k, (n, nv))*hinge,
                           pos_ref=rng.uniform(-0.3, 0.3, (n, nv)), vel_gain=rng.uniform(0, d, (n, nv)))
         assert B.control_law_active
-    if kind == 'group':
+    if 'group' in kind:
         assert B.n_models == 2
     return _roll(B, 6, seed=5, events={3: lambda B_: (B_.reset([1, 2, 30]), {})[1]})
 
 
 # name -> (which library, rollout)
 CASES = {'plain_64': (0, lambda lib: _plain(lib, 64)), 'plain_32': (0, lambda lib: _plain(lib, 32)), 'plain_dense_64': (1, lambda lib: _plain(lib, 64)),
-         'forces_64': (0, lambda lib: _small(lib, 'forces')), 'law_64': (0, lambda lib: _small(lib, 'law')), 'group_64': (0, lambda lib: _small(lib, 'group'))}
+         'forces_64': (0, lambda lib: _small(lib, 'forces')), 'law_64': (0, lambda lib: _small(lib, 'law')), 'group_64': (0, lambda lib: _small(lib, 'group')),
+         'forces_32': (0, lambda lib: _small(lib, 'forces', 32)), 'law_32': (0, lambda lib: _small(lib, 'law', 32)), 'group_32': (0, lambda lib: _small(lib, 'group', 32)),
+         'group_forces_64': (0, lambda lib: _small(lib, 'group_forces'))}
+# committed record -> its cases
+RECORDS = {GOLDEN: ('plain_64', 'plain_32', 'plain_dense_64', 'forces_64', 'law_64', 'group_64'),
+           GOLDEN_VARIANTS: ('forces_32', 'law_32', 'group_32', 'group_forces_64')}
 SCHEDULERS = {'per_wave': {'FB_NO_TICKETS': '1'}, 'tickets': {'FB_TICKET_SLOTS': '1'}}
 
 
@@ -133,9 +145,19 @@ def _run(name, sched, libs, setenv, delenv):
     return fn(libs[which])
 
 
+def _load_records():
+    """{array name: array} of every committed record; the case names are distinct, so the arrays' are."""
+    out = {}
+    for path, names in RECORDS.items():
+        g = np.load(path)
+        assert {k.split('__')[0] for k in g.files} == set(names), path
+        out.update({k: g[k] for k in g.files})
+    return out
+
+
 @pytest.fixture(scope='module')
 def golden():
-    return np.load(GOLDEN)
+    return _load_records()
 
 
 @pytest.mark.parametrize('sched', list(SCHEDULERS))
@@ -143,7 +165,7 @@ def golden():
 def test_rollout_equal_to_the_parent_to_the_bit(golden, name, sched, monkeypatch):
     from flybody_amd import engine
     got = _run(name, sched, (engine.HIP_LIB, engine.HIP_LIB_DENSE), monkeypatch.setenv, lambda v: monkeypatch.delenv(v, raising=False))
-    keys = [k for k in golden.files if k.startswith(name + '__')]
+    keys = [k for k in golden if k.startswith(name + '__')]
     assert sorted(keys) == sorted('%s__%s' % (name, f) for f in got)
     for f, v in got.items():
         g = golden['%s__%s' % (name, f)]
@@ -152,7 +174,7 @@ def test_rollout_equal_to_the_parent_to_the_bit(golden, name, sched, monkeypatch
 
 def test_golden_reaches_the_branches():
     """A record that stops exercising a branch must not pass silently (index 0 of the per-step arrays is the state after the reset)."""
-    golden = np.load(GOLDEN)
+    golden = _load_records()
     for name in CASES:
         t = golden[name + '__STEP_TYPE'][1:, :, 0]
         assert ((t[:-1] == 2) & (t[1:] == 0)).any(), name                      # an episode ends, the next step auto-resets
@@ -168,7 +190,9 @@ if __name__ == '__main__':
     assert len(libs) == 2, 'LIB,LIB_DENSE'
     setenv = os.environ.__setitem__; delenv = lambda v: os.environ.pop(v, None)
     rec, same = {}, True
-    for name in CASES:
+    out = [p for p in RECORDS if len(sys.argv) > 2 and os.path.basename(p) == os.path.basename(sys.argv[2])]
+    assert out or len(sys.argv) == 2, 'OUT is named like one of %s' % [os.path.basename(p) for p in RECORDS]
+    for name in (RECORDS[out[0]] if out else CASES):
         runs = {s: _run(name, s, libs, setenv, delenv) for s in SCHEDULERS}
         for f, v in runs['per_wave'].items():
             if not np.array_equal(v, runs['tickets'][f]): same = False; print('%s: %s differs between the schedulers' % (name, f))
@@ -179,8 +203,8 @@ if __name__ == '__main__':
         np.savez_compressed(sys.argv[2], **rec)
         print('wrote %s: %d arrays, %d bytes' % (sys.argv[2], len(rec), os.path.getsize(sys.argv[2])))
     else:
-        g = np.load(GOLDEN)
-        bad = [k for k in rec if k not in g.files or not np.array_equal(rec[k], g[k])]
-        print('differs from the committed record: %s' % bad if bad else 'equal to the committed record (%d arrays)' % len(rec))
+        g = _load_records()
+        bad = [k for k in rec if k not in g or not np.array_equal(rec[k], g[k])]
+        print('differs from the committed records: %s' % bad if bad else 'equal to the committed records (%d arrays)' % len(rec))
         same = same and not bad
     sys.exit(0 if same else 1)
