@@ -26,6 +26,7 @@ extern "C" { long long fb_stats[64]; }
 #include "fb_step.hpp"
 #include "fb_ik.hpp"
 #include "fb_inverse.hpp"
+#include "fb_deriv.hpp"
 
 static thread_local std::string g_err;
 static int fail(const std::string& s) { g_err = s; return -1; }
@@ -993,6 +994,11 @@ struct fb_batch {
   // batch's precision, qpos addresses [nv]; set = k_step_law steps the batch.  law_owns_forces: the law allocated the force arrays itself (no caller
   // touched them), so clearing the law frees them too and the batch is back on k_fly
   void *law_coef = nullptr, *law_out = nullptr; int* law_qadr = nullptr; int law_rows = 0; bool law_owns_forces = false;
+  // fb_batch_transition_fd (fb_deriv.hpp), allocated on the first call: the pool of scratch rows (one real + one int arena row per resident wave),
+  // the staging buffer of the tickets' raw results (at most FB_FD_STAGING_BYTES, grown as needed), the frames' environments, the counters
+  double* fd_pool_r = nullptr; int* fd_pool_i = nullptr; int fd_slots = 0;
+  double* fd_stage = nullptr; size_t fd_stage_bytes = 0; int* fd_env = nullptr; int fd_env_cap = 0; int* fd_counter = nullptr;
+  std::vector<int> fd_env_host;
 };
 
 template <typename real, typename T, typename P>
@@ -1330,7 +1336,7 @@ extern "C" void fb_batch_destroy(fb_batch* b) {
   if (!b) return;
   (void)hipSetDevice(b->device);
   for (void* p : b->allocs) (void)hipFree(p);
-  void* frees_[] = {b->rarena, b->iarena, b->obs, b->reward, b->discount, b->step_type, b->d_ids, b->sched, b->cost, b->order, b->ref_qpos, b->ref_qvel, b->dM, b->tick, b->done, b->sched_err, b->park, b->probe_word, b->torder, b->ik_err, b->ik_steps, b->ik_buf, b->inv_qfrc, b->inv_cforce, b->qfrc_applied, b->xfrc_applied, b->env_model, b->law_coef, b->law_out, b->law_qadr};
+  void* frees_[] = {b->rarena, b->iarena, b->obs, b->reward, b->discount, b->step_type, b->d_ids, b->sched, b->cost, b->order, b->ref_qpos, b->ref_qvel, b->dM, b->tick, b->done, b->sched_err, b->park, b->probe_word, b->torder, b->ik_err, b->ik_steps, b->ik_buf, b->inv_qfrc, b->inv_cforce, b->qfrc_applied, b->xfrc_applied, b->env_model, b->law_coef, b->law_out, b->law_qadr, b->fd_pool_r, b->fd_pool_i, b->fd_stage, b->fd_env, b->fd_counter};
   for (void* p : frees_) (void)hipFree(p);
 
   if (b->ev0) (void)hipEventDestroy(b->ev0);
@@ -1722,6 +1728,107 @@ extern "C" int fb_batch_inverse(fb_batch* b, int flags, void* stream) {
   HIPCHK(hipGetLastError());
   return 0;
   FB_GUARD_END
+}
+
+// ------------------------------------------------------------------ transition derivatives
+// mjd_transitionFD for the listed environments (fb_deriv.hpp: k_transition_fd draws (frame, column, side) tickets onto a pool of scratch rows,
+// k_fd_assemble forms the quotients).  Like fb_batch_ik / fb_batch_inverse it does not go through launch() and is not a timed launch.  The
+// environments' rows are only read: state, caches, warm start, warnings, size statistics and step ticks stay as they were.
+static int fd_resident_slots(fb_batch* b) {
+  if (b->fd_slots > 0) return 0;
+#ifdef FB_EMULATE
+  b->fd_slots = 8;                                           // (host emulation has no residency: a few rows, so that the tests can vary the pool)
+#else
+  hipDeviceProp_t prop; HIPCHK(hipGetDeviceProperties(&prop, b->device));
+  constexpr int EPB = LdsCfg<double>::EPB;
+  int nbk = 0;
+  HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nbk, (const void*)k_transition_fd<double>, FB_WAVE*EPB, 0));
+  const int own = nbk*prop.multiProcessorCount*EPB;
+  b->fd_slots = std::max(1, b->slots > 0 ? std::min(b->slots, own) : own);
+#endif
+  return 0;
+}
+
+extern "C" int fb_batch_transition_fd(fb_batch* b, const fb_fd_config* cfg, double* A, double* Bm, double* Cm, double* Dm, int32_t* status, void* stream) {
+  if (!b) return fail("fb_batch_transition_fd: null batch");
+  if (!cfg) return fail("fb_batch_transition_fd: null config");
+  if (b->precision != 64) return fail("fb_batch_transition_fd: transition derivatives need an FP64 batch (precision 64)");
+  if (b->n_models() > 1) return fail("fb_batch_transition_fd: per-model derivatives are not supported: this batch is a group of " + std::to_string(b->n_models()) + " models (fb_batch_create_group)");
+  if (b->law_coef) return fail("fb_batch_transition_fd: the derivative kernel knows no control law; call fb_batch_set_control_law(batch, NULL) first");
+  if (b->qfrc_applied) return fail("fb_batch_transition_fd: the derivative kernel knows no applied forces; call fb_batch_clear_forces first");
+  if (!A && !Bm && !Cm && !Dm) return fail("fb_batch_transition_fd: all four outputs are NULL");
+  if (!std::isfinite(cfg->eps) || !(cfg->eps > 0)) return fail("fb_batch_transition_fd: eps must be finite and > 0");
+  if (cfg->n_substeps < 1) return fail("fb_batch_transition_fd: n_substeps must be >= 1");
+  if (cfg->n_frames < 1) return fail("fb_batch_transition_fd: n_frames must be >= 1");
+  if (cfg->centered != 0 && cfg->centered != 1) return fail("fb_batch_transition_fd: centered must be 0 or 1");
+  if (!cfg->env_ids && cfg->n_frames > b->n_env) return fail("fb_batch_transition_fd: environment id out of range (n_frames exceeds the batch and env_ids is NULL)");
+  if (cfg->env_ids) for (int k = 0; k < cfg->n_frames; k++) if (cfg->env_ids[k] < 0 || cfg->env_ids[k] >= b->n_env)
+    return fail("fb_batch_transition_fd: environment id " + std::to_string(cfg->env_ids[k]) + " out of range (frame " + std::to_string(k) + ")");
+  FB_GUARD_BEGIN
+  HIPCHK(hipSetDevice(b->device));
+  if (fd_resident_slots(b)) return -1;
+  if (cfg->pool_rows < 0 || cfg->pool_rows > b->fd_slots) return fail("fb_batch_transition_fd: pool_rows out of range (0, or 1 .. " + std::to_string(b->fd_slots) + " resident slots)");
+  hipStream_t st = (hipStream_t)stream;
+  const fb_model* m = b->m;
+  const int nf = cfg->n_frames, ndx = 2*m->nv + m->na, nst = m->nq + m->nv + m->na + FB_NSENS;
+  const int c0 = (A || Cm) ? 0 : ndx, c1 = (Bm || Dm) ? ndx + m->nu : ndx, sides = cfg->centered ? 2 : 1, per_frame = 1 + sides*(c1 - c0);
+  if (c1 <= c0) return fail("fb_batch_transition_fd: the outputs asked for have no column (a model without controls has no B or D)");
+  if (alloc_zeroed_once(&b->fd_pool_r,(size_t)b->fd_slots*b->off.nreal*sizeof(double)) || alloc_zeroed_once(&b->fd_pool_i, (size_t)b->fd_slots*b->off.nint*sizeof(int)) ||
+      alloc_zeroed_once(&b->fd_counter, 2*sizeof(int))) return -1;
+  // frames per chunk: the tickets' staging slots stay inside the budget
+  const size_t frame_bytes = (size_t)per_frame*nst*sizeof(double);
+  const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)nf, FB_FD_STAGING_BYTES/frame_bytes));
+  if (b->fd_stage_bytes < chunk*frame_bytes || b->fd_env_cap < nf) {
+    HIPCHK(hipDeviceSynchronize());                    // (an earlier call may still use the buffers)
+    if (b->fd_stage_bytes < chunk*frame_bytes) {
+      (void)hipFree(b->fd_stage); b->fd_stage = nullptr; b->fd_stage_bytes = 0;
+      HIPCHK(hipMalloc((void**)&b->fd_stage, chunk*frame_bytes)); b->fd_stage_bytes = chunk*frame_bytes;
+    }
+    if (b->fd_env_cap < nf) {
+      (void)hipFree(b->fd_env); b->fd_env = nullptr; b->fd_env_cap = 0;
+      HIPCHK(hipMalloc((void**)&b->fd_env, (size_t)nf*sizeof(int))); b->fd_env_cap = nf;
+    }
+  }
+  b->fd_env_host.resize(nf);
+  for (int k = 0; k < nf; k++) b->fd_env_host[k] = cfg->env_ids ? cfg->env_ids[k] : k;
+  HIPCHK(hipMemcpyAsync(b->fd_env, b->fd_env_host.data(), (size_t)nf*sizeof(int), hipMemcpyHostToDevice, st));
+  if (sync_model(b)) return -1;
+  if (status) HIPCHK(hipMemsetAsync(status, 0, (size_t)nf*sizeof(int32_t), st));
+  HIPCHK(hipMemsetAsync(b->fd_counter, 0, 2*sizeof(int), st));
+  constexpr int EPB = LdsCfg<double>::EPB;
+  const int pool = cfg->pool_rows > 0 ? cfg->pool_rows : b->fd_slots;
+  for (int lo = 0; lo < nf; lo += chunk) {
+    const int n = std::min(chunk, nf - lo);
+    FdArgs<double> F;
+    F.rarena = (const double*)b->rarena; F.iarena = b->iarena; F.pool_r = b->fd_pool_r; F.pool_i = b->fd_pool_i;
+    F.frame_env = b->fd_env + lo; F.stage = b->fd_stage; F.counter = b->fd_counter; F.status = status ? (int*)status + lo : nullptr;
+    F.A = A ? A + (size_t)lo*ndx*ndx : nullptr; F.B = Bm ? Bm + (size_t)lo*ndx*m->nu : nullptr;
+    F.C = Cm ? Cm + (size_t)lo*FB_NSENS*ndx : nullptr; F.D = Dm ? Dm + (size_t)lo*FB_NSENS*m->nu : nullptr;
+    F.eps = cfg->eps; F.n_frames = n; F.c0 = c0; F.c1 = c1; F.centered = cfg->centered; F.n_substeps = cfg->n_substeps;
+    F.skip_tail = (!Cm && !Dm) ? 1 : 0;
+    const long long tickets = (long long)n*per_frame;
+    F.nwave = (int)std::min<long long>(pool, tickets);
+    if (lo > 0) HIPCHK(hipMemsetAsync(b->fd_counter, 0, sizeof(int), st));      // (the next-ticket word; the run count goes on)
+    hipLaunchKernelGGL((k_transition_fd<double>), dim3((F.nwave + EPB - 1)/EPB), dim3(FB_WAVE*EPB), 0, st, (const DevModel<double>*)b->dM, F);
+    hipLaunchKernelGGL((k_fd_assemble<double>), dim3(n*(c1 - c0)), dim3(FB_WAVE), 0, st, (const DevModel<double>*)b->dM, F);
+  }
+  HIPCHK(hipGetLastError());
+  return 0;
+  FB_GUARD_END
+}
+
+// Tickets the last fb_batch_transition_fd call ran (perturbed and nominal transitions; a ctrl side that a range limit forbids is not run).
+// Synchronises the device.  A debug counter: the tests count columns with it instead of timing them.
+extern "C" int fb_batch_fd_tickets(fb_batch* b, int64_t* n) {
+  if (!b || !n) return fail("fb_batch_fd_tickets: null argument");
+  *n = 0;
+  if (!b->fd_counter) return 0;
+  HIPCHK(hipSetDevice(b->device));
+  HIPCHK(hipDeviceSynchronize());
+  int c[2] = {0, 0};
+  HIPCHK(hipMemcpy(c, b->fd_counter, sizeof(c), hipMemcpyDeviceToHost));
+  *n = c[1];
+  return 0;
 }
 
 // ------------------------------------------------------------------ field access

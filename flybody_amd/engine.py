@@ -66,6 +66,9 @@ def stage_sequence(nsubstep: int):
     return [('task_pre', ST['PRE'])] + sub*nsubstep + [('task_post', ST['POST'])]
 
 
+# Batch.transition_fd / derivatives.transition_fd: the Jacobians of one transition (None: not asked for) and the frames' warning bits
+TransitionFD = collections.namedtuple('TransitionFD', ['A', 'B', 'C', 'D', 'status'])
+
 _libs: Dict[str, C.CDLL] = {}
 
 
@@ -133,6 +136,9 @@ def load_library(lib_path: Optional[str] = None) -> C.CDLL:
         L.fb_batch_set_control_law.argtypes = [C.c_void_p, C.c_void_p]
         L.fb_batch_control_law_active.argtypes = [C.c_void_p]
         L.fb_batch_end_episode.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    if hasattr(L, 'fb_batch_transition_fd'):
+        L.fb_batch_transition_fd.argtypes = [C.c_void_p] + [C.c_void_p]*7
+        L.fb_batch_fd_tickets.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
     _libs[path] = L
     return L
 
@@ -186,6 +192,12 @@ class _IKConfig(C.Structure):
 class _ControlLaw(C.Structure):
     """fb_control_law (include/flybody_engine.h)."""
     _fields_ = [(k, C.c_void_p) for k in LAW_ROWS] + [('n_rows', C.c_int32)]
+
+
+class _FDConfig(C.Structure):
+    """fb_fd_config (include/flybody_engine.h)."""
+    _fields_ = [('eps', C.c_double), ('centered', C.c_int32), ('n_substeps', C.c_int32), ('n_frames', C.c_int32), ('env_ids', C.c_void_p),
+                ('pool_rows', C.c_int32)]
 
 
 class Model:
@@ -253,7 +265,7 @@ class Batch:
     def __init__(self, model, n_env: int, device: int = 0, precision: int = 64):
         self.group = model if isinstance(model, ModelGroup) else None
         self.model = model.models[0] if self.group else model
-        self.L = self.model.L; self.n_env = n_env; self.precision = precision
+        self.L = self.model.L; self.n_env = n_env; self.precision = precision; self.device = device
         h = C.c_void_p()
         if self.group:
             _check(self.L, self.L.fb_batch_create_group(self.group.handles, len(self.group), n_env, device, precision, C.byref(h)))
@@ -368,6 +380,37 @@ class Batch:
         ([n_env][MAXCON][3], contact frame); EFC_FORCE / QFRC_CONSTRAINT hold the inverse's values.  discrete: QACC is (qvel+ - qvel) / h
         of the engine's Euler substep (FB_INV_DISCRETE).  Noslip is not inverted.  FP64 batches only.  Asynchronous after its checks."""
         _check(self.L, self.L.fb_batch_inverse(self.h, 1 if discrete else 0, stream))
+
+    def transition_fd(self, env_ids=None, eps: float = 1e-6, centered: bool = True, n_substeps: int = 1, sensors: bool = False,
+                      want_A: bool = True, want_B: bool = True, pool_rows: int = 0, stream=None) -> 'TransitionFD':
+        """Transition derivatives of the listed environments (fb_batch_transition_fd, MuJoCo's mjd_transitionFD; None: all of them):
+        TransitionFD(A [n, ndx, ndx], B [n, ndx, nu], C [n, 33, ndx], D [n, 33, nu], status [n]) as torch FP64 (status: int32) tensors
+        on the batch's device, None for what was not asked for (want_A / want_B; sensors: C and D beside them).  ndx = 2 nv + na;
+        x = (qpos, qvel, act) in the tangent space, u = ctrl.  The environments are only read.  Asynchronous on `stream` (None: torch's
+        current stream of the device, so torch work that follows is ordered behind it).  A library without a GPU behind it (the tests'
+        kernel-emulation build) gets CPU tensors: its "device" memory is host memory."""
+        import torch
+        ids = np.arange(self.n_env, dtype=np.int32) if env_ids is None else np.ascontiguousarray(env_ids, np.int32).reshape(-1)
+        n, nv, na, nu = len(ids), self.model.dim('nv'), self.model.dim('na'), self.model.dim('nu')
+        ndx = 2*nv + na
+        emulated = b'emulation' in self.L.fb_version()
+        dev = 'cpu' if emulated else 'cuda:%d' % self.device
+        if stream is None and not emulated:
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+        new = lambda want, *shape: torch.zeros((n,) + shape, dtype=torch.float64, device=dev) if want and n else None
+        A, B = new(want_A, ndx, ndx), new(want_B, ndx, nu)
+        Cs, Ds = new(want_A and sensors, NSENSOR, ndx), new(want_B and sensors, NSENSOR, nu)
+        status = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
+        cfg = _FDConfig(float(eps), int(bool(centered)), int(n_substeps), n, ids.ctypes.data, int(pool_rows))
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        _check(self.L, self.L.fb_batch_transition_fd(self.h, C.byref(cfg), ptr(A), ptr(B), ptr(Cs), ptr(Ds), ptr(status), stream))
+        return TransitionFD(A, B, Cs, Ds, status[:n])
+
+    def fd_tickets(self) -> int:
+        """Transitions (nominal + perturbed) the last transition_fd call ran (fb_batch_fd_tickets; synchronises the device)."""
+        n = C.c_int64(0)
+        _check(self.L, self.L.fb_batch_fd_tickets(self.h, C.byref(n)))
+        return n.value
 
     def clear_forces(self):
         """Free the applied-force arrays (QFRC_APPLIED / XFRC_APPLIED) and return the batch to the plain step kernel

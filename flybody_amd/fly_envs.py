@@ -364,6 +364,16 @@ class BatchedFlyEnv:
         if not self.batch.forces_active:
             self._force_views = None
 
+    # ---- transition derivatives (flybody_amd.derivatives, csrc/fb_deriv.hpp) ---------------------
+    def linearize(self, env_ids=None, **kw):
+        """Linearise live environments between two control steps without disturbing them: engine.TransitionFD(A, B, C, D, status) of one
+        physics substep (or n_substeps=...) around each listed environment's current state and held ctrl, as torch FP64 tensors on the
+        device (Batch.transition_fd: eps, centered, n_substeps, sensors, want_A, want_B, pool_rows, stream).  The environments are only
+        read -- the steps that follow are bit-identical to those of an environment that was never linearised.  The constraint solves
+        warm-start from the acceleration the environment's next substep would start from.  FP64 batches without applied forces or a
+        control law."""
+        return self.batch.transition_fd(env_ids=env_ids, **kw)
+
     # ---- the parts of a control step around the kernel ------------------------------------------
     @property
     def _hooks_after(self) -> bool:

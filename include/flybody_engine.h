@@ -266,6 +266,49 @@ int fb_batch_ik(fb_batch* b, const fb_ik_config* cfg, const double* target_xpos,
 enum { FB_INV_DISCRETE = 1 };
 int fb_batch_inverse(fb_batch* b, int flags, void* stream);
 
+/* Transition derivatives, MuJoCo's mjd_transitionFD for the engine's step (FP64 batches only; csrc/fb_deriv.hpp): the
+ * finite-difference Jacobians of n_substeps physics substeps with ctrl held,
+ *     A = dx'/dx [ndx][ndx]   B = dx'/du [ndx][nu]   C = ds'/dx [33][ndx]   D = ds'/du [33][nu]      per frame, row-major, FP64,
+ * in caller-provided DEVICE buffers [n_frames][..][..].  x = (qpos, qvel, act), u = ctrl, s = FB_SENSORDATA as the last substep leaves it
+ * (the engine's legacy-step timing: acceleration-stage sensors lag one substep).  The tangent is dx = (dq[nv], dv[nv], dact[na]),
+ * ndx = 2 nv + na, with dq in the joints' velocity space (mj_integratePos / mj_differentiatePos: free-joint translation, free- and
+ * ball-joint rotation as a local 3-vector, hinge angle).
+ * Frame k is environment env_ids[k] (k when env_ids is NULL) as it stands: its FB_QPOS / FB_QVEL / FB_ACT / FB_CTRL, and its warm start
+ * w = the acceleration its next solve would start from (after fb_batch_forward: that pass's FB_QACC).  The transition recomputes the
+ * position and velocity stages from the (perturbed) state -- no cached stage output is trusted --, then runs the substeps in the step's
+ * own order (actuation .. acceleration sensors, Euler with implicit damping, position + velocity stages of the new state; noslip
+ * included).  The first substep's constraint solve warm-starts from w, the SAME w for every perturbation (as MuJoCo saves and restores
+ * qacc_warmstart); later substeps from their predecessor.  No task hook runs: no action mapping, reward, termination, auto-reset or
+ * pattern generator -- the transition is a function of (qpos, qvel, act, ctrl, w) only.
+ * Columns: j < nv: qpos integrated by +-eps e_j; j < 2 nv: qvel[j - nv] +- eps; j < ndx: act +- eps; beyond: ctrl +- eps.  centered = 1:
+ * diff(T(x-), T(x+)) / (2 eps); 0: diff(T(x), T(x+)) / eps; diff is differentiatePos on the qpos rows, subtraction elsewhere.  The
+ * actuation stage clamps ctrl to ctrlrange, so a ctrl nudge that would leave the range is not taken: a centred column becomes one-sided
+ * on the side that stays inside, a forward column nudges backwards, and if neither side fits the column is zero (MuJoCo's rule).
+ * A NULL output is skipped: with A and C NULL no state column is run, with B and D NULL no ctrl column; with C and D NULL the position
+ * and velocity stages behind the last integration are skipped too.  status (optional, DEVICE, int32 [n_frames]) receives the OR of the
+ * FB_WARN_* bits any of the frame's transitions raised (contact / row caps, the solver's iteration limit, ...): a derivative through a
+ * capped solve is not a derivative.
+ * Nothing a later control step reads changes: the environments' rows are only read; state, caches, warm start, FB_WARN*, FB_SIZE_STATS
+ * and FB_STEP_TICKS stay as they were.  The work runs on scratch rows the batch owns (allocated on the first call: one workspace row per
+ * resident wave slot -- fb_batch_scheduler's `slots` -- never frames x columns; pool_rows uses fewer) and through a staging buffer of at
+ * most 256 MB: more frames than fit are processed in chunks.  Results do not depend on pool_rows or on scheduling: two calls give the
+ * same bits.
+ * Refused, with the reason in fb_last_error(): an FP32 batch; a grouped batch of more than one model; a batch with a control law set or
+ * with applied forces allocated (as fb_batch_stage refuses them); null batch or config; all four outputs NULL; eps not finite or <= 0;
+ * n_substeps < 1; n_frames < 1; centered other than 0 / 1; an environment id out of range; pool_rows out of range.
+ * Asynchronous on `stream` after validation, ordered like any other launch on that stream.
+ * fb_batch_fd_tickets: the number of transitions (nominal + perturbed) the last call ran; synchronises the device (a debug counter). */
+typedef struct fb_fd_config {
+  double eps;                 /* > 0, finite; MuJoCo's default use is 1e-6 */
+  int32_t centered;           /* 0 forward, 1 centred */
+  int32_t n_substeps;         /* >= 1: derivative of n physics substeps with ctrl held (1 = mjd_transitionFD) */
+  int32_t n_frames;           /* >= 1 */
+  const int32_t* env_ids;     /* HOST [n_frames]: the environments linearised; NULL: 0 .. n_frames-1 */
+  int32_t pool_rows;          /* 0: the resident slots; otherwise 1 .. resident slots */
+} fb_fd_config;
+int fb_batch_transition_fd(fb_batch* b, const fb_fd_config* cfg, double* A, double* B, double* C, double* D, int32_t* status, void* stream);
+int fb_batch_fd_tickets(fb_batch* b, int64_t* n);
+
 /* External forces (FB_QFRC_APPLIED, FB_XFRC_APPLIED), MuJoCo's two user inputs for everything that is not an actuator, a contact or the
  * fluid model.  Every substep
  *     qfrc_smooth = qfrc_passive - qfrc_bias + qfrc_actuator + qfrc_applied + sum_b J_b(xipos_b)' xfrc_applied_b
