@@ -139,9 +139,21 @@ enum hipMemcpyKind { hipMemcpyHostToDevice, hipMemcpyDeviceToHost, hipMemcpyDevi
 static inline const char* hipGetErrorString(hipError_t) { return "emu error"; }
 static inline hipError_t hipGetDeviceCount(int* n) { *n = 1; return hipSuccess; }
 static inline hipError_t hipSetDevice(int) { return hipSuccess; }
-static inline hipError_t hipMalloc(void** p, size_t n) { *p = calloc(n ? n : 1, 1); return *p ? hipSuccess : 1; }
+// Test hooks of the host layer (tests/test_host_ownership_emulation.py): the blocks and events that are alive, and one allocation made to
+// fail -- fb_emu_fail_alloc(k): the k-th hipMalloc from now returns an error, once; k < 0 disarms.  Exported by the emulation build only.
+static int emu_live_allocs = 0, emu_live_events = 0, emu_fail_in = -1;
+extern "C" __attribute__((visibility("default"))) int fb_emu_live_allocs(void) { return emu_live_allocs; }
+extern "C" __attribute__((visibility("default"))) int fb_emu_live_events(void) { return emu_live_events; }
+extern "C" __attribute__((visibility("default"))) void fb_emu_fail_alloc(int k) { emu_fail_in = k < 0 ? -1 : k; }
+static inline hipError_t hipMalloc(void** p, size_t n) {
+  *p = nullptr;
+  if (emu_fail_in >= 0 && emu_fail_in-- == 0) return 2;
+  *p = calloc(n ? n : 1, 1);
+  if (*p) emu_live_allocs++;
+  return *p ? hipSuccess : 2;
+}
 template <typename T> static inline hipError_t hipMalloc(T** p, size_t n) { return hipMalloc((void**)p, n); }
-static inline hipError_t hipFree(void* p) { free(p); return hipSuccess; }
+static inline hipError_t hipFree(void* p) { if (p) emu_live_allocs--; free(p); return hipSuccess; }
 static inline hipError_t hipMemset(void* p, int v, size_t n) { memset(p, v, n); return hipSuccess; }
 static inline hipError_t hipMemsetAsync(void* p, int v, size_t n, hipStream_t) { memset(p, v, n); return hipSuccess; }
 static inline hipError_t hipMemcpy(void* d, const void* s, size_t n, hipMemcpyKind) { memcpy(d, s, n); return hipSuccess; }
@@ -153,8 +165,8 @@ static inline hipError_t hipMemcpy2D(void* d, size_t dp, const void* s, size_t s
 static inline hipError_t hipDeviceSynchronize() { return hipSuccess; }
 static inline hipError_t hipStreamSynchronize(hipStream_t) { return hipSuccess; }
 static inline hipError_t hipGetLastError() { return hipSuccess; }
-static inline hipError_t hipEventCreate(hipEvent_t* e) { *e = new emu_event(); return hipSuccess; }
-static inline hipError_t hipEventDestroy(hipEvent_t e) { delete e; return hipSuccess; }
+static inline hipError_t hipEventCreate(hipEvent_t* e) { *e = new emu_event(); emu_live_events++; return hipSuccess; }
+static inline hipError_t hipEventDestroy(hipEvent_t e) { if (e) emu_live_events--; delete e; return hipSuccess; }
 static inline hipError_t hipEventRecord(hipEvent_t e, hipStream_t) { e->t = std::chrono::steady_clock::now(); return hipSuccess; }
 static inline hipError_t hipEventSynchronize(hipEvent_t) { return hipSuccess; }
 static inline hipError_t hipEventElapsedTime(float* ms, hipEvent_t a, hipEvent_t b) {
@@ -175,4 +187,9 @@ static inline void emu_launch(F kernel, dim3 grid, dim3 block, Args... args) {
   auto thunk = [](void* p) { Ctx* c = (Ctx*)p; emu_apply(c->k, *c->t, std::index_sequence_for<Args...>{}); };
   for (unsigned b = 0; b < grid.x; b++) emu_run_block(thunk, &ctx, b);
 }
+#ifdef FB_EMU_NO_LAUNCH
+// (tests/host_lifecycle_main.cpp: the host layer under AddressSanitizer, which does not follow the fibers' hand-made stack switches)
+#define hipLaunchKernelGGL(kernel, grid, block, shmem, stream, ...) ((void)0)
+#else
 #define hipLaunchKernelGGL(kernel, grid, block, shmem, stream, ...) emu_launch(kernel, grid, block, __VA_ARGS__)
+#endif

@@ -27,58 +27,10 @@ extern "C" { long long fb_stats[64]; }
 #include "fb_ik.hpp"
 #include "fb_inverse.hpp"
 #include "fb_deriv.hpp"
+#include "fb_host.hpp"                    // g_err / fail / HIPCHK, DevBuf, DevEvent
+#include "fb_model.hpp"                   // fb_model and the C-ABI's model entry points
 
-static thread_local std::string g_err;
-static int fail(const std::string& s) { g_err = s; return -1; }
 extern "C" const char* fb_last_error(void) { return g_err.c_str(); }
-
-#define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return fail(std::string(#x) + ": " + hipGetErrorString(e_)); } while (0)
-
-// ------------------------------------------------------------------ blob
-struct BlobEntry { char name[40]; uint32_t dtype, ndim, shape[4]; uint64_t offset, nbytes; };
-
-struct fb_model {
-  std::vector<char> blob;
-  std::map<std::string, const BlobEntry*> idx;
-  // host-side derived tables
-  int nq, nv, nbody, njnt, ngeom, nsite, nu, na, ntendon, npair, nM, nsubstep, nobsjnt, napp, nforce, ntouch;
-  int task_id;                           // FB_TASK_* (fb_types.hpp)
-  std::vector<int> body_nsub, body_depth, body_chlen, body_chain, body_common, dof_depth, dof_ndesc, lvl_dof, lvl_start, adh_act;
-  std::vector<int> wrap_qadr, act_wn, act_wdof, act_lenadr; std::vector<double> act_wcoef;
-  std::vector<int> pair_word, pair_body, plane_geoms;
-  std::vector<double> geom_box;          // [ngeom][3] oriented-box half extents by geom type (constant: one lookup instead of type -> size -> switch)
-  std::vector<int> dof_cl, dof_gen, gen_k, gen_m, fwd_tab, fwd_pack, fac_w, fac_band, fac_dof; int ngen = 0, ntrunk = 1, prefix_split = 0;
-  int nlevel;
-  std::vector<double> body_box, body_rec;
-  std::vector<int> body_fluid_geom, sens_body, dof_jump, dof_vbef, body_veldof;
-  double totalmass;
-  // A missing or ill-typed array is an error of the caller's blob, never a reason to take the process down: the accessors
-  // throw, every extern "C" entry point that reads the model catches and returns -1 with the message in fb_last_error().
-  // fb_model_load checks every array the engine reads (name, type, minimum length) up front, so a loaded model cannot throw.
-  const double* d(const char* n, size_t* cnt = nullptr) const {
-    auto it = idx.find(n);
-    if (it == idx.end() || it->second->dtype != 0) throw std::runtime_error(std::string("model blob: missing f64 array '") + n + "'");
-    if (cnt) *cnt = it->second->nbytes/8;
-    return (const double*)(blob.data() + it->second->offset);
-  }
-  const int* i(const char* n, size_t* cnt = nullptr) const {
-    auto it = idx.find(n);
-    if (it == idx.end() || it->second->dtype != 1) throw std::runtime_error(std::string("model blob: missing i32 array '") + n + "'");
-    if (cnt) *cnt = it->second->nbytes/4;
-    return (const int*)(blob.data() + it->second->offset);
-  }
-  bool has(const char* n, int dtype) const { auto it = idx.find(n); return it != idx.end() && (int)it->second->dtype == dtype; }
-  void need(const char* n, int dtype, size_t min_count) const {
-    auto it = idx.find(n);
-    if (it == idx.end()) throw std::runtime_error(std::string("model blob: missing array '") + n + "'");
-    if ((int)it->second->dtype != dtype) throw std::runtime_error(std::string("model blob: array '") + n + "' has the wrong type (expected " + (dtype ? "i32" : "f64") + ")");
-    size_t c = it->second->nbytes/(dtype ? 4 : 8);
-    if (c < min_count) throw std::runtime_error(std::string("model blob: array '") + n + "' has " + std::to_string(c) + " elements, expected at least " + std::to_string(min_count));
-  }
-};
-
-#define FB_GUARD_BEGIN try {
-#define FB_GUARD_END } catch (const std::exception& e_) { return fail(e_.what()); }
 
 // Build identity of this shared object (the GPU test log / smoke() print it, so a log shows which binary ran)
 #ifndef FB_BUILD_ID
@@ -92,438 +44,6 @@ extern "C" const char* fb_version(void) {
 #endif
 }
 
-static int model_load_impl(fb_model* m, size_t n);
-
-extern "C" int fb_model_load(const void* blob, size_t n, fb_model** out) {
-  if (!out) return fail("fb_model_load: null output pointer");
-  *out = nullptr;
-  if (!blob || n < 8 || memcmp(blob, "FBM1", 4) != 0) return fail("fb_model_load: bad blob magic");
-  fb_model* m = new fb_model();
-  int rc;
-  try {
-    m->blob.assign((const char*)blob, (const char*)blob + n);
-    rc = model_load_impl(m, n);
-  } catch (const std::exception& e_) { rc = fail(std::string("fb_model_load: ") + e_.what()); }
-  if (rc != 0) { delete m; return rc; }
-  *out = m;
-  return 0;
-}
-
-// every array the engine reads, with its element type and the minimum length the model's dimensions imply
-static void check_model_arrays(const fb_model* m) {
-  const size_t nq = m->nq, nv = m->nv, nb = m->nbody, nj = m->njnt, ng = m->ngeom, ns = m->nsite, nu = m->nu, nt = m->ntendon, np = m->npair;
-  struct Req { const char* name; int dtype; size_t n; };
-  size_t nwrap = 0; { size_t c = 0; m->i("wrap_dofid", &c); nwrap = c; }
-  const Req req[] = {
-    {"body_mass", 0, nb}, {"body_inertia", 0, 3*nb}, {"body_invweight0", 0, 2*nb}, {"body_pos", 0, 3*nb}, {"body_quat", 0, 4*nb},
-    {"body_ipos", 0, 3*nb}, {"body_iquat", 0, 4*nb}, {"jnt_pos", 0, 3*nj}, {"jnt_axis", 0, 3*nj}, {"jnt_stiffness", 0, nj},
-    {"jnt_range", 0, 2*nj}, {"jnt_solref", 0, 2*nj}, {"jnt_solimp", 0, 5*nj}, {"jnt_margin", 0, nj}, {"qpos0", 0, nq}, {"qpos_spring", 0, nq},
-    {"dof_armature", 0, nv}, {"dof_damping", 0, nv}, {"dof_invweight0", 0, nv}, {"geom_pos", 0, 3*ng}, {"geom_quat", 0, 4*ng},
-    {"geom_size", 0, 3*ng}, {"geom_rbound", 0, ng}, {"geom_fluid", 0, 12*ng}, {"site_pos", 0, 3*ns}, {"site_quat", 0, 4*ns}, {"site_size", 0, 3*ns},
-    {"wrap_coef", 0, nwrap}, {"actuator_dynprm", 0, nu}, {"actuator_gainprm", 0, 3*nu}, {"actuator_biasprm", 0, 3*nu},
-    {"actuator_ctrlrange", 0, 2*nu}, {"actuator_forcerange", 0, 2*nu}, {"pair_friction", 0, 5*np}, {"pair_solref", 0, 2*np},
-    {"pair_solimp", 0, 5*np}, {"pair_margin", 0, np}, {"pair_gap", 0, np}, {"opt_timestep", 0, 1}, {"opt_control_timestep", 0, 1},
-    {"opt_gravity", 0, 3}, {"opt_density", 0, 1}, {"opt_viscosity", 0, 1}, {"opt_impratio", 0, 1}, {"opt_tolerance", 0, 1},
-    {"opt_noslip_tolerance", 0, 1}, {"stat_meaninertia", 0, 1}, {"com_offset", 0, 3},
-    {"body_parent", 1, nb}, {"body_dofadr", 1, nb}, {"body_dofnum", 1, nb}, {"body_jntadr", 1, nb}, {"body_jntnum", 1, nb},
-    {"jnt_type", 1, nj}, {"jnt_qposadr", 1, nj}, {"jnt_dofadr", 1, nj}, {"jnt_bodyid", 1, nj}, {"jnt_limited", 1, nj},
-    {"dof_bodyid", 1, nv}, {"dof_jntid", 1, nv}, {"dof_parentid", 1, nv}, {"dof_Madr", 1, nv + 1}, {"geom_type", 1, ng}, {"geom_bodyid", 1, ng},
-    {"site_bodyid", 1, ns}, {"site_type", 1, ns}, {"tendon_adr", 1, nt}, {"tendon_num", 1, nt}, {"actuator_trntype", 1, nu},
-    {"actuator_trnid", 1, nu}, {"actuator_dyntype", 1, nu}, {"actuator_biastype", 1, nu}, {"actuator_ctrllimited", 1, nu},
-    {"actuator_forcelimited", 1, nu}, {"actuator_actadr", 1, nu}, {"action_to_ctrl", 1, nu}, {"pair_geom1", 1, np}, {"pair_geom2", 1, np},
-    {"pair_condim", 1, np}, {"observable_joints", 1, 0}, {"appendage_sites", 1, 0}, {"sensor_force_sites", 1, 0}, {"sensor_touch_sites", 1, 0},
-    {"wing_jnt", 1, 6}, {"wing_action_idx", 1, 0}, {"task_id", 1, 1}, {"user_action_idx", 1, 1}, {"sensor_site_thorax", 1, 1},
-    {"opt_iterations", 1, 1}, {"opt_noslip_iterations", 1, 1}, {"wrap_dofid", 1, 0},
-  };
-  for (const Req& r : req) m->need(r.name, r.dtype, r.n);
-  // index ranges the kernels rely on
-  auto in_range = [&](const char* name, size_t cnt, int lo, int hi) {
-    const int* v = m->i(name);
-    for (size_t k = 0; k < cnt; k++) if (v[k] < lo || v[k] >= hi) throw std::runtime_error(std::string("model blob: '") + name + "' holds an index out of range");
-  };
-  in_range("body_parent", nb, -1, (int)nb); in_range("dof_bodyid", nv, 0, (int)nb); in_range("dof_jntid", nv, 0, (int)nj);
-  in_range("jnt_qposadr", nj, 0, (int)nq); in_range("jnt_dofadr", nj, 0, (int)nv); in_range("jnt_bodyid", nj, 0, (int)nb);
-  in_range("geom_bodyid", ng, 0, (int)nb); in_range("site_bodyid", ns, 0, (int)nb); in_range("pair_geom1", np, 0, (int)ng); in_range("pair_geom2", np, 0, (int)ng);
-  in_range("action_to_ctrl", nu, 0, (int)nu); in_range("wrap_dofid", nwrap, 0, (int)nv);
-  { size_t c = 0; m->i("observable_joints", &c); in_range("observable_joints", c, 0, (int)nj); }
-  { size_t c = 0; m->i("appendage_sites", &c); in_range("appendage_sites", c, 0, (int)ns); }
-  { size_t c = 0; m->i("sensor_force_sites", &c); in_range("sensor_force_sites", c, 0, (int)ns); }
-  { size_t c = 0; m->i("sensor_touch_sites", &c); in_range("sensor_touch_sites", c, 0, (int)ns); }
-  in_range("wing_jnt", 6, 0, (int)nj); in_range("sensor_site_thorax", 1, 0, (int)ns);
-}
-
-static int model_load_impl(fb_model* m, size_t n) {
-  uint32_t narr; memcpy(&narr, m->blob.data() + 4, 4);
-  if (narr > 4096 || 8 + (size_t)narr*sizeof(BlobEntry) > n) return fail("fb_model_load: corrupt table of contents");
-  const BlobEntry* e = (const BlobEntry*)(m->blob.data() + 8);
-  for (uint32_t k = 0; k < narr; k++) {
-    if (!memchr(e[k].name, 0, sizeof(e[k].name))) return fail("fb_model_load: unterminated array name");
-    if (e[k].dtype > 1) return fail(std::string("fb_model_load: array '") + e[k].name + "' has an unknown element type");
-    if (e[k].offset > n || e[k].nbytes > n - e[k].offset) return fail(std::string("fb_model_load: array '") + e[k].name + "' lies outside the blob");
-    if (e[k].offset % 8 != 0) return fail(std::string("fb_model_load: array '") + e[k].name + "' is misaligned");
-    m->idx[std::string(e[k].name)] = e + k;
-  }
-  size_t c;
-  m->d("qpos0", &c); m->nq = (int)c;
-  m->i("dof_bodyid", &c); m->nv = (int)c;
-  m->i("body_parent", &c); m->nbody = (int)c;
-  m->i("jnt_type", &c); m->njnt = (int)c;
-  m->i("geom_type", &c); m->ngeom = (int)c;
-  m->i("site_bodyid", &c); m->nsite = (int)c;
-  m->i("actuator_trntype", &c); m->nu = (int)c;
-  m->i("tendon_adr", &c); m->ntendon = (int)c;
-  m->i("pair_geom1", &c); m->npair = (int)c;
-  m->i("observable_joints", &c); m->nobsjnt = (int)c;
-  m->i("appendage_sites", &c); m->napp = (int)c;
-  m->i("sensor_force_sites", &c); m->nforce = (int)c;
-  m->i("sensor_touch_sites", &c); m->ntouch = (int)c;
-  if (m->nq <= 0 || m->nv <= 0 || m->nbody <= 1 || m->njnt <= 0) return fail("fb_model_load: empty model");
-  check_model_arrays(m);
-  m->task_id = m->i("task_id")[0];
-  m->nM = m->i("dof_Madr")[m->nv];
-  if (!(m->d("opt_timestep")[0] > 0) || !(m->d("opt_control_timestep")[0] >= m->d("opt_timestep")[0])) return fail("fb_model_load: bad timestep / control timestep");
-  m->nsubstep = (int)floor(m->d("opt_control_timestep")[0] / m->d("opt_timestep")[0] + 0.5);
-  const int* actadr = m->i("actuator_actadr");
-  m->na = 0; for (int k = 0; k < m->nu; k++) if (actadr[k] >= 0) m->na++;
-  // ---- derived topology tables
-  int nb = m->nbody, nv = m->nv;
-  const int* parent = m->i("body_parent"); const int* dofadr = m->i("body_dofadr"); const int* dofnum = m->i("body_dofnum");
-  const int* dofpar = m->i("dof_parentid"); const int* dofbody = m->i("dof_bodyid");
-  m->body_depth.assign(nb, 0); m->body_nsub.assign(nb, 1);
-  for (int b = 1; b < nb; b++) m->body_depth[b] = m->body_depth[parent[b]] + 1;
-  for (int b = nb - 1; b > 0; b--) m->body_nsub[parent[b]] += m->body_nsub[b];
-  for (int b = 1; b < nb; b++) {
-    if (m->body_depth[b] > FB_MAXDEPTH) { return fail("fb_model_load: body tree deeper than FB_MAXDEPTH"); }
-    // LDS staging of the position / velocity stages (fb_smooth.hpp): frames + joint rotations + anchors / axes; motion axes + inertias;
-    // motion axes + body velocities + per-body wrenches -- all inside the smallest LDS pool of this build
-    { const int pool = std::min(LdsCfg<double>::POOL, LdsCfg<float>::POOL);
-      if (nb > 2*FB_WAVE || 7*nb + 10*m->njnt > pool || 6*nv + 10*nb > pool || 6*nv + 12*nb > pool || m->nM + 1 > FB_LDS_SCRATCH) { return fail("fb_model_load: model exceeds the per-environment LDS pool (bodies / joints / dofs)"); } }
-    // DFS contiguity: every body in (b, b+nsub) must descend from b
-    for (int d = b + 1; d < b + m->body_nsub[b]; d++) {
-      int a = d; while (a > b) a = parent[a];
-      if (a != b) { return fail("fb_model_load: bodies are not in DFS order"); }
-    }
-  }
-  m->dof_depth.assign(nv, 0);
-  for (int k = 0; k < nv; k++) { int a = dofpar[k], n_ = 0; while (a >= 0) { n_++; a = dofpar[a]; } m->dof_depth[k] = n_; }
-  m->body_chlen.assign(nb, 0); m->body_chain.assign((size_t)nb*FB_MAXCH, 0);
-  for (int b = 1; b < nb; b++) {
-    int a = b; while (a > 0 && dofnum[a] == 0) a = parent[a];
-    if (a <= 0) continue;
-    int last = dofadr[a] + dofnum[a] - 1;
-    int len = m->dof_depth[last] + 1;
-    if (len > FB_MAXCH) { return fail("fb_model_load: dof chain longer than FB_MAXCH"); }
-    if (m->nM > FB_MAXNM || m->nv > FB_MAXNV) { return fail("fb_model_load: model exceeds the LDS capacity constants FB_MAXNM / FB_MAXNV"); }
-    m->body_chlen[b] = len;
-    for (int k = last, s = len - 1; k >= 0; k = dofpar[k], s--) m->body_chain[(size_t)b*FB_MAXCH + s] = k;
-  }
-  m->body_common.assign((size_t)nb*nb, 0);
-  for (int a = 0; a < nb; a++) for (int b = 0; b < nb; b++) {
-    int n_ = 0, la = m->body_chlen[a], lb = m->body_chlen[b];
-    while (n_ < la && n_ < lb && m->body_chain[(size_t)a*FB_MAXCH + n_] == m->body_chain[(size_t)b*FB_MAXCH + n_]) n_++;
-    m->body_common[(size_t)a*nb + b] = n_;
-  }
-  // descendant ranges (dofs are in DFS order) and depth levels
-  m->dof_ndesc.assign(nv, 0);
-  for (int k = nv - 1; k >= 0; k--) if (dofpar[k] >= 0) m->dof_ndesc[dofpar[k]] += m->dof_ndesc[k] + 1;
-  for (int k = 0; k < nv; k++)
-    for (int q = k + 1; q <= k + m->dof_ndesc[k]; q++) {
-      int a = q; while (a > k) a = dofpar[a];
-      if (a != k) { return fail("fb_model_load: dofs are not in DFS order"); }
-    }
-  m->nlevel = 0;
-  for (int k = 0; k < nv; k++) if (m->dof_depth[k] + 1 > m->nlevel) m->nlevel = m->dof_depth[k] + 1;
-  m->lvl_start.assign(m->nlevel + 1, 0);
-  for (int d = 0; d < m->nlevel; d++) {
-    m->lvl_start[d] = (int)m->lvl_dof.size();
-    for (int k = 0; k < nv; k++) if (m->dof_depth[k] == d) m->lvl_dof.push_back(k);
-    if ((int)m->lvl_dof.size() - m->lvl_start[d] > FB_WAVE) { return fail("fb_model_load: more than 64 dofs on one depth level"); }
-  }
-  m->lvl_start[m->nlevel] = (int)m->lvl_dof.size();
-  // The factor is stored ROW-major like qM: row k = [1/D[k], L[k,parent], L[k,grandparent], ...] at dof_Madr[k].
-  // Along an unbranched chain consecutive rows grow by one entry, so the row start of the descendant of dof i on
-  // depth level d is  dof_Madr[i] - T(depth[i]) + T(d)  with T(d) = d(d+1)/2 -- no table lookup.
-  const int* madr = m->i("dof_Madr");
-  {
-    int adr = 0;
-    for (int k = 0; k < nv; k++) { if (madr[k] != adr) { return fail("fb_model_load: dof_Madr does not match the dof tree"); } adr += m->dof_depth[k] + 1; }
-    if (adr != m->nM) { return fail("fb_model_load: dof_Madr does not match the dof tree"); }
-  }
-  // pure-chain length below each dof (descendants i+1 .. i+cl are one unbranched chain).  The unbranched chain
-  // that starts at dof 0 is the "trunk" (the free joint): its rows are handled wave-parallel.  Other dofs whose
-  // subtree branches further down ("general" dofs: head, ...) get a per-level list of their descendants.
-  {
-    std::vector<int> nchild(nv, 0);
-    for (int k = 0; k < nv; k++) if (dofpar[k] >= 0) nchild[dofpar[k]]++;
-    m->dof_cl.assign(nv, 0);
-    for (int k = nv - 2; k >= 0; k--) m->dof_cl[k] = (nchild[k] == 1) ? m->dof_cl[k + 1] + 1 : 0;
-    // the trunk optimisation needs ONE dof tree whose root chain is an ancestor of every other dof (free-joint models);
-    // a forest (tethered fly: every limb is its own tree) has no trunk
-    int nroots = 0; for (int k = 0; k < nv; k++) if (dofpar[k] < 0) nroots++;
-    m->ntrunk = (nroots == 1) ? std::min(m->dof_cl[0] + 1, FB_MAXTRUNK) : 0;
-    m->dof_gen.assign(nv, -1);
-    for (int k = m->ntrunk; k < nv; k++) if (m->dof_ndesc[k] > m->dof_cl[k]) m->dof_gen[k] = m->ngen++;
-    if (m->ngen > 15 || m->ngen > FB_MAXGEN || m->ngen > FB_LGEN) { return fail("fb_model_load: more than FB_MAXGEN branching dofs"); }
-    m->gen_k.assign((size_t)FB_MAXGEN*FB_MAXCH, -1);            // 4 descendant dof ids per (general dof, level), 0xff = none
-    m->gen_m.assign((size_t)FB_MAXGEN*FB_MAXCH*2, -1);          // ... and their row starts, 4 x u16, 0xffff = none
-    for (int k = 0; k < nv; k++) {
-      if (m->dof_gen[k] < 0) continue;
-      for (int d = 0; d < m->nlevel; d++) {
-        unsigned pk = 0xffffffffu; unsigned long long pm = ~0ull; int cnt = 0;
-        for (int t = m->lvl_start[d]; t < m->lvl_start[d + 1]; t++) {
-          int q = m->lvl_dof[t];
-          if (q > k && q <= k + m->dof_ndesc[k]) {
-            if (cnt == 4) { return fail("fb_model_load: a branching dof has more than 4 descendants on one level"); }
-            pk = (pk & ~(0xffu << (8*cnt))) | ((unsigned)q << (8*cnt));
-            pm = (pm & ~(0xffffull << (16*cnt))) | ((unsigned long long)madr[q] << (16*cnt));
-            cnt++;
-          }
-        }
-        size_t o = (size_t)m->dof_gen[k]*FB_MAXCH + d;
-        m->gen_k[o] = (int)pk; m->gen_m[2*o] = (int)(unsigned)(pm & 0xffffffffu); m->gen_m[2*o + 1] = (int)(unsigned)(pm >> 32);
-      }
-    }
-    // forward-substitution table: ancestor of dof k on level d
-    m->fwd_tab.assign((size_t)FB_MAXCH*FB_MAXNV, 0);
-    for (int k = 0; k < nv; k++)
-      for (int a = dofpar[k]; a >= 0; a = dofpar[a]) m->fwd_tab[(size_t)m->dof_depth[a]*FB_MAXNV + k] = a;
-    // ... the same, four levels per word (8-bit dof ids): the solve's root-to-leaf loop fetches one word per four levels, one block
-    // ahead, instead of one table entry per level with a global-memory latency on every level
-    if (nv > 255) return fail("fb_model_load: more than 255 dofs (packed ancestor table)");
-    if (m->nbody > 2*FB_WAVE || 6*nv + 10*m->nbody > FB_LDS_SCRATCH + 276) return fail("fb_model_load: bodies / dofs exceed the LDS staging of the inertia stages");
-    m->fwd_pack.assign((size_t)((FB_MAXCH + 3)/4)*FB_MAXNV, 0);
-    for (int k = 0; k < nv; k++)
-      for (int a = dofpar[k]; a >= 0; a = dofpar[a]) { int d = m->dof_depth[a]; m->fwd_pack[(size_t)(d >> 2)*FB_MAXNV + k] |= (int)((unsigned)a << (8*(d & 3))); }
-  }
-  // factorisation work list: every off-diagonal entry (i, j) of the lower triangle with i outside the trunk is
-  // owned by one (lane, slot); the diagonal of dof j belongs to lane j & 63.  Entries are spread so that the number
-  // of triple products (= ndesc[i] per entry) is balanced over the 64 lanes.  Entries of general dofs need the
-  // descendant lists and may only sit in the first FB_FGEN slots.  One packed word per slot (fb_smooth.hpp).
-  {
-    struct Ent { int i, j, work; bool gen; };
-    std::vector<Ent> gen_ents, chain_ents;
-    for (int i = m->ntrunk; i < nv; i++)
-      for (int j = dofpar[i]; j >= 0; j = dofpar[j]) (m->dof_gen[i] >= 0 ? gen_ents : chain_ents).push_back({i, j, m->dof_ndesc[i] + 1, m->dof_gen[i] >= 0});
-    m->fac_w.assign((size_t)FB_FSLOT*FB_WAVE, (31 << 13) | (int)(15u << 28));        // depth 31: empty slot
-    auto put = [&](const Ent& e, int lane_, int slot) -> bool {
-      int dep = m->dof_depth[e.i], base = madr[e.i] - dep*(dep + 1)/2, ee = dep - m->dof_depth[e.j];
-      if (base < -4096 || base > 4095 || dep > 30) return false;
-      m->fac_w[(size_t)slot*FB_WAVE + lane_] = (base & 0x1fff) | (dep << 13) | (m->dof_cl[e.i] << 18) | (ee << 23) | (int)((unsigned)(e.gen ? m->dof_gen[e.i] : 15) << 28);
-      return true;
-    };
-    // Entries of branching dofs: the first FB_FGEN slots, spread over the lanes.
-    std::vector<int> ngs(FB_WAVE, 0);
-    if ((int)gen_ents.size() > FB_FGEN*FB_WAVE) { return fail("fb_model_load: lower triangle of M does not fit the factor work list"); }
-    for (size_t k = 0; k < gen_ents.size(); k++) { int l = (int)(k % FB_WAVE); if (!put(gen_ents[k], l, ngs[l]++)) return fail("fb_model_load: factor work list field overflow"); }
-    // Chain entries: sorted deepest dof first and DEALT to the lanes in turn, so slot s of every lane holds entries of (nearly) the
-    // same depth.  An entry publishes on level dep and pulls on levels dep+1 .. dep+cl; with this order the slots that do
-    // anything on a level form a narrow band that is the same for all lanes, and the level loop skips the rest (fac_band).
-    // (first key: the deepest level the entry still pulls on -- the abdomen's rows, which alone reach the last levels, then share a
-    // few slots instead of being spread over all of them by their depth)
-    std::stable_sort(chain_ents.begin(), chain_ents.end(), [&](const Ent& a, const Ent& b) {
-      int da = m->dof_depth[a.i], db = m->dof_depth[b.i], la = da + m->dof_cl[a.i], lb = db + m->dof_cl[b.i];
-      if (la != lb) return la > lb; if (da != db) return da > db; return a.work > b.work; });
-    const int nchain_slots = FB_FSLOT - FB_FGEN;
-    size_t placed = 0;
-    for (; placed < chain_ents.size() && placed < (size_t)nchain_slots*FB_WAVE; placed++)
-      if (!put(chain_ents[placed], (int)(placed % FB_WAVE), FB_FGEN + (int)(placed / FB_WAVE))) return fail("fb_model_load: factor work list field overflow");
-    // what does not fit the chain slots (the shallowest entries) goes to free slots of the first FB_FGEN (never skipped)
-    for (; placed < chain_ents.size(); placed++) {
-      int best = -1;
-      for (int l = 0; l < FB_WAVE; l++) if (ngs[l] < FB_FGEN && (best < 0 || ngs[l] < ngs[best])) best = l;
-      if (best < 0) { return fail("fb_model_load: lower triangle of M does not fit the factor work list"); }
-      if (!put(chain_ents[placed], best, ngs[best]++)) return fail("fb_model_load: factor work list field overflow");
-    }
-    // per level: bit masks of the chain slots that publish (dep == d) and that pull (dep < d <= dep + cl), over all lanes
-    m->fac_band.assign(64, 0);
-    for (int d = 0; d < 32; d++) {
-      unsigned pub = 0, pull = 0;
-      for (int s = FB_FGEN; s < FB_FSLOT; s++)
-        for (int l = 0; l < FB_WAVE; l++) {
-          int wd = m->fac_w[(size_t)s*FB_WAVE + l], dep = (wd >> 13) & 31, cl_ = (wd >> 18) & 31;
-          if (dep == 31) continue;
-          if (dep == d) pub |= 1u << s;
-          if (dep < d && d <= dep + cl_) pull |= 1u << s;
-        }
-      m->fac_band[2*d] = (int)pub; m->fac_band[2*d + 1] = (int)pull;
-    }
-    // rows of the factorisation / the solves per lane, dealt by depth: the 64 shallowest dofs outside the trunk are the lanes' first rows
-    // (in dof order, so that neighbouring lanes still hold neighbouring rows), the deeper ones their second rows (fb_smooth.hpp: fac_dof)
-    {
-      std::vector<int> order;
-      for (int i = m->ntrunk; i < nv; i++) order.push_back(i);
-      std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return m->dof_depth[a] < m->dof_depth[b]; });
-      if ((int)order.size() > 2*FB_WAVE) { return fail("fb_model_load: more dofs than two rows per lane"); }
-      std::vector<int> first(order.begin(), order.begin() + std::min<size_t>(order.size(), FB_WAVE)), second(order.begin() + std::min<size_t>(order.size(), FB_WAVE), order.end());
-      std::sort(first.begin(), first.end()); std::sort(second.begin(), second.end());
-      m->fac_dof.assign(2*FB_WAVE, 255);
-      for (size_t k = 0; k < first.size(); k++) m->fac_dof[k] = first[k];
-      for (size_t k = 0; k < second.size(); k++) m->fac_dof[FB_WAVE + k] = second[k];
-    }
-  }
-  const int* trn = m->i("actuator_trntype");
-  for (int k = 0; k < m->nu; k++) if (trn[k] == TRN_BODY) m->adh_act.push_back(k);
-  // collision mid phase: one packed word per candidate pair; the geoms' bounding spheres (and the plane normals) are
-  // staged in LDS (the Delassus-matrix slot, free at that point of the step), fb_collide.hpp: d_collision
-  {
-    const int *g1 = m->i("pair_geom1"), *g2 = m->i("pair_geom2"), *gt = m->i("geom_type");
-    std::vector<int> slot(m->ngeom, 0);
-    for (int g = 0; g < m->ngeom; g++) if (gt[g] == GEOM_PLANE) { m->plane_geoms.push_back(g); slot[g] = m->ngeom + (int)m->plane_geoms.size() - 1; }
-    if (m->ngeom + (int)m->plane_geoms.size() > 1023 || 4*(m->ngeom + (int)m->plane_geoms.size()) > LdsCfg<double>::AR_ELEMS + FB_MAXNV) { return fail("fb_model_load: too many geoms for the LDS staging area of the collision mid phase"); }
-    m->pair_word.assign(std::max(m->npair, 1), 0);
-    // the two bodies of a pair, packed (b1 | b2 << 16): constant, so that a contact's bodies are one lookup behind its pair id
-    // instead of pair -> geom -> body
-    m->pair_body.assign(std::max(m->npair, 1), 0);
-    { const int* gb = m->i("geom_bodyid"); for (int q = 0; q < m->npair; q++) m->pair_body[q] = gb[g1[q]] | (gb[g2[q]] << 16); }
-    for (int q = 0; q < m->npair; q++) {
-      if (gt[g2[q]] == GEOM_PLANE) { return fail("fb_model_load: a plane must be the first geom of a pair"); }
-      // bit 30: the pair goes through the convex narrow phase (MPR) -- everything but plane-x, sphere-sphere, sphere-capsule and
-      // capsule-capsule, which have closed forms (fb_collide.hpp: narrow_phase)
-      const int t1 = gt[g1[q]], t2 = gt[g2[q]];
-      const bool analytic = t1 == GEOM_PLANE || (t1 == GEOM_SPHERE && (t2 == GEOM_SPHERE || t2 == GEOM_CAPSULE)) || (t1 == GEOM_CAPSULE && t2 == GEOM_CAPSULE);
-      m->pair_word[q] = g1[q] | (g2[q] << 10) | (slot[g1[q]] << 20) | (analytic ? 0 : (1 << 30));
-    }
-    if (m->plane_geoms.empty()) m->plane_geoms.push_back(0);
-    const double* gs = m->d("geom_size");
-    m->geom_box.assign(3*std::max(m->ngeom, 1), 0.0);
-    for (int g = 0; g < m->ngeom; g++) {
-      double* e = &m->geom_box[3*g]; const double* sz = gs + 3*g;
-      if (gt[g] == GEOM_CAPSULE) { e[0] = e[1] = sz[0]; e[2] = sz[1] + sz[0]; }
-      else if (gt[g] == GEOM_CYLINDER) { e[0] = e[1] = sz[0]; e[2] = sz[1]; }
-      else if (gt[g] == GEOM_ELLIPSOID) { e[0] = sz[0]; e[1] = sz[1]; e[2] = sz[2]; }
-      else { e[0] = e[1] = e[2] = sz[0]; }
-    }
-  }
-  // flattened actuator transmissions and tendon wraps: one padded record per actuator / wrap, so that the kernel fetches
-  // them with a fixed number of independent loads instead of walking tendon_adr -> wrap_dofid -> dof_jntid -> jnt_qposadr
-  {
-    size_t nw_ = 0, c_ = 0;
-    const int *wd = m->i("wrap_dofid", &nw_), *tadr = m->i("tendon_adr"), *tnum = m->i("tendon_num"), *tid = m->i("actuator_trnid");
-    const int *djnt = m->i("dof_jntid"), *jqa = m->i("jnt_qposadr"), *jda = m->i("jnt_dofadr");
-    const double* wc = m->d("wrap_coef", &c_);
-    m->wrap_qadr.assign(std::max<size_t>(nw_, 1), 0);
-    for (size_t k = 0; k < nw_; k++) m->wrap_qadr[k] = jqa[djnt[wd[k]]];
-    for (int t = 0; t < m->ntendon; t++) if (tnum[t] > FB_MAXWRAP) { return fail("fb_model_load: tendon with more than FB_MAXWRAP joints"); }
-    m->act_wn.assign(m->nu, 0); m->act_lenadr.assign(m->nu, 0);
-    m->act_wdof.assign((size_t)m->nu*FB_MAXWRAP, 0); m->act_wcoef.assign((size_t)m->nu*FB_MAXWRAP, 0.0);
-    std::vector<int> owner(m->nv, -1);
-    for (int k = 0; k < m->nu; k++) {
-      int n_ = 0;
-      if (trn[k] == TRN_JOINT) { m->act_wdof[(size_t)k*FB_MAXWRAP] = jda[tid[k]]; m->act_wcoef[(size_t)k*FB_MAXWRAP] = 1.0; m->act_lenadr[k] = jqa[tid[k]]; n_ = 1; }
-      else if (trn[k] == TRN_TENDON) {
-        for (int q = 0; q < tnum[tid[k]]; q++) { m->act_wdof[(size_t)k*FB_MAXWRAP + q] = wd[tadr[tid[k]] + q]; m->act_wcoef[(size_t)k*FB_MAXWRAP + q] = wc[tadr[tid[k]] + q]; }
-        m->act_lenadr[k] = tid[k]; n_ = tnum[tid[k]];
-      }
-      m->act_wn[k] = n_;
-      // the kernel scatters joint / tendon actuator forces with plain stores (one lane per actuator): dofs must not be shared
-      for (int q = 0; q < n_; q++) {
-        int dq = m->act_wdof[(size_t)k*FB_MAXWRAP + q];
-        if (owner[dq] >= 0) { return fail("fb_model_load: two joint/tendon actuators drive the same dof"); }
-        owner[dq] = k;
-      }
-    }
-  }
-  const double* mass = m->d("body_mass"); const double* inert = m->d("body_inertia");
-  // per-body kinematics record: every constant the frame composition of one body needs, contiguous, so that a
-  // tree level costs one round of independent loads instead of a chain of table lookups (fb_smooth.hpp: fk_pass)
-  {
-    const double *bp = m->d("body_pos"), *bq = m->d("body_quat"), *bip = m->d("body_ipos"), *biq = m->d("body_iquat");
-    const double *jp = m->d("jnt_pos"), *jx = m->d("jnt_axis");
-    const int *bja = m->i("body_jntadr"), *bjn = m->i("body_jntnum"), *jt = m->i("jnt_type"), *jqa = m->i("jnt_qposadr");
-    m->body_rec.assign((size_t)nb*FB_BODYREC, 0);
-    for (int b = 0; b < nb; b++) {
-      double* R = m->body_rec.data() + (size_t)b*FB_BODYREC;
-      int jn = bjn[b], ja = bja[b];
-      if (jn > 3) { return fail("fb_model_load: more than 3 joints on one body"); }
-      bool fr = jn > 0 && jt[ja] == JNT_FREE;
-      if (fr && jn != 1) { return fail("fb_model_load: a free joint must be the only joint of its body"); }
-      R[0] = parent[b]; R[1] = ja; R[2] = jn; R[3] = fr ? 1 : 0;
-      for (int k = 0; k < 3; k++) { R[4 + k] = bp[3*b + k]; R[11 + k] = bip[3*b + k]; }
-      for (int k = 0; k < 4; k++) { R[7 + k] = bq[4*b + k]; R[14 + k] = biq[4*b + k]; }
-      for (int q = 0; q < jn; q++) for (int k = 0; k < 3; k++) { R[18 + 6*q + k] = jp[3*(ja + q) + k]; R[21 + 6*q + k] = jx[3*(ja + q) + k]; }
-      R[36] = fr ? jqa[ja] : 0;
-    }
-  }
-  m->body_box.assign((size_t)nb*3, 0); m->totalmass = 0;
-  for (int b = 1; b < nb; b++) {
-    m->totalmass += mass[b];
-    if (mass[b] < 1e-15) continue;
-    const double* I = inert + 3*b;
-    m->body_box[3*b+0] = sqrt(fmax(1e-15, I[1] + I[2] - I[0]) / mass[b] * 6.0);
-    m->body_box[3*b+1] = sqrt(fmax(1e-15, I[0] + I[2] - I[1]) / mass[b] * 6.0);
-    m->body_box[3*b+2] = sqrt(fmax(1e-15, I[0] + I[1] - I[2]) / mass[b] * 6.0);
-  }
-  // tree prefix sums over the dofs (body velocities, bias accelerations): ancestors at distance 2^k, the dof whose inclusive
-  // velocity prefix is the velocity "before" a dof (mj_comVel: the parent body's velocity plus the earlier dofs of the same body;
-  // a free joint's rotational axes see its three translations, a ball joint none of its own dofs), the last dof of a body's chain
-  {
-    if (FB_MAXCH > (1 << FB_NJUMP) || nv > 2*FB_WAVE) return fail("fb_model_load: dof tree too deep / too wide for the prefix tables");
-    m->dof_jump.assign((size_t)FB_NJUMP*nv, -1);
-    for (int i = 0; i < nv; i++) {
-      if (dofpar[i] >= i) return fail("fb_model_load: dof_parentid must number parents before children (the prefix sums exchange one slot for the ancestors of the first 64 dofs)");
-      m->dof_jump[i] = dofpar[i];
-    }
-    // Round 6: when every chain is at most 2^(FB_NJUMP - 1) dofs long BELOW the trunk (the fruit fly: 6 trunk dofs + <= 14), the jumps of the other dofs
-    // stop at the trunk: four rounds finish the trunk's own prefixes and everybody else's sum over their non-trunk ancestors, and the trunk's total -- common
-    // to all of them -- is added by one broadcast (tree_prefix6).  One round of lane exchanges less in each of the three prefix sums of a substep.
-    m->prefix_split = 0;
-    {
-      const int nT = m->ntrunk; int below = 0;
-      for (int i = nT; i < nv; i++) below = std::max(below, m->dof_depth[i] + 1 - nT);
-      if (nT > 0 && nT <= (1 << (FB_NJUMP - 1)) && below <= (1 << (FB_NJUMP - 1))) {
-        bool ok = true;
-        for (int i = nT; i < nv; i++) { int a = i; while (dofpar[a] >= nT) a = dofpar[a]; ok = ok && dofpar[a] == nT - 1; }      // (everything hangs off the last trunk dof)
-        if (ok) { m->prefix_split = 1; for (int i = nT; i < nv; i++) if (dofpar[i] < nT) m->dof_jump[i] = -1; }
-      }
-    }
-    for (int k = 1; k < FB_NJUMP; k++)
-      for (int i = 0; i < nv; i++) { int a = m->dof_jump[(size_t)(k - 1)*nv + i]; m->dof_jump[(size_t)k*nv + i] = a >= 0 ? m->dof_jump[(size_t)(k - 1)*nv + a] : -1; }
-    const int *djnt = m->i("dof_jntid"), *jt = m->i("jnt_type"), *jda = m->i("jnt_dofadr");
-    m->dof_vbef.assign(nv, -1);
-    for (int i = 0; i < nv; i++) {
-      int j = djnt[i];
-      if (jt[j] == JNT_FREE) m->dof_vbef[i] = (i - jda[j] < 3) ? -2 : jda[j] + 2;
-      else if (jt[j] == JNT_BALL) m->dof_vbef[i] = dofpar[jda[j]];
-      else m->dof_vbef[i] = dofpar[i];
-    }
-    m->body_veldof.assign(nb, -1);
-    for (int b = 1; b < nb; b++) if (m->body_chlen[b] > 0) m->body_veldof[b] = m->body_chain[(size_t)b*FB_MAXCH + m->body_chlen[b] - 1];
-  }
-  // bodies whose acceleration / force the sensors need: the accelerometer's body and the subtrees below the force-sensor bodies
-  {
-    std::vector<char> need(nb, 0);
-    const int* sb = m->i("site_bodyid");
-    need[sb[m->i("sensor_site_thorax")[0]]] = 1;
-    size_t nf = 0; const int* fs = m->i("sensor_force_sites", &nf);
-    for (size_t k = 0; k < nf; k++) { int b = sb[fs[k]]; for (int d = 0; d < m->body_nsub[b]; d++) need[b + d] = 1; }
-    for (int b = 0; b < nb; b++) if (need[b]) m->sens_body.push_back(b);
-    if ((int)m->sens_body.size() > FB_WAVE) m->sens_body.clear();
-  }
-  m->body_fluid_geom.assign(nb, -1);
-  { const double* gfl = m->d("geom_fluid"); const int* gb = m->i("geom_bodyid");
-    for (int g = 0; g < m->ngeom; g++) if (gfl[12*g] > 0) m->body_fluid_geom[gb[g]] = g; }
-  (void)dofbody;
-  return 0;
-}
-
-extern "C" void fb_model_destroy(fb_model* m) { delete m; }
-
-// Width of the observation vector (engine.observation_layout; fb_task.hpp: d_pack_obs writes it): the walker's own observables, 7 per reference frame
-// of the imitation tasks (nref = future_steps + 1 of them) and, for walk_on_ball, the ball's velocity
-static int obs_width(const fb_model* m, int nref, bool ball) {
-  return 3 + m->na + 3*m->napp + (ball ? 3 : 0) + 3*m->nforce + 3 + 2*m->nobsjnt + 7*nref + m->ntouch + 3 + 3;
-}
-
-extern "C" int fb_model_dim(const fb_model* m, const char* name) {
-  if (!m || !name) return -1;
-#define X(f) if (!strcmp(name, #f)) return m->f
-  X(nq); X(nv); X(nbody); X(njnt); X(ngeom); X(nsite); X(nu); X(na); X(ntendon); X(npair); X(nM); X(nsubstep);
-  X(nobsjnt); X(napp); X(nforce); X(ntouch); X(task_id);
-#undef X
-  if (!strcmp(name, "nact")) return m->nu + (m->i("user_action_idx")[0] >= 0 ? 1 : 0);
-  if (!strcmp(name, "nobs_base")) return obs_width(m, 0, false);
-  return -1;
-}
 
 // ------------------------------------------------------------------ kernels
 template <typename real>
@@ -965,39 +485,43 @@ struct fb_batch {
   const fb_model* m;
   int n_env, device, precision, nobs;
   WSOff off;
-  void* rarena = nullptr; int* iarena = nullptr;
-  float *obs = nullptr, *reward = nullptr, *discount = nullptr; int* step_type = nullptr;
-  int* d_ids = nullptr;
-  int* sched = nullptr;
-  int *cost = nullptr, *order = nullptr; bool order_valid = false, reorder = true, use_prio = true, ticket_order = true;
-  int *tick = nullptr, *done = nullptr, *sched_err = nullptr, *torder = nullptr; int nq = 0, slots = 0; bool tickets = false;      // substep scheduler (k_fly)
-  unsigned xcc_mask = 0; std::vector<void*> probed_streams; unsigned* probe_word = nullptr;  // ... the streams it was validated on, the probe's device word
-  void* park = nullptr;               // MODE_STAGE: LDS pools between single-stage launches (allocated on first use)
-  std::vector<void*> allocs;          // model tables on the device
+  // Device memory and events: every one a DevBuf / DevEvent member (fb_host.hpp), released when the batch is deleted.  A new buffer is one
+  // more such member and nothing else.  <void>: elements of the batch's precision, counted in bytes.
+  DevBuf<void> rarena; DevBuf<int> iarena;
+  DevBuf<float> obs, reward, discount; DevBuf<int> step_type;
+  DevBuf<int> d_ids;
+  DevBuf<int> sched;
+  DevBuf<int> cost, order; bool order_valid = false, reorder = true, use_prio = true, ticket_order = true;
+  DevBuf<int> tick, done, sched_err, torder; int nq = 0, slots = 0; bool tickets = false;      // substep scheduler (k_fly)
+  unsigned xcc_mask = 0; std::vector<void*> probed_streams; DevBuf<unsigned> probe_word;  // ... the streams it was validated on, the probe's device word
+  DevBuf<void> park;                  // MODE_STAGE: LDS pools between single-stage launches (allocated on first use)
+  // model tables on the device (upload, upload_i).  A second fb_batch_set_wbpg or fb_batch_set_*_dataset adds its tables and the earlier ones
+  // stay until the batch is destroyed: a launch in flight may still read them.
+  std::vector<DevBuf<void>> allocs;
   DevModel<double> M64; DevModel<float> M32;   // the model at the batch's precision (with_model: only that one is built)
   // grouped batch (fb_batch_create_group): the models, the device structs of all of them at the batch's precision (element 0 follows
   // M64 / M32, which the setters change: sync_model) and the assignment FB_ENV_MODEL [n_env] (null: a batch made by fb_batch_create)
-  std::vector<const fb_model*> models; std::vector<DevModel<double>> G64; std::vector<DevModel<float>> G32; int* env_model = nullptr;
+  std::vector<const fb_model*> models; std::vector<DevModel<double>> G64; std::vector<DevModel<float>> G32; DevBuf<int> env_model;
   int n_models() const { return models.empty() ? 1 : (int)models.size(); }
-  void* dM = nullptr;                 // the model struct in device memory (the kernels read it through the constant path)
+  DevBuf<void> dM;                    // the model struct in device memory (the kernels read it through the constant path)
   std::vector<char> dM_copy;          // ... what it currently holds (sync_model)
-  void *ref_qpos = nullptr, *ref_qvel = nullptr;
+  DevBuf<void> ref_qpos, ref_qvel;
   bool have_ref = false, have_wbpg = false;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr; int timed_launches = 0; bool timing = false;
-  std::vector<hipEvent_t> lev;        // per-launch event pairs of the timed region (fb_batch_timing_launches), created on first use
-  double* ik_err = nullptr; int* ik_steps = nullptr;      // fb_batch_ik results (FB_IK_ERR / FB_IK_STEPS), allocated on the first call
-  void* ik_buf = nullptr; size_t ik_buf_bytes = 0;        // ... its tables and targets (grown as needed)
-  double* inv_qfrc = nullptr; double* inv_cforce = nullptr;      // fb_batch_inverse results (FB_QFRC_INVERSE / FB_CONTACT_FORCE), allocated on the first call
-  void *qfrc_applied = nullptr, *xfrc_applied = nullptr;         // applied forces (FB_QFRC_APPLIED / FB_XFRC_APPLIED) at the batch's precision: both allocated by the first
+  DevEvent ev0, ev1; int timed_launches = 0; bool timing = false;
+  std::vector<DevEvent> lev;          // per-launch event pairs of the timed region (fb_batch_timing_launches), created on first use
+  DevBuf<double> ik_err; DevBuf<int> ik_steps;            // fb_batch_ik results (FB_IK_ERR / FB_IK_STEPS), allocated on the first call
+  DevBuf<void> ik_buf;                                    // ... its tables and targets (grown as needed)
+  DevBuf<double> inv_qfrc, inv_cforce;                           // fb_batch_inverse results (FB_QFRC_INVERSE / FB_CONTACT_FORCE), allocated on the first call
+  DevBuf<void> qfrc_applied, xfrc_applied;                       // applied forces (FB_QFRC_APPLIED / FB_XFRC_APPLIED) at the batch's precision: both allocated by the first
                                                                  // fb_batch_set / fb_batch_device_ptr of either, freed by fb_batch_clear_forces; allocated = k_step_forces steps the batch
   // substep control law (fb_batch_set_control_law, fb_law.hpp): coefficients [law_rows][5][nv] (FB_CONTROL_LAW) and output [n_env][nv] (FB_QFRC_LAW) at the
   // batch's precision, qpos addresses [nv]; set = k_step_law steps the batch.  law_owns_forces: the law allocated the force arrays itself (no caller
   // touched them), so clearing the law frees them too and the batch is back on k_fly
-  void *law_coef = nullptr, *law_out = nullptr; int* law_qadr = nullptr; int law_rows = 0; bool law_owns_forces = false;
+  DevBuf<void> law_coef, law_out; DevBuf<int> law_qadr; int law_rows = 0; bool law_owns_forces = false;
   // fb_batch_transition_fd (fb_deriv.hpp), allocated on the first call: the pool of scratch rows (one real + one int arena row per resident wave),
   // the staging buffer of the tickets' raw results (at most FB_FD_STAGING_BYTES, grown as needed), the frames' environments, the counters
-  double* fd_pool_r = nullptr; int* fd_pool_i = nullptr; int fd_slots = 0;
-  double* fd_stage = nullptr; size_t fd_stage_bytes = 0; int* fd_env = nullptr; int fd_env_cap = 0; int* fd_counter = nullptr;
+  DevBuf<double> fd_pool_r; DevBuf<int> fd_pool_i; int fd_slots = 0;
+  DevBuf<double> fd_stage; DevBuf<int> fd_env, fd_counter;
   std::vector<int> fd_env_host;
 };
 
@@ -1005,22 +529,22 @@ template <typename real, typename T, typename P>
 static int upload(fb_batch* b, const T* src, size_t n, P* dst) {
   std::vector<real> tmp(n ? n : 1);
   for (size_t k = 0; k < n; k++) tmp[k] = (real)src[k];
-  void* p;
-  HIPCHK(hipMalloc(&p, tmp.size()*sizeof(real)));
-  HIPCHK(hipMemcpy(p, tmp.data(), tmp.size()*sizeof(real), hipMemcpyHostToDevice));
-  b->allocs.push_back(p);
-  *dst = (const real*)p;
+  DevBuf<void> d;
+  if (d.alloc(tmp.size()*sizeof(real))) return -1;
+  HIPCHK(hipMemcpy(d.get(), tmp.data(), tmp.size()*sizeof(real), hipMemcpyHostToDevice));
+  *dst = (const real*)d.get();
+  b->allocs.push_back(std::move(d));
   return 0;
 }
 template <typename P>
 static int upload_i(fb_batch* b, const int* src, size_t n, P* dst) {
-  void* p;
-  HIPCHK(hipMalloc(&p, (n ? n : 1)*sizeof(int)));
-  if (n) HIPCHK(hipMemcpy(p, src, n*sizeof(int), hipMemcpyHostToDevice));
-  else HIPCHK(hipMemset(p, 0, sizeof(int)));        // an EMPTY table keeps one ZERO entry: the kernels read entry 0 of a table unpredicated in places
+  DevBuf<void> d;
+  if (d.alloc((n ? n : 1)*sizeof(int))) return -1;
+  if (n) HIPCHK(hipMemcpy(d.get(), src, n*sizeof(int), hipMemcpyHostToDevice));
+  else HIPCHK(hipMemset(d.get(), 0, sizeof(int)));  // an EMPTY table keeps one ZERO entry: the kernels read entry 0 of a table unpredicated in places
                                                     // (flight_imitation has no force sensors: a garbage site id from here indexed site_bodyid wildly)
-  b->allocs.push_back(p);
-  *dst = (const int*)p;
+  *dst = (const int*)d.get();
+  b->allocs.push_back(std::move(d));
   return 0;
 }
 
@@ -1049,30 +573,25 @@ static int sync_model(fb_batch* b) {
   return with_model(b, [&](auto& M) {
     auto& G = group_models(b, M);
     const size_t bytes = sizeof(M)*(G.empty() ? 1 : G.size());
-    if (!b->dM) HIPCHK(hipMalloc(&b->dM, bytes));
+    if (!b->dM && b->dM.alloc(bytes)) return -1;
     if (!G.empty()) { G[0] = M; for (size_t k = 1; k < G.size(); k++) copy_task_fields(G[k], M); }
     const char* h = G.empty() ? (const char*)&M : (const char*)G.data();
     if (b->dM_copy.empty() || memcmp(h, b->dM_copy.data(), bytes) != 0) {
       HIPCHK(hipDeviceSynchronize());
-      HIPCHK(hipMemcpy(b->dM, h, bytes, hipMemcpyHostToDevice));
+      HIPCHK(hipMemcpy(b->dM.get(), h, bytes, hipMemcpyHostToDevice));
       b->dM_copy.assign(h, h + bytes);
     }
     return 0;
   });
 }
 
-// a zeroed device buffer, allocated on the first call that needs it
+// a zeroed device buffer of n elements, allocated on the first call that needs it
 template <typename T>
-static int alloc_zeroed_once(T** p, size_t bytes) {
-  if (!*p) { HIPCHK(hipMalloc((void**)p, bytes)); HIPCHK(hipMemset(*p, 0, bytes)); }
-  return 0;
-}
+static int alloc_zeroed_once(DevBuf<T>& d, size_t n) { return d ? 0 : d.alloc_zeroed(n); }
 
 // a new, zeroed observation buffer of nobs floats per environment
 static int alloc_obs(fb_batch* b, int nobs) {
-  (void)hipFree(b->obs); b->obs = nullptr;
-  HIPCHK(hipMalloc((void**)&b->obs, (size_t)b->n_env*nobs*sizeof(float)));
-  HIPCHK(hipMemset(b->obs, 0, (size_t)b->n_env*nobs*sizeof(float)));
+  if (b->obs.alloc_zeroed((size_t)b->n_env*nobs)) return -1;
   b->nobs = nobs;
   return 0;
 }
@@ -1259,22 +778,13 @@ static int batch_create_impl(fb_batch* b) {
   if (!b->models.empty()) {
     std::vector<int> em(n_env);
     for (int e = 0; e < n_env; e++) em[e] = e % b->n_models();
-    HIPCHK(hipMalloc((void**)&b->env_model, n_env*sizeof(int)));
-    HIPCHK(hipMemcpy(b->env_model, em.data(), n_env*sizeof(int), hipMemcpyHostToDevice));
+    if (b->env_model.alloc(n_env)) return -1;
+    HIPCHK(hipMemcpy(b->env_model.get(), em.data(), n_env*sizeof(int), hipMemcpyHostToDevice));
   }
   const size_t rs = real_size(b);
-  HIPCHK(hipMalloc(&b->rarena, (size_t)n_env*b->off.nreal*rs));
-  HIPCHK(hipMemset(b->rarena, 0, (size_t)n_env*b->off.nreal*rs));
-  HIPCHK(hipMalloc((void**)&b->iarena, (size_t)n_env*b->off.nint*sizeof(int)));
-  HIPCHK(hipMemset(b->iarena, 0, (size_t)n_env*b->off.nint*sizeof(int)));
-  HIPCHK(hipMalloc((void**)&b->reward, n_env*sizeof(float)));
-  HIPCHK(hipMalloc((void**)&b->discount, n_env*sizeof(float)));
-  HIPCHK(hipMalloc((void**)&b->step_type, n_env*sizeof(int)));
-  HIPCHK(hipMalloc((void**)&b->d_ids, n_env*sizeof(int)));
-  HIPCHK(hipMalloc((void**)&b->sched, FB_NSCHED*sizeof(int)));
-  HIPCHK(hipMalloc((void**)&b->cost, n_env*sizeof(int)));
-  HIPCHK(hipMemset(b->cost, 0, n_env*sizeof(int)));
-  HIPCHK(hipMalloc((void**)&b->order, n_env*sizeof(int)));
+  if (b->rarena.alloc_zeroed((size_t)n_env*b->off.nreal*rs) || b->iarena.alloc_zeroed((size_t)n_env*b->off.nint)) return -1;
+  if (b->reward.alloc_zeroed(n_env) || b->discount.alloc_zeroed(n_env) || b->step_type.alloc_zeroed(n_env)) return -1;
+  if (b->d_ids.alloc(n_env) || b->sched.alloc(FB_NSCHED) || b->cost.alloc_zeroed(n_env) || b->order.alloc(n_env)) return -1;
   { const char* e_ = getenv("FB_NO_REORDER"); b->reorder = !(e_ && e_[0] == '1'); b->ticket_order = b->reorder; }
   // substep scheduler: for batches larger than the resident wave slots (k_fly)
   {
@@ -1292,10 +802,10 @@ static int batch_create_impl(fb_batch* b) {
           }
           b->slots = nb*prop.multiProcessorCount*LdsCfg<real>::EPB;
           return 0; })) return -1;
-    unsigned* dmask; unsigned hmask = 0;
-    HIPCHK(hipMalloc((void**)&dmask, sizeof(unsigned))); HIPCHK(hipMemset(dmask, 0, sizeof(unsigned)));
-    hipLaunchKernelGGL(k_probe_xcc, dim3(4096), dim3(FB_WAVE), 0, 0, dmask);
-    HIPCHK(hipMemcpy(&hmask, dmask, sizeof(unsigned), hipMemcpyDeviceToHost)); HIPCHK(hipFree(dmask));
+    DevBuf<unsigned> dmask; unsigned hmask = 0;
+    if (dmask.alloc_zeroed(1)) return -1;
+    hipLaunchKernelGGL(k_probe_xcc, dim3(4096), dim3(FB_WAVE), 0, 0, dmask.get());
+    HIPCHK(hipMemcpy(&hmask, dmask.get(), sizeof(unsigned), hipMemcpyDeviceToHost)); dmask.reset();
     int nqq = __builtin_popcount(hmask);
     b->nq = (nqq > 0 && hmask == (1u << nqq) - 1u) ? nqq : 0;          // XCC ids 0 .. nq-1, all seen; anything else: scheduler off
     b->xcc_mask = hmask;
@@ -1304,21 +814,13 @@ static int batch_create_impl(fb_batch* b) {
     if (strncmp(prop.gcnArchName, "gfx942", 6) != 0 && strncmp(prop.gcnArchName, "gfx950", 6) != 0) b->nq = 0;
     if (const char* e_ = getenv("FB_TICKET_SLOTS")) b->slots = atoi(e_);             // (test switch: pretend fewer resident slots)
 #endif
-    HIPCHK(hipMalloc((void**)&b->tick, 16*16*sizeof(int)));
-    HIPCHK(hipMalloc((void**)&b->done, n_env*sizeof(int)));
-    HIPCHK(hipMalloc((void**)&b->torder, (size_t)(n_env + 16)*sizeof(int)));
-    HIPCHK(hipMalloc((void**)&b->sched_err, sizeof(int)));
-    HIPCHK(hipMemset(b->sched_err, 0, sizeof(int)));
-    HIPCHK(hipMalloc((void**)&b->probe_word, sizeof(unsigned)));
+    if (b->tick.alloc(16*16) || b->done.alloc(n_env) || b->torder.alloc((size_t)n_env + 16) || b->sched_err.alloc_zeroed(1) || b->probe_word.alloc(1)) return -1;
     // (round 3 kept flight_imitation -- equal-cost environments, short substeps -- on the per-wave path: tickets cost 3 % there.  With
     // the round-4 kernel they win for flight too: 8192 FP64 environments 2.21 -> 2.25 M env-steps/s on the default build, 2.52 -> 2.63 M
     // on the 12-per-CU build, profiles/r4/flight_variants.txt.  FB_NO_TICKETS=1 still forces the per-wave path.)
     b->tickets = b->nq > 0 && b->slots > 0 && n_env > b->slots && getenv("FB_NO_TICKETS") == nullptr;
   }
   b->use_prio = getenv("FB_NO_PRIO") == nullptr;
-  HIPCHK(hipMemset(b->reward, 0, n_env*sizeof(float)));
-  HIPCHK(hipMemset(b->discount, 0, n_env*sizeof(float)));
-  HIPCHK(hipMemset(b->step_type, 0, n_env*sizeof(int)));
   // initial state: qpos0 everywhere (fb_batch_reset overrides it once a reference is set)
   if (with_model(b, [&](auto& M) {
         std::vector<decltype(M.timestep)> rows((size_t)n_env*m->nq);
@@ -1326,7 +828,7 @@ static int batch_create_impl(fb_batch* b) {
           const double* q0 = (b->models.empty() ? m : b->models[e % b->n_models()])->d("qpos0");
           std::copy_n(q0, m->nq, rows.data() + (size_t)e*m->nq);
         }
-        HIPCHK(hipMemcpy2D((char*)b->rarena + (size_t)b->off.qpos*rs, (size_t)b->off.nreal*rs, rows.data(), (size_t)m->nq*rs, (size_t)m->nq*rs, n_env, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy2D((char*)b->rarena.get() + (size_t)b->off.qpos*rs, (size_t)b->off.nreal*rs, rows.data(), (size_t)m->nq*rs, (size_t)m->nq*rs, n_env, hipMemcpyHostToDevice));
         return 0; })) return -1;
   b->nobs = 0;
   return 0;
@@ -1335,14 +837,7 @@ static int batch_create_impl(fb_batch* b) {
 extern "C" void fb_batch_destroy(fb_batch* b) {
   if (!b) return;
   (void)hipSetDevice(b->device);
-  for (void* p : b->allocs) (void)hipFree(p);
-  void* frees_[] = {b->rarena, b->iarena, b->obs, b->reward, b->discount, b->step_type, b->d_ids, b->sched, b->cost, b->order, b->ref_qpos, b->ref_qvel, b->dM, b->tick, b->done, b->sched_err, b->park, b->probe_word, b->torder, b->ik_err, b->ik_steps, b->ik_buf, b->inv_qfrc, b->inv_cforce, b->qfrc_applied, b->xfrc_applied, b->env_model, b->law_coef, b->law_out, b->law_qadr, b->fd_pool_r, b->fd_pool_i, b->fd_stage, b->fd_env, b->fd_counter};
-  for (void* p : frees_) (void)hipFree(p);
-
-  if (b->ev0) (void)hipEventDestroy(b->ev0);
-  if (b->ev1) (void)hipEventDestroy(b->ev1);
-  for (hipEvent_t e_ : b->lev) (void)hipEventDestroy(e_);
-  delete b;
+  delete b;                             // (its DevBuf / DevEvent members release the device memory and the events)
 }
 
 extern "C" int fb_batch_set_reference(fb_batch* b, const double* ref_qpos, const double* ref_qvel, int T,
@@ -1350,8 +845,7 @@ extern "C" int fb_batch_set_reference(fb_batch* b, const double* ref_qpos, const
   if (!b || !ref_qpos || !ref_qvel || T < 2) return fail("fb_batch_set_reference: bad arguments");
   if (T - future_steps - 1 < 1) return fail("fb_batch_set_reference: trajectory shorter than future_steps + 2");
   HIPCHK(hipSetDevice(b->device));
-  (void)hipFree(b->ref_qpos); (void)hipFree(b->ref_qvel);
-  b->ref_qpos = b->ref_qvel = nullptr; b->have_ref = false;     // (a failed allocation below must not leave dangling pointers)
+  b->ref_qpos.reset(); b->ref_qvel.reset(); b->have_ref = false;     // (a failure below leaves the batch without a reference)
   const fb_model* m = b->m;
   int max_steps = (int)floor(time_limit / m->d("opt_control_timestep")[0] + 0.5) + 1;
   int snippet = T - future_steps - 1;
@@ -1363,12 +857,11 @@ extern "C" int fb_batch_set_reference(fb_batch* b, const double* ref_qpos, const
   return with_model(b, [&](auto& M) {
     using real = decltype(M.timestep);
     const std::vector<real> q(ref_qpos, ref_qpos + (size_t)T*7), v(ref_qvel, ref_qvel + (size_t)T*6);
-    HIPCHK(hipMalloc(&b->ref_qpos, q.size()*sizeof(real)));
-    HIPCHK(hipMalloc(&b->ref_qvel, v.size()*sizeof(real)));
-    HIPCHK(hipMemcpy(b->ref_qpos, q.data(), q.size()*sizeof(real), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(b->ref_qvel, v.data(), v.size()*sizeof(real), hipMemcpyHostToDevice));
+    if (b->ref_qpos.alloc(q.size()*sizeof(real)) || b->ref_qvel.alloc(v.size()*sizeof(real))) return -1;
+    HIPCHK(hipMemcpy(b->ref_qpos.get(), q.data(), q.size()*sizeof(real), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(b->ref_qvel.get(), v.data(), v.size()*sizeof(real), hipMemcpyHostToDevice));
     if (alloc_obs(b, obs_width(m, m->task_id == FB_TASK_TEMPLATE ? 0 : future_steps + 1, false))) return -1;      // (template_task: the reference is the start pose only, no reference observables)
-    M.ref_qpos = (const real*)b->ref_qpos; M.ref_qvel = (const real*)b->ref_qvel; M.T = T;
+    M.ref_qpos = (const real*)b->ref_qpos.get(); M.ref_qvel = (const real*)b->ref_qvel.get(); M.T = T;
     M.future_steps = future_steps; M.episode_steps = episode_steps; M.nobs = b->nobs;
     M.terminal_com_dist = (real)terminal_com_dist; M.time_limit = (real)time_limit;
     b->have_ref = true;
@@ -1475,12 +968,12 @@ extern "C" int fb_batch_set_flight_dataset(fb_batch* b, const fb_flight_dataset*
 template <typename real>
 static void launch_fly(fb_batch* b, int mode, const float* action, const int* ids, int n, int nsub, hipStream_t st, bool tickets, const int* tord) {
   constexpr int EPB = LdsCfg<real>::EPB;
-  const DevModel<real>* dM = (const DevModel<real>*)b->dM;          // (a grouped batch: the array of the group's model structs)
-  Batch<real> B = {(real*)b->rarena, b->iarena, b->obs, b->reward, b->discount, b->step_type, b->n_env, b->nobs, b->use_prio ? b->sched : nullptr, b->cost,
-                   tickets ? b->tick : nullptr, b->done, b->nq, b->sched_err, tord, (real*)b->park};
-  const ForceArgs<real> F = {(const real*)b->qfrc_applied, (const real*)b->xfrc_applied};
-  const LawArgs<real> L = {(const real*)b->law_coef, b->law_qadr, (real*)b->law_out, b->law_rows > 1 || b->n_env == 1 ? 1 : 0};
-  const GroupArgs G = {b->env_model, b->n_models()};
+  const DevModel<real>* dM = (const DevModel<real>*)b->dM.get();    // (a grouped batch: the array of the group's model structs)
+  Batch<real> B = {(real*)b->rarena.get(), b->iarena.get(), b->obs.get(), b->reward.get(), b->discount.get(), b->step_type.get(), b->n_env, b->nobs,
+                   b->use_prio ? b->sched.get() : nullptr, b->cost.get(), tickets ? b->tick.get() : nullptr, b->done.get(), b->nq, b->sched_err.get(), tord, (real*)b->park.get()};
+  const ForceArgs<real> F = {(const real*)b->qfrc_applied.get(), (const real*)b->xfrc_applied.get()};
+  const LawArgs<real> L = {(const real*)b->law_coef.get(), b->law_qadr.get(), (real*)b->law_out.get(), b->law_rows > 1 || b->n_env == 1 ? 1 : 0};
+  const GroupArgs G = {b->env_model.get(), b->n_models()};
   const dim3 grid((n + EPB - 1)/EPB), block(FB_WAVE*EPB);
   auto go = [&](auto kernel, auto... args) { hipLaunchKernelGGL(kernel, grid, block, 0, st, dM, B, args...); };
   if (b->n_models() > 1) {
@@ -1498,7 +991,7 @@ static void launch_fly(fb_batch* b, int mode, const float* action, const int* id
 static int launch(fb_batch* b, int mode, const float* action, const int* ids, int n, int nsub, void* stream) {
   hipStream_t st = (hipStream_t)stream;
   if (sync_model(b)) return -1;
-  HIPCHK(hipMemsetAsync(b->sched, 0, FB_NSCHED*sizeof(int), st));
+  HIPCHK(hipMemsetAsync(b->sched.get(), 0, FB_NSCHED*sizeof(int), st));
   // a control step of the whole batch: substep scheduler when the batch exceeds the resident slots, otherwise one environment per
   // wave in longest-first order
   bool tickets = (mode == MODE_STEP) && !ids && n == b->n_env && b->tickets;
@@ -1514,30 +1007,30 @@ static int launch(fb_batch* b, int mode, const float* action, const int* ids, in
     if (cap != hipStreamCaptureStatusNone) tickets = false;
     else {
       unsigned hmask = 0;
-      HIPCHK(hipMemsetAsync(b->probe_word, 0, sizeof(unsigned), st));
-      hipLaunchKernelGGL(k_probe_xcc, dim3(4096), dim3(FB_WAVE), 0, st, b->probe_word);
-      HIPCHK(hipMemcpyAsync(&hmask, b->probe_word, sizeof(unsigned), hipMemcpyDeviceToHost, st)); HIPCHK(hipStreamSynchronize(st));
+      HIPCHK(hipMemsetAsync(b->probe_word.get(), 0, sizeof(unsigned), st));
+      hipLaunchKernelGGL(k_probe_xcc, dim3(4096), dim3(FB_WAVE), 0, st, b->probe_word.get());
+      HIPCHK(hipMemcpyAsync(&hmask, b->probe_word.get(), sizeof(unsigned), hipMemcpyDeviceToHost, st)); HIPCHK(hipStreamSynchronize(st));
       if (hmask != b->xcc_mask) { b->tickets = false; tickets = false; }
       else { if (b->probed_streams.size() >= 64) b->probed_streams.clear(); b->probed_streams.push_back(stream); }
     }
   }
 #endif
   const bool full_step = (mode == MODE_STEP) && !ids && n == b->n_env && b->reorder && !tickets;
-  if (full_step && b->order_valid) ids = b->order;       // slowest environments of the previous step first
+  if (full_step && b->order_valid) ids = b->order.get();       // slowest environments of the previous step first
   if (tickets) {
-    HIPCHK(hipMemsetAsync(b->tick, 0, 16*16*sizeof(int), st)); HIPCHK(hipMemsetAsync(b->done, 0, (size_t)n*sizeof(int), st));
-    if (b->ticket_order) hipLaunchKernelGGL(k_ticket_order, dim3(b->nq), dim3(FB_ORDER_THREADS), 0, st, (const int*)b->iarena, (int)b->off.nint, (int)(b->off.istate + IS_NEFC), b->torder, n, b->nq);
+    HIPCHK(hipMemsetAsync(b->tick.get(), 0, 16*16*sizeof(int), st)); HIPCHK(hipMemsetAsync(b->done.get(), 0, (size_t)n*sizeof(int), st));
+    if (b->ticket_order) hipLaunchKernelGGL(k_ticket_order, dim3(b->nq), dim3(FB_ORDER_THREADS), 0, st, (const int*)b->iarena.get(), (int)b->off.nint, (int)(b->off.istate + IS_NEFC), b->torder.get(), n, b->nq);
   }
-  const int* tord = (tickets && b->ticket_order) ? b->torder : nullptr;
+  const int* tord = (tickets && b->ticket_order) ? b->torder.get() : nullptr;
   const int FB_TIMED_MAX = 2048;
   const bool per_launch = b->timing && mode == MODE_STEP && b->timed_launches < FB_TIMED_MAX;
   if (per_launch) {
-    while ((int)b->lev.size() < 2*(b->timed_launches + 1)) { hipEvent_t nev; HIPCHK(hipEventCreate(&nev)); b->lev.push_back(nev); }
-    HIPCHK(hipEventRecord(b->lev[2*b->timed_launches], st));
+    while ((int)b->lev.size() < 2*(b->timed_launches + 1)) { DevEvent nev; if (nev.create()) return -1; b->lev.push_back(std::move(nev)); }
+    HIPCHK(hipEventRecord(b->lev[2*b->timed_launches].get(), st));
   }
   with_model(b, [&](auto& M) { launch_fly<decltype(M.timestep)>(b, mode, action, ids, n, nsub, st, tickets, tord); });
-  if (per_launch) HIPCHK(hipEventRecord(b->lev[2*b->timed_launches + 1], st));
-  if (full_step) { hipLaunchKernelGGL(k_order, dim3(1), dim3(FB_ORDER_THREADS), 0, st, b->cost, b->order, n); b->order_valid = true; }
+  if (per_launch) HIPCHK(hipEventRecord(b->lev[2*b->timed_launches + 1].get(), st));
+  if (full_step) { hipLaunchKernelGGL(k_order, dim3(1), dim3(FB_ORDER_THREADS), 0, st, b->cost.get(), b->order.get(), n); b->order_valid = true; }
   HIPCHK(hipGetLastError());
   if (b->timing) b->timed_launches++;
   return 0;
@@ -1557,13 +1050,13 @@ extern "C" int fb_batch_reset(fb_batch* b, const int32_t* env_ids, int n, void* 
   if (env_ids) {
     if (n <= 0 || n > b->n_env) return fail("fb_batch_reset: bad n");
     for (int k = 0; k < n; k++) if (env_ids[k] < 0 || env_ids[k] >= b->n_env) return fail("fb_batch_reset: env id out of range");
-    HIPCHK(hipMemcpyAsync(b->d_ids, env_ids, n*sizeof(int), hipMemcpyHostToDevice, (hipStream_t)stream));
+    HIPCHK(hipMemcpyAsync(b->d_ids.get(), env_ids, n*sizeof(int), hipMemcpyHostToDevice, (hipStream_t)stream));
     if (b->law_out) {                                   // a reset skips the law: FB_QFRC_LAW of the reset environments is zero (k_fly_reset knows no law)
-      hipLaunchKernelGGL(k_zero_rows, dim3(n), dim3(FB_WAVE), 0, (hipStream_t)stream, (uint32_t*)b->law_out, (const int*)b->d_ids, n, (unsigned)(b->m->nv*real_size(b)/4));
+      hipLaunchKernelGGL(k_zero_rows, dim3(n), dim3(FB_WAVE), 0, (hipStream_t)stream, (uint32_t*)b->law_out.get(), (const int*)b->d_ids.get(), n, (unsigned)(b->m->nv*real_size(b)/4));
     }
-    return launch(b, MODE_RESET, nullptr, b->d_ids, n, 0, stream);
+    return launch(b, MODE_RESET, nullptr, b->d_ids.get(), n, 0, stream);
   }
-  if (b->law_out) HIPCHK(hipMemsetAsync(b->law_out, 0, (size_t)b->n_env*b->m->nv*real_size(b), (hipStream_t)stream));
+  if (b->law_out) HIPCHK(hipMemsetAsync(b->law_out.get(), 0, (size_t)b->n_env*b->m->nv*real_size(b), (hipStream_t)stream));
   return launch(b, MODE_RESET, nullptr, nullptr, b->n_env, 0, stream);
 }
 
@@ -1597,7 +1090,7 @@ extern "C" int fb_batch_forget_stream(fb_batch* b, void* stream) {
 // substep scheduler: a control step that abandoned tickets (capped wait, k_fly) left environments half-stepped -- sticky failure
 static int check_sched_errors(fb_batch* b) {
   int n = 0;
-  HIPCHK(hipMemcpy(&n, b->sched_err, sizeof(int), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(&n, b->sched_err.get(), sizeof(int), hipMemcpyDeviceToHost));
   if (n) return fail("substep scheduler: " + std::to_string(n) + " ticket(s) were abandoned because the wait for an environment's previous substep hit its cap; "
                      "the flagged environments (FB_WARN_SCHED_WAIT) are not in a valid state and this batch fails from now on (sticky, include/flybody_engine.h): "
                      "destroy it and create a new one; FB_NO_TICKETS=1 selects the per-wave path");
@@ -1621,7 +1114,7 @@ extern "C" int fb_batch_stage(fb_batch* b, int stage_word, const float* action, 
   if (b->qfrc_applied) return fail("fb_batch_stage: single-stage profiling runs k_fly, which knows no applied forces; call fb_batch_clear_forces first");
   HIPCHK(hipSetDevice(b->device));
   const size_t pool = with_model(b, [](auto& M) { return sizeof(M.timestep)*LdsCfg<decltype(M.timestep)>::POOL; });
-  if (alloc_zeroed_once(&b->park, (size_t)b->n_env*pool)) return -1;
+  if (alloc_zeroed_once(b->park, (size_t)b->n_env*pool)) return -1;
   return launch(b, MODE_STAGE, action, nullptr, b->n_env, stage_word, stream);
 }
 
@@ -1678,21 +1171,17 @@ extern "C" int fb_batch_ik(fb_batch* b, const fb_ik_config* cfg, const double* t
   const size_t tgt_off = ((it.size()*sizeof(int) + 255) & ~(size_t)255), bytes = tgt_off + (size_t)n*3*ns*sizeof(double);
   HIPCHK(hipSetDevice(b->device));
   HIPCHK(hipDeviceSynchronize());                      // (a previous IK launch may still read the buffer)
-  if (alloc_zeroed_once(&b->ik_err, (size_t)n*2*sizeof(double)) || alloc_zeroed_once(&b->ik_steps, (size_t)n*2*sizeof(int))) return -1;
-  if (b->ik_buf_bytes < bytes) {
-    (void)hipFree(b->ik_buf); b->ik_buf = nullptr; b->ik_buf_bytes = 0;
-    HIPCHK(hipMalloc(&b->ik_buf, bytes)); b->ik_buf_bytes = bytes;
-  }
-  HIPCHK(hipMemcpy(b->ik_buf, it.data(), it.size()*sizeof(int), hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy((char*)b->ik_buf + tgt_off, target_xpos, (size_t)n*3*ns*sizeof(double), hipMemcpyHostToDevice));
+  if (alloc_zeroed_once(b->ik_err, (size_t)n*2) || alloc_zeroed_once(b->ik_steps, (size_t)n*2) || b->ik_buf.reserve(bytes)) return -1;
+  HIPCHK(hipMemcpy(b->ik_buf.get(), it.data(), it.size()*sizeof(int), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy((char*)b->ik_buf.get() + tgt_off, target_xpos, (size_t)n*3*ns*sizeof(double), hipMemcpyHostToDevice));
   if (sync_model(b)) return -1;
-  const int* ib = (const int*)b->ik_buf;
+  const int* ib = (const int*)b->ik_buf.get();
   IKArgs<double> A;
   A.site = ib + o_site; A.bsite_off = ib + o_boff; A.bsite = ib + o_bsite; A.include = ib + o_inc; A.dof = ib + o_dof; A.dof_hq = ib + o_hq;
-  A.target = (const double*)((const char*)b->ik_buf + tgt_off); A.err = b->ik_err; A.steps = b->ik_steps;
+  A.target = (const double*)((const char*)b->ik_buf.get() + tgt_off); A.err = b->ik_err.get(); A.steps = b->ik_steps.get();
   A.n_site = ns; A.n_dof = (int)nd; A.max_steps = cfg->max_steps; A.n_env = n;
   A.reg = cfg->reg_strength; A.lr = cfg->lr; A.beta = cfg->beta; A.thr = cfg->progress_threshold;
-  hipLaunchKernelGGL((k_ik<double>), dim3(n), dim3(FB_WAVE), 0, (hipStream_t)stream, (const DevModel<double>*)b->dM, (double*)b->rarena, b->iarena, A);
+  hipLaunchKernelGGL((k_ik<double>), dim3(n), dim3(FB_WAVE), 0, (hipStream_t)stream, (const DevModel<double>*)b->dM.get(), (double*)b->rarena.get(), b->iarena.get(), A);
   HIPCHK(hipGetLastError());
   return 0;
   FB_GUARD_END
@@ -1713,18 +1202,18 @@ extern "C" int fb_batch_inverse(fb_batch* b, int flags, void* stream) {
   HIPCHK(hipDeviceSynchronize());                      // (the qacc check below reads what earlier launches wrote)
   {
     std::vector<double> qacc((size_t)n*nv);
-    HIPCHK(hipMemcpy2D(qacc.data(), (size_t)nv*8, (char*)b->rarena + (size_t)b->off.qacc*8, (size_t)b->off.nreal*8, (size_t)nv*8, n, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy2D(qacc.data(), (size_t)nv*8, (char*)b->rarena.get() + (size_t)b->off.qacc*8, (size_t)b->off.nreal*8, (size_t)nv*8, n, hipMemcpyDeviceToHost));
     for (size_t k = 0; k < qacc.size(); k++)
       if (!std::isfinite(qacc[k])) return fail("fb_batch_inverse: FB_QACC of environment " + std::to_string(k/nv) + " is not finite");
   }
-  if (alloc_zeroed_once(&b->inv_qfrc, (size_t)n*nv*sizeof(double)) || alloc_zeroed_once(&b->inv_cforce, (size_t)n*3*FB_MAXCON_*sizeof(double))) return -1;
+  if (alloc_zeroed_once(b->inv_qfrc, (size_t)n*nv) || alloc_zeroed_once(b->inv_cforce, (size_t)n*3*FB_MAXCON_)) return -1;
   if (sync_model(b)) return -1;
   InvArgs<double> A;
-  A.qfrc_inverse = b->inv_qfrc; A.contact_force = b->inv_cforce; A.n_env = n;
+  A.qfrc_inverse = b->inv_qfrc.get(); A.contact_force = b->inv_cforce.get(); A.n_env = n;
   A.flags = (flags & FB_INV_DISCRETE) ? FB_INV_FLAG_DISCRETE : 0;
   constexpr int EPB = LdsCfg<double>::EPB;
-  hipLaunchKernelGGL((k_inverse<double>), dim3((n + EPB - 1)/EPB), dim3(FB_WAVE*EPB), 0, (hipStream_t)stream, (const DevModel<double>*)b->dM,
-                     (double*)b->rarena, b->iarena, A);
+  hipLaunchKernelGGL((k_inverse<double>), dim3((n + EPB - 1)/EPB), dim3(FB_WAVE*EPB), 0, (hipStream_t)stream, (const DevModel<double>*)b->dM.get(),
+                     (double*)b->rarena.get(), b->iarena.get(), A);
   HIPCHK(hipGetLastError());
   return 0;
   FB_GUARD_END
@@ -1773,44 +1262,38 @@ extern "C" int fb_batch_transition_fd(fb_batch* b, const fb_fd_config* cfg, doub
   const int nf = cfg->n_frames, ndx = 2*m->nv + m->na, nst = m->nq + m->nv + m->na + FB_NSENS;
   const int c0 = (A || Cm) ? 0 : ndx, c1 = (Bm || Dm) ? ndx + m->nu : ndx, sides = cfg->centered ? 2 : 1, per_frame = 1 + sides*(c1 - c0);
   if (c1 <= c0) return fail("fb_batch_transition_fd: the outputs asked for have no column (a model without controls has no B or D)");
-  if (alloc_zeroed_once(&b->fd_pool_r,(size_t)b->fd_slots*b->off.nreal*sizeof(double)) || alloc_zeroed_once(&b->fd_pool_i, (size_t)b->fd_slots*b->off.nint*sizeof(int)) ||
-      alloc_zeroed_once(&b->fd_counter, 2*sizeof(int))) return -1;
+  if (alloc_zeroed_once(b->fd_pool_r, (size_t)b->fd_slots*b->off.nreal) || alloc_zeroed_once(b->fd_pool_i, (size_t)b->fd_slots*b->off.nint) ||
+      alloc_zeroed_once(b->fd_counter, 2)) return -1;
   // frames per chunk: the tickets' staging slots stay inside the budget
   const size_t frame_bytes = (size_t)per_frame*nst*sizeof(double);
   const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)nf, FB_FD_STAGING_BYTES/frame_bytes));
-  if (b->fd_stage_bytes < chunk*frame_bytes || b->fd_env_cap < nf) {
+  const size_t stage_n = chunk*frame_bytes/sizeof(double);
+  if (b->fd_stage.count() < stage_n || b->fd_env.count() < (size_t)nf) {
     HIPCHK(hipDeviceSynchronize());                    // (an earlier call may still use the buffers)
-    if (b->fd_stage_bytes < chunk*frame_bytes) {
-      (void)hipFree(b->fd_stage); b->fd_stage = nullptr; b->fd_stage_bytes = 0;
-      HIPCHK(hipMalloc((void**)&b->fd_stage, chunk*frame_bytes)); b->fd_stage_bytes = chunk*frame_bytes;
-    }
-    if (b->fd_env_cap < nf) {
-      (void)hipFree(b->fd_env); b->fd_env = nullptr; b->fd_env_cap = 0;
-      HIPCHK(hipMalloc((void**)&b->fd_env, (size_t)nf*sizeof(int))); b->fd_env_cap = nf;
-    }
+    if (b->fd_stage.reserve(stage_n) || b->fd_env.reserve(nf)) return -1;
   }
   b->fd_env_host.resize(nf);
   for (int k = 0; k < nf; k++) b->fd_env_host[k] = cfg->env_ids ? cfg->env_ids[k] : k;
-  HIPCHK(hipMemcpyAsync(b->fd_env, b->fd_env_host.data(), (size_t)nf*sizeof(int), hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(b->fd_env.get(), b->fd_env_host.data(), (size_t)nf*sizeof(int), hipMemcpyHostToDevice, st));
   if (sync_model(b)) return -1;
   if (status) HIPCHK(hipMemsetAsync(status, 0, (size_t)nf*sizeof(int32_t), st));
-  HIPCHK(hipMemsetAsync(b->fd_counter, 0, 2*sizeof(int), st));
+  HIPCHK(hipMemsetAsync(b->fd_counter.get(), 0, 2*sizeof(int), st));
   constexpr int EPB = LdsCfg<double>::EPB;
   const int pool = cfg->pool_rows > 0 ? cfg->pool_rows : b->fd_slots;
   for (int lo = 0; lo < nf; lo += chunk) {
     const int n = std::min(chunk, nf - lo);
     FdArgs<double> F;
-    F.rarena = (const double*)b->rarena; F.iarena = b->iarena; F.pool_r = b->fd_pool_r; F.pool_i = b->fd_pool_i;
-    F.frame_env = b->fd_env + lo; F.stage = b->fd_stage; F.counter = b->fd_counter; F.status = status ? (int*)status + lo : nullptr;
+    F.rarena = (const double*)b->rarena.get(); F.iarena = b->iarena.get(); F.pool_r = b->fd_pool_r.get(); F.pool_i = b->fd_pool_i.get();
+    F.frame_env = b->fd_env.get() + lo; F.stage = b->fd_stage.get(); F.counter = b->fd_counter.get(); F.status = status ? (int*)status + lo : nullptr;
     F.A = A ? A + (size_t)lo*ndx*ndx : nullptr; F.B = Bm ? Bm + (size_t)lo*ndx*m->nu : nullptr;
     F.C = Cm ? Cm + (size_t)lo*FB_NSENS*ndx : nullptr; F.D = Dm ? Dm + (size_t)lo*FB_NSENS*m->nu : nullptr;
     F.eps = cfg->eps; F.n_frames = n; F.c0 = c0; F.c1 = c1; F.centered = cfg->centered; F.n_substeps = cfg->n_substeps;
     F.skip_tail = (!Cm && !Dm) ? 1 : 0;
     const long long tickets = (long long)n*per_frame;
     F.nwave = (int)std::min<long long>(pool, tickets);
-    if (lo > 0) HIPCHK(hipMemsetAsync(b->fd_counter, 0, sizeof(int), st));      // (the next-ticket word; the run count goes on)
-    hipLaunchKernelGGL((k_transition_fd<double>), dim3((F.nwave + EPB - 1)/EPB), dim3(FB_WAVE*EPB), 0, st, (const DevModel<double>*)b->dM, F);
-    hipLaunchKernelGGL((k_fd_assemble<double>), dim3(n*(c1 - c0)), dim3(FB_WAVE), 0, st, (const DevModel<double>*)b->dM, F);
+    if (lo > 0) HIPCHK(hipMemsetAsync(b->fd_counter.get(), 0, sizeof(int), st));      // (the next-ticket word; the run count goes on)
+    hipLaunchKernelGGL((k_transition_fd<double>), dim3((F.nwave + EPB - 1)/EPB), dim3(FB_WAVE*EPB), 0, st, (const DevModel<double>*)b->dM.get(), F);
+    hipLaunchKernelGGL((k_fd_assemble<double>), dim3(n*(c1 - c0)), dim3(FB_WAVE), 0, st, (const DevModel<double>*)b->dM.get(), F);
   }
   HIPCHK(hipGetLastError());
   return 0;
@@ -1826,7 +1309,7 @@ extern "C" int fb_batch_fd_tickets(fb_batch* b, int64_t* n) {
   HIPCHK(hipSetDevice(b->device));
   HIPCHK(hipDeviceSynchronize());
   int c[2] = {0, 0};
-  HIPCHK(hipMemcpy(c, b->fd_counter, sizeof(c), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(c, b->fd_counter.get(), sizeof(c), hipMemcpyDeviceToHost));
   *n = c[1];
   return 0;
 }
@@ -1870,24 +1353,24 @@ static int field_desc(fb_batch* b, int field, FieldDesc* f) {
     case FB_GEOM_XPOS: *f = {REAL_ARENA, o.gxpos, (size_t)3*m->ngeom}; break;
     case FB_GEOM_XMAT: *f = {REAL_ARENA, o.gxmat, (size_t)9*m->ngeom}; break;
     case FB_CVEL: *f = {REAL_ARENA, o.cvel, (size_t)6*m->nbody}; break;
-    case FB_OBS: *f = {F32_ARRAY, 0, (size_t)b->nobs, b->obs, no_ref}; break;
-    case FB_REWARD: *f = {F32_ARRAY, 0, 1, b->reward}; break;
-    case FB_DISCOUNT: *f = {F32_ARRAY, 0, 1, b->discount}; break;
-    case FB_STEP_TYPE: *f = {I32_ARRAY, 0, 1, b->step_type}; break;
+    case FB_OBS: *f = {F32_ARRAY, 0, (size_t)b->nobs, b->obs.get(), no_ref}; break;
+    case FB_REWARD: *f = {F32_ARRAY, 0, 1, b->reward.get()}; break;
+    case FB_DISCOUNT: *f = {F32_ARRAY, 0, 1, b->discount.get()}; break;
+    case FB_STEP_TYPE: *f = {I32_ARRAY, 0, 1, b->step_type.get()}; break;
     case FB_WARN: *f = {INT_ARENA, o.istate + IS_WARN, 1}; break;
     case FB_WARN_EVER: *f = {INT_ARENA, o.istate + IS_WARN_EVER, 1}; break;
     case FB_SIZE_STATS: *f = {INT_ARENA, o.istate + IS_MAX_NCON, 4}; break;
-    case FB_STEP_TICKS: *f = {I32_ARRAY, 0, 1, b->cost}; break;
-    case FB_LAUNCH_ORDER: *f = {I32_ARRAY, 0, 1, b->order}; break;
+    case FB_STEP_TICKS: *f = {I32_ARRAY, 0, 1, b->cost.get()}; break;
+    case FB_LAUNCH_ORDER: *f = {I32_ARRAY, 0, 1, b->order.get()}; break;
     case FB_SITE_XPOS: *f = {REAL_ARENA, o.sxpos, (size_t)3*m->nsite}; break;
-    case FB_IK_ERR: *f = {F64_ARRAY, 0, 2, b->ik_err, no_ik}; break;
-    case FB_IK_STEPS: *f = {I32_ARRAY, 0, 2, b->ik_steps, no_ik}; break;
-    case FB_QFRC_INVERSE: *f = {F64_ARRAY, 0, (size_t)m->nv, b->inv_qfrc, no_inv}; break;
-    case FB_CONTACT_FORCE: *f = {F64_ARRAY, 0, (size_t)3*FB_MAXCON_, b->inv_cforce, no_inv}; break;
-    case FB_QFRC_APPLIED: *f = {REAL_ARRAY, 0, (size_t)m->nv, b->qfrc_applied, no_frc}; break;
-    case FB_XFRC_APPLIED: *f = {REAL_ARRAY, 0, (size_t)6*m->nbody, b->xfrc_applied, no_frc}; break;
-    case FB_ENV_MODEL: *f = {I32_ARRAY, 0, 1, b->env_model, no_grp}; break;
-    case FB_QFRC_LAW: *f = {REAL_ARRAY, 0, (size_t)m->nv, b->law_out, "fb_batch_get: no control law (fb_batch_set_control_law sets one)"}; break;
+    case FB_IK_ERR: *f = {F64_ARRAY, 0, 2, b->ik_err.get(), no_ik}; break;
+    case FB_IK_STEPS: *f = {I32_ARRAY, 0, 2, b->ik_steps.get(), no_ik}; break;
+    case FB_QFRC_INVERSE: *f = {F64_ARRAY, 0, (size_t)m->nv, b->inv_qfrc.get(), no_inv}; break;
+    case FB_CONTACT_FORCE: *f = {F64_ARRAY, 0, (size_t)3*FB_MAXCON_, b->inv_cforce.get(), no_inv}; break;
+    case FB_QFRC_APPLIED: *f = {REAL_ARRAY, 0, (size_t)m->nv, b->qfrc_applied.get(), no_frc}; break;
+    case FB_XFRC_APPLIED: *f = {REAL_ARRAY, 0, (size_t)6*m->nbody, b->xfrc_applied.get(), no_frc}; break;
+    case FB_ENV_MODEL: *f = {I32_ARRAY, 0, 1, b->env_model.get(), no_grp}; break;
+    case FB_QFRC_LAW: *f = {REAL_ARRAY, 0, (size_t)m->nv, b->law_out.get(), "fb_batch_get: no control law (fb_batch_set_control_law sets one)"}; break;
     case FB_CONTROL_LAW: return fail("FB_CONTROL_LAW is [n_rows][5][nv], not one row per environment: read and write it through fb_batch_device_ptr, set it with fb_batch_set_control_law");
     default: return fail("unknown field");
   }
@@ -1900,14 +1383,10 @@ static int alloc_forces(fb_batch* b) {
   if (b->qfrc_applied && b->xfrc_applied) return 0;
   const size_t rs = real_size(b);
   HIPCHK(hipDeviceSynchronize());
-  void *q = nullptr, *x = nullptr;
-  const size_t nq_ = (size_t)b->n_env*b->m->nv*rs, nx_ = (size_t)b->n_env*6*b->m->nbody*rs;
-  if (hipMalloc(&q, nq_) != hipSuccess || hipMalloc(&x, nx_) != hipSuccess || hipMemset(q, 0, nq_) != hipSuccess || hipMemset(x, 0, nx_) != hipSuccess) {
-    (void)hipFree(q); (void)hipFree(x); (void)hipGetLastError();
-    return fail("applied forces: device allocation failed");
-  }
+  DevBuf<void> q, x;                                   // (both or neither: a failure gives back what it got)
+  if (q.alloc_zeroed((size_t)b->n_env*b->m->nv*rs) || x.alloc_zeroed((size_t)b->n_env*6*b->m->nbody*rs)) return fail("applied forces: device allocation failed");
   HIPCHK(hipDeviceSynchronize());                      // (the zeroes are there before a launch on any stream reads them)
-  b->qfrc_applied = q; b->xfrc_applied = x;
+  b->qfrc_applied = std::move(q); b->xfrc_applied = std::move(x);
   return 0;
 }
 
@@ -1916,8 +1395,7 @@ extern "C" int fb_batch_clear_forces(fb_batch* b) {
   if (b->law_coef) return fail("fb_batch_clear_forces: a control law is set, and its kernel (k_step_law) reads the force arrays; call fb_batch_set_control_law(batch, NULL) first");
   HIPCHK(hipSetDevice(b->device));
   HIPCHK(hipDeviceSynchronize());                      // (a launch in flight may still read the arrays)
-  (void)hipFree(b->qfrc_applied); (void)hipFree(b->xfrc_applied);
-  b->qfrc_applied = b->xfrc_applied = nullptr;
+  b->qfrc_applied.reset(); b->xfrc_applied.reset();
   return 0;
 }
 
@@ -1933,8 +1411,7 @@ extern "C" int fb_batch_set_control_law(fb_batch* b, const fb_control_law* law) 
   HIPCHK(hipSetDevice(b->device));
   if (!law) {
     HIPCHK(hipDeviceSynchronize());                    // (a launch in flight may still read the law)
-    (void)hipFree(b->law_coef); (void)hipFree(b->law_out); (void)hipFree(b->law_qadr);
-    b->law_coef = b->law_out = nullptr; b->law_qadr = nullptr; b->law_rows = 0;
+    b->law_coef.reset(); b->law_out.reset(); b->law_qadr.reset(); b->law_rows = 0;
     if (b->law_owns_forces) { b->law_owns_forces = false; return fb_batch_clear_forces(b); }
     return 0;
   }
@@ -1958,26 +1435,23 @@ extern "C" int fb_batch_set_control_law(fb_batch* b, const fb_control_law* law) 
                     (jt[djnt[k % nv]] == JNT_FREE ? "free" : "ball") + " joint, which has no scalar position; position feedback is for hinge dofs only");
     }
   }
-  const bool had_forces = b->qfrc_applied != nullptr;
+  const bool had_forces = (bool)b->qfrc_applied;
   if (alloc_forces(b)) return -1;
   if (!had_forces) b->law_owns_forces = true;
   HIPCHK(hipDeviceSynchronize());
-  // Everything the new law needs is allocated and filled first and swapped in last: a failure on the way leaves the batch as it was, the
-  // previous law included (a block of another row count is a new block; the old one is freed after the swap).
+  // Whatever the new law needs and the batch does not have yet is allocated in locals, filled, and moved in last: a failure on the way leaves
+  // the batch as it was, the previous law included (a block of another row count is a new block; the move frees the old one).
   const size_t rs = real_size(b);
   const bool reuse = b->law_coef && b->law_rows == nr;
-  void *coef = reuse ? b->law_coef : nullptr, *out = b->law_out; int* qa = b->law_qadr;
-  auto undo = [&](const char* why) {
-    if (!reuse) (void)hipFree(coef);
-    if (!b->law_out) (void)hipFree(out);
-    if (!b->law_qadr) (void)hipFree(qa);
+  DevBuf<void> new_coef, new_out; DevBuf<int> new_qa;
+  auto undo = [&](const char* why) {                   // (the locals free themselves; the forces this call brought are the batch's by now)
     if (!had_forces && !b->law_coef) { b->law_owns_forces = false; (void)fb_batch_clear_forces(b); }
     (void)hipGetLastError();
     return fail(std::string("fb_batch_set_control_law: ") + why);
   };
-  if (!coef && hipMalloc(&coef, (size_t)nr*LAW_NROW*nv*rs) != hipSuccess) { coef = nullptr; return undo("device allocation failed"); }
-  if (!qa && hipMalloc((void**)&qa, nv*sizeof(int)) != hipSuccess) { qa = nullptr; return undo("device allocation failed"); }
-  if (!out && (hipMalloc(&out, (size_t)n*nv*rs) != hipSuccess || hipMemset(out, 0, (size_t)n*nv*rs) != hipSuccess)) return undo("device allocation failed");
+  if ((!reuse && new_coef.alloc((size_t)nr*LAW_NROW*nv*rs)) || (!b->law_qadr && new_qa.alloc(nv)) || (!b->law_out && new_out.alloc_zeroed((size_t)n*nv*rs)))
+    return undo("device allocation failed");
+  void* coef = reuse ? b->law_coef.get() : new_coef.get(); int* qa = b->law_qadr ? b->law_qadr.get() : new_qa.get();
   if (hipMemcpy(qa, qadr.data(), nv*sizeof(int), hipMemcpyHostToDevice) != hipSuccess) return undo("copy to the device failed");
   const int rc = with_model(b, [&](auto& M) {
     std::vector<decltype(M.timestep)> tmp((size_t)nr*LAW_NROW*nv, 0);
@@ -1986,9 +1460,10 @@ extern "C" int fb_batch_set_control_law(fb_batch* b, const fb_control_law* law) 
     return hipMemcpy(coef, tmp.data(), tmp.size()*sizeof(tmp[0]), hipMemcpyHostToDevice) == hipSuccess ? 0 : -1;
   });
   if (rc || hipDeviceSynchronize() != hipSuccess) return undo("copy to the device failed");
-  void* old = reuse ? nullptr : b->law_coef;
-  b->law_coef = coef; b->law_rows = nr; b->law_out = out; b->law_qadr = qa;
-  (void)hipFree(old);
+  if (new_coef) b->law_coef = std::move(new_coef);
+  if (new_out) b->law_out = std::move(new_out);
+  if (new_qa) b->law_qadr = std::move(new_qa);
+  b->law_rows = nr;
   return 0;
   FB_GUARD_END
 }
@@ -2001,8 +1476,8 @@ extern "C" int fb_batch_control_law_active(const fb_batch* b) {
 extern "C" int fb_batch_end_episode(fb_batch* b, const uint8_t* mask_dev, const float* discount_dev, void* stream) {
   if (!b || !mask_dev) return fail("fb_batch_end_episode: null argument");
   HIPCHK(hipSetDevice(b->device));
-  hipLaunchKernelGGL(k_end_episode, dim3((b->n_env + FB_WAVE - 1)/FB_WAVE), dim3(FB_WAVE), 0, (hipStream_t)stream, b->iarena, (unsigned)b->off.nint, (unsigned)b->off.istate,
-                     b->step_type, b->discount, mask_dev, discount_dev, b->n_env);
+  hipLaunchKernelGGL(k_end_episode, dim3((b->n_env + FB_WAVE - 1)/FB_WAVE), dim3(FB_WAVE), 0, (hipStream_t)stream, b->iarena.get(), (unsigned)b->off.nint, (unsigned)b->off.istate,
+                     b->step_type.get(), b->discount.get(), mask_dev, discount_dev, b->n_env);
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -2012,7 +1487,7 @@ static int real_rows(fb_batch* b, const FieldDesc& f, double* host, bool to_devi
   return with_model(b, [&](auto& M) {
     using real = decltype(M.timestep);
     const size_t row = f.width*sizeof(real), pitch = (size_t)b->off.nreal*sizeof(real);
-    char* dev = (char*)b->rarena + f.off*sizeof(real);
+    char* dev = (char*)b->rarena.get() + f.off*sizeof(real);
     std::vector<real> tmp((size_t)b->n_env*f.width);
     if (to_device) std::copy(host, host + tmp.size(), tmp.begin());
     HIPCHK(to_device ? hipMemcpy2D(dev, pitch, tmp.data(), row, row, b->n_env, hipMemcpyHostToDevice)
@@ -2034,8 +1509,8 @@ extern "C" int fb_batch_get(fb_batch* b, int field, void* dst, size_t bytes) {
     return with_model(b, [&](auto& M) {
       std::vector<decltype(M.timestep)> rr((size_t)n*b->off.nreal);
       std::vector<int> ii((size_t)n*b->off.nint);
-      HIPCHK(hipMemcpy(rr.data(), b->rarena, rr.size()*sizeof(rr[0]), hipMemcpyDeviceToHost));
-      HIPCHK(hipMemcpy(ii.data(), b->iarena, ii.size()*sizeof(int), hipMemcpyDeviceToHost));
+      HIPCHK(hipMemcpy(rr.data(), b->rarena.get(), rr.size()*sizeof(rr[0]), hipMemcpyDeviceToHost));
+      HIPCHK(hipMemcpy(ii.data(), b->iarena.get(), ii.size()*sizeof(int), hipMemcpyDeviceToHost));
       double* out = (double*)dst;
       for (int e = 0; e < n; e++) for (int c = 0; c < FB_MAXCON_; c++) {
         double* o = out + ((size_t)e*FB_MAXCON_ + c)*8;
@@ -2054,7 +1529,7 @@ extern "C" int fb_batch_get(fb_batch* b, int field, void* dst, size_t bytes) {
     return real_rows(b, f, (double*)dst, false);
   } else if (f.kind == INT_ARENA) {
     if (bytes != (size_t)n*f.width*sizeof(int)) return fail("fb_batch_get: size mismatch");
-    HIPCHK(hipMemcpy2D(dst, f.width*4, (char*)b->iarena + f.off*4, (size_t)b->off.nint*4, f.width*4, n, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy2D(dst, f.width*4, (char*)b->iarena.get() + f.off*4, (size_t)b->off.nint*4, f.width*4, n, hipMemcpyDeviceToHost));
   } else if (f.kind == REAL_ARRAY) {
     if (!f.base) return fail(f.unset);
     if (bytes != (size_t)n*f.width*sizeof(double)) return fail("fb_batch_get: size mismatch (physics fields are returned as FP64)");
@@ -2084,7 +1559,7 @@ extern "C" int fb_batch_set(fb_batch* b, int field, const void* src, size_t byte
     return real_rows(b, f, (double*)src, true);
   } else if (f.kind == INT_ARENA) {
     if (bytes != (size_t)n*f.width*sizeof(int)) return fail("fb_batch_set: size mismatch");
-    HIPCHK(hipMemcpy2D((char*)b->iarena + f.off*4, (size_t)b->off.nint*4, src, f.width*4, f.width*4, n, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy2D((char*)b->iarena.get() + f.off*4, (size_t)b->off.nint*4, src, f.width*4, f.width*4, n, hipMemcpyHostToDevice));
   } else if (field == FB_QFRC_LAW) {
     return fail("fb_batch_set: FB_QFRC_LAW is read-only (the law stage writes it; fb_batch_set_control_law sets the law)");
   } else if (f.kind == REAL_ARRAY) {
@@ -2097,7 +1572,7 @@ extern "C" int fb_batch_set(fb_batch* b, int field, const void* src, size_t byte
       if (!std::isfinite(v[k])) return fail(std::string("fb_batch_set: ") + name + " of environment " + std::to_string(k/f.width) + " is not finite");
     if (alloc_forces(b)) return -1;
     b->law_owns_forces = false;
-    void* dev = field == FB_QFRC_APPLIED ? b->qfrc_applied : b->xfrc_applied;
+    void* dev = field == FB_QFRC_APPLIED ? b->qfrc_applied.get() : b->xfrc_applied.get();
     return with_model(b, [&](auto& M) {
       const std::vector<decltype(M.timestep)> tmp(v, v + (size_t)n*f.width);
       HIPCHK(hipMemcpy(dev, tmp.data(), tmp.size()*sizeof(tmp[0]), hipMemcpyHostToDevice));
@@ -2110,7 +1585,7 @@ extern "C" int fb_batch_set(fb_batch* b, int field, const void* src, size_t byte
     const int* v = (const int*)src;
     for (int e = 0; e < n; e++)
       if (v[e] < 0 || v[e] >= b->n_models()) return fail("fb_batch_set: FB_ENV_MODEL of environment " + std::to_string(e) + " is " + std::to_string(v[e]) + ", outside [0, " + std::to_string(b->n_models()) + ")");
-    HIPCHK(hipMemcpy(b->env_model, v, bytes, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(b->env_model.get(), v, bytes, hipMemcpyHostToDevice));
   } else return fail("fb_batch_set: field is read-only");
   return 0;
 }
@@ -2118,19 +1593,19 @@ extern "C" int fb_batch_set(fb_batch* b, int field, const void* src, size_t byte
 extern "C" void* fb_batch_device_ptr(fb_batch* b, int field) {
   if (!b) return nullptr;
   switch (field) {
-    case FB_OBS: return b->obs;
-    case FB_REWARD: return b->reward;
-    case FB_DISCOUNT: return b->discount;
-    case FB_STEP_TYPE: return b->step_type;
-    case FB_ENV_MODEL: return b->env_model;            // (null on a batch made by fb_batch_create)
+    case FB_OBS: return b->obs.get();
+    case FB_REWARD: return b->reward.get();
+    case FB_DISCOUNT: return b->discount.get();
+    case FB_STEP_TYPE: return b->step_type.get();
+    case FB_ENV_MODEL: return b->env_model.get();           // (null on a batch made by fb_batch_create)
     case FB_QFRC_APPLIED: case FB_XFRC_APPLIED:        // (allocates both arrays on first use: the batch is stepped by k_step_forces from then on)
       if (hipSetDevice(b->device) != hipSuccess || alloc_forces(b)) return nullptr;
       b->law_owns_forces = false;
-      return field == FB_QFRC_APPLIED ? b->qfrc_applied : b->xfrc_applied;
+      return field == FB_QFRC_APPLIED ? b->qfrc_applied.get() : b->xfrc_applied.get();
     case FB_QPOS: case FB_QVEL:                        // rows of the arena: environment e's row starts e x (fb_batch_row's row_bytes of the real arena) further on
-      return (char*)b->rarena + (size_t)(field == FB_QPOS ? b->off.qpos : b->off.qvel)*real_size(b);
-    case FB_QFRC_LAW: return b->law_out;               // (null while no law is set)
-    case FB_CONTROL_LAW: return b->law_coef;
+      return (char*)b->rarena.get() + (size_t)(field == FB_QPOS ? b->off.qpos : b->off.qvel)*real_size(b);
+    case FB_QFRC_LAW: return b->law_out.get();         // (null while no law is set)
+    case FB_CONTROL_LAW: return b->law_coef.get();
     default: return nullptr;
   }
 }
@@ -2144,7 +1619,7 @@ extern "C" int fb_batch_row(fb_batch* b, int which, int env, void* host, size_t 
   if (!host || bytes != rb) return fail("fb_batch_row: size mismatch");
   HIPCHK(hipSetDevice(b->device));
   HIPCHK(hipDeviceSynchronize());
-  char* dev = (which == 0 ? (char*)b->rarena : (char*)b->iarena) + (size_t)env*rb;
+  char* dev = (which == 0 ? (char*)b->rarena.get() : (char*)b->iarena.get()) + (size_t)env*rb;
   if (write) HIPCHK(hipMemcpy(dev, host, rb, hipMemcpyHostToDevice)); else HIPCHK(hipMemcpy(host, dev, rb, hipMemcpyDeviceToHost));
   return 0;
 }
@@ -2158,19 +1633,19 @@ extern "C" int fb_batch_scheduler(const fb_batch* b, int* slots) {
 extern "C" int fb_batch_timing_begin(fb_batch* b, void* stream) {
   if (!b) return fail("fb_batch_timing_begin: null batch");
   HIPCHK(hipSetDevice(b->device));
-  if (!b->ev0) { HIPCHK(hipEventCreate(&b->ev0)); HIPCHK(hipEventCreate(&b->ev1)); }
+  if ((!b->ev0 && b->ev0.create()) || (!b->ev1 && b->ev1.create())) return -1;
   b->timed_launches = 0; b->timing = true;
-  HIPCHK(hipEventRecord(b->ev0, (hipStream_t)stream));
+  HIPCHK(hipEventRecord(b->ev0.get(), (hipStream_t)stream));
   return 0;
 }
 
 extern "C" int fb_batch_timing_end(fb_batch* b, void* stream, float* total_ms, int* n_launches) {
   if (!b || !b->timing) return fail("fb_batch_timing_end: timing not started");
   HIPCHK(hipSetDevice(b->device));
-  HIPCHK(hipEventRecord(b->ev1, (hipStream_t)stream));
-  HIPCHK(hipEventSynchronize(b->ev1));
+  HIPCHK(hipEventRecord(b->ev1.get(), (hipStream_t)stream));
+  HIPCHK(hipEventSynchronize(b->ev1.get()));
   float ms = 0;
-  HIPCHK(hipEventElapsedTime(&ms, b->ev0, b->ev1));
+  HIPCHK(hipEventElapsedTime(&ms, b->ev0.get(), b->ev1.get()));
   if (total_ms) *total_ms = ms;
   if (n_launches) *n_launches = b->timed_launches;
   b->timing = false;
@@ -2181,6 +1656,6 @@ extern "C" int fb_batch_timing_launches(fb_batch* b, float* ms, int cap) {
   if (!b || b->timing) return fail("fb_batch_timing_launches: call after fb_batch_timing_end");
   HIPCHK(hipSetDevice(b->device));
   const int n = std::min((int)b->lev.size()/2, std::min(b->timed_launches, cap));
-  for (int k = 0; k < n && ms; k++) HIPCHK(hipEventElapsedTime(ms + k, b->lev[2*k], b->lev[2*k + 1]));
+  for (int k = 0; k < n && ms; k++) HIPCHK(hipEventElapsedTime(ms + k, b->lev[2*k].get(), b->lev[2*k + 1].get()));
   return n;
 }

@@ -69,7 +69,7 @@ def test_build_flags_are_part_of_the_source_hash():
 # tests/test_kernel_emulation.py: FB_SCHED_SPIN_CAP), FB_MPR_PAIRED (derived from FB_EMULATE in fb_collide.hpp) and FB_TICKET_SPLIT (0:
 # folding its arithmetic changes k_fly's code).  A new switch lands together with the build, test or tool that sets it.
 ENGINE_KERNEL_SOURCES = ('fb_collide.hpp', 'fb_constraint.hpp', 'fb_math.hpp', 'fb_newton.hpp', 'fb_smooth.hpp', 'fb_step.hpp', 'fb_types.hpp',
-                         'fb_ik.hpp', 'fb_inverse.hpp', 'fb_engine.hip')
+                         'fb_ik.hpp', 'fb_inverse.hpp', 'fb_forces.hpp', 'fb_law.hpp', 'fb_task.hpp', 'fb_host.hpp', 'fb_model.hpp', 'fb_engine.hip')
 KEPT_SWITCHES = {'FB_EMULATE', 'FB_PROFILE', 'FB_STATS', 'FB_F64_DENSE', 'FB_SCHED_SPIN_CAP', 'FB_BUILD_ID', 'FB_MPR_PAIRED', 'FB_TICKET_SPLIT'}
 
 
