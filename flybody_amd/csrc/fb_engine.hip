@@ -27,6 +27,7 @@ extern "C" { long long fb_stats[64]; }
 #include "fb_ik.hpp"
 #include "fb_inverse.hpp"
 #include "fb_deriv.hpp"
+#include "fb_rollout.hpp"
 #include "fb_host.hpp"                    // g_err / fail / HIPCHK, DevBuf, DevEvent
 #include "fb_model.hpp"                   // fb_model and the C-ABI's model entry points
 
@@ -523,6 +524,10 @@ struct fb_batch {
   DevBuf<double> fd_pool_r; DevBuf<int> fd_pool_i; int fd_slots = 0;
   DevBuf<double> fd_stage; DevBuf<int> fd_env, fd_counter;
   std::vector<int> fd_env_host;
+  // fb_batch_rollout (fb_rollout.hpp): it runs on the scratch rows above (roll_slots of them: what its own kernel keeps resident, at most fd_slots);
+  // the rollouts' source environments and its own counters
+  DevBuf<int> roll_env, roll_counter, roll_sched; int roll_slots = 0;
+  std::vector<int> roll_env_host;
 };
 
 template <typename real, typename T, typename P>
@@ -1310,6 +1315,85 @@ extern "C" int fb_batch_fd_tickets(fb_batch* b, int64_t* n) {
   HIPCHK(hipDeviceSynchronize());
   int c[2] = {0, 0};
   HIPCHK(hipMemcpy(c, b->fd_counter.get(), sizeof(c), hipMemcpyDeviceToHost));
+  *n = c[1];
+  return 0;
+}
+
+// ------------------------------------------------------------------ open-loop rollouts
+// MuJoCo's rollout for the listed environments (fb_rollout.hpp: k_rollout draws one ticket per rollout onto the scratch rows
+// fb_batch_transition_fd owns too).  Like that call it does not go through launch() and is not a timed launch, and the environments' rows
+// are only read.  Steady state: no host synchronisation, one upload (the rollouts' source environments).
+extern "C" int fb_batch_rollout(fb_batch* b, const fb_rollout_config* cfg, const double* ctrl, const float* action, double* state, double* sensordata,
+                                int32_t* status, void* stream) {
+  if (!b) return fail("fb_batch_rollout: null batch");
+  if (!cfg) return fail("fb_batch_rollout: null config");
+  if (b->precision != 64) return fail("fb_batch_rollout: rollouts need an FP64 batch (precision 64)");
+  if (b->n_models() > 1) return fail("fb_batch_rollout: per-model rollouts are not supported: this batch is a group of " + std::to_string(b->n_models()) + " models (fb_batch_create_group)");
+  if (b->law_coef) return fail("fb_batch_rollout: the rollout kernel knows no control law; call fb_batch_set_control_law(batch, NULL) first");
+  if (b->qfrc_applied) return fail("fb_batch_rollout: the rollout kernel knows no applied forces; call fb_batch_clear_forces first");
+  if (!state) return fail("fb_batch_rollout: the state output is NULL");
+  if (ctrl && action) return fail("fb_batch_rollout: both ctrl and action are given; a rollout takes exactly one of them");
+  if (!ctrl && !action) return fail("fb_batch_rollout: neither ctrl nor action is given; a rollout takes exactly one of them");
+  if (cfg->n_roll < 1) return fail("fb_batch_rollout: n_roll must be >= 1");
+  if (cfg->horizon < 1) return fail("fb_batch_rollout: horizon must be >= 1");
+  if (cfg->n_substeps < 0) return fail("fb_batch_rollout: n_substeps must be >= 0 (0: the model's own)");
+  if (!cfg->env_ids && cfg->n_roll > b->n_env) return fail("fb_batch_rollout: environment id out of range (n_roll exceeds the batch and env_ids is NULL)");
+  if (cfg->env_ids) for (int k = 0; k < cfg->n_roll; k++) if (cfg->env_ids[k] < 0 || cfg->env_ids[k] >= b->n_env)
+    return fail("fb_batch_rollout: environment id " + std::to_string(cfg->env_ids[k]) + " out of range (rollout " + std::to_string(k) + ")");
+  if (action && b->m->task_id == FB_TASK_FLIGHT_IMITATION && !b->have_wbpg) return fail("fb_batch_rollout: an action rollout of the flight task needs fb_batch_set_wbpg first");
+  FB_GUARD_BEGIN
+  HIPCHK(hipSetDevice(b->device));
+  if (fd_resident_slots(b)) return -1;
+  if (b->roll_slots == 0) {
+#ifdef FB_EMULATE
+    b->roll_slots = b->fd_slots;
+#else
+    hipDeviceProp_t prop; HIPCHK(hipGetDeviceProperties(&prop, b->device));
+    int nbk = 0;
+    HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nbk, (const void*)k_rollout<double>, FB_WAVE*LdsCfg<double>::EPB, 0));
+    b->roll_slots = std::max(1, std::min(b->fd_slots, nbk*prop.multiProcessorCount*LdsCfg<double>::EPB));
+#endif
+  }
+  if (cfg->pool_rows < 0 || cfg->pool_rows > b->roll_slots) return fail("fb_batch_rollout: pool_rows out of range (0, or 1 .. " + std::to_string(b->roll_slots) + " scratch rows)");
+  hipStream_t st = (hipStream_t)stream;
+  const int nr = cfg->n_roll;
+  if (alloc_zeroed_once(b->fd_pool_r, (size_t)b->fd_slots*b->off.nreal) || alloc_zeroed_once(b->fd_pool_i, (size_t)b->fd_slots*b->off.nint) ||
+      alloc_zeroed_once(b->roll_counter, 2)) return -1;
+  const int nsub = cfg->n_substeps > 0 ? cfg->n_substeps : b->m->nsubstep;
+  const size_t nctr = (size_t)cfg->horizon*nsub;        // one progress counter per substep of a rollout (k_rollout: tail-aware priorities)
+  if (b->roll_env.count() < (size_t)nr || b->roll_sched.count() < nctr) {
+    HIPCHK(hipDeviceSynchronize());                    // (an earlier call may still read them)
+    if (b->roll_env.reserve(nr) || b->roll_sched.reserve(nctr)) return -1;
+  }
+  b->roll_env_host.resize(nr);
+  for (int k = 0; k < nr; k++) b->roll_env_host[k] = cfg->env_ids ? cfg->env_ids[k] : k;
+  HIPCHK(hipMemcpyAsync(b->roll_env.get(), b->roll_env_host.data(), (size_t)nr*sizeof(int), hipMemcpyHostToDevice, st));
+  if (sync_model(b)) return -1;
+  HIPCHK(hipMemsetAsync(b->roll_counter.get(), 0, 2*sizeof(int), st));
+  HIPCHK(hipMemsetAsync(b->roll_sched.get(), 0, nctr*sizeof(int), st));
+  constexpr int EPB = LdsCfg<double>::EPB;
+  RolloutArgs<double> R;
+  R.rarena = (const double*)b->rarena.get(); R.iarena = b->iarena.get(); R.pool_r = b->fd_pool_r.get(); R.pool_i = b->fd_pool_i.get();
+  R.roll_env = b->roll_env.get(); R.ctrl = ctrl; R.action = action; R.state = state; R.sens = sensordata; R.status = (int*)status;
+  R.counter = b->roll_counter.get();
+  R.n_roll = nr; R.horizon = cfg->horizon; R.n_substeps = nsub;
+  R.nwave = std::min(cfg->pool_rows > 0 ? cfg->pool_rows : b->roll_slots, nr);
+  R.sched = nr <= R.nwave ? b->roll_sched.get() : nullptr;      // (a wave with a second rollout would count into the first one's substeps)
+  hipLaunchKernelGGL((k_rollout<double>), dim3((R.nwave + EPB - 1)/EPB), dim3(FB_WAVE*EPB), 0, st, (const DevModel<double>*)b->dM.get(), R);
+  HIPCHK(hipGetLastError());
+  return 0;
+  FB_GUARD_END
+}
+
+// Rollouts the last fb_batch_rollout call finished.  Synchronises the device.  A debug counter, like fb_batch_fd_tickets.
+extern "C" int fb_batch_rollouts_run(fb_batch* b, int64_t* n) {
+  if (!b || !n) return fail("fb_batch_rollouts_run: null argument");
+  *n = 0;
+  if (!b->roll_counter) return 0;
+  HIPCHK(hipSetDevice(b->device));
+  HIPCHK(hipDeviceSynchronize());
+  int c[2] = {0, 0};
+  HIPCHK(hipMemcpy(c, b->roll_counter.get(), sizeof(c), hipMemcpyDeviceToHost));
   *n = c[1];
   return 0;
 }

@@ -69,6 +69,10 @@ def stage_sequence(nsubstep: int):
 # Batch.transition_fd / derivatives.transition_fd: the Jacobians of one transition (None: not asked for) and the frames' warning bits
 TransitionFD = collections.namedtuple('TransitionFD', ['A', 'B', 'C', 'D', 'status'])
 
+# Batch.rollout / BatchedFlyEnv.rollout: state [n, T, nq + nv + na] and its views qpos / qvel / act, sensordata [n, T, 33] (None: not asked
+# for) and the rollouts' warning bits [n]
+Rollout = collections.namedtuple('Rollout', ['state', 'qpos', 'qvel', 'act', 'sensordata', 'status'])
+
 _libs: Dict[str, C.CDLL] = {}
 
 
@@ -139,6 +143,9 @@ def load_library(lib_path: Optional[str] = None) -> C.CDLL:
     if hasattr(L, 'fb_batch_transition_fd'):
         L.fb_batch_transition_fd.argtypes = [C.c_void_p] + [C.c_void_p]*7
         L.fb_batch_fd_tickets.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
+    if hasattr(L, 'fb_batch_rollout'):
+        L.fb_batch_rollout.argtypes = [C.c_void_p] + [C.c_void_p]*7
+        L.fb_batch_rollouts_run.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
     _libs[path] = L
     return L
 
@@ -198,6 +205,11 @@ class _FDConfig(C.Structure):
     """fb_fd_config (include/flybody_engine.h)."""
     _fields_ = [('eps', C.c_double), ('centered', C.c_int32), ('n_substeps', C.c_int32), ('n_frames', C.c_int32), ('env_ids', C.c_void_p),
                 ('pool_rows', C.c_int32)]
+
+
+class _RolloutConfig(C.Structure):
+    """fb_rollout_config (include/flybody_engine.h)."""
+    _fields_ = [('n_roll', C.c_int32), ('horizon', C.c_int32), ('n_substeps', C.c_int32), ('env_ids', C.c_void_p), ('pool_rows', C.c_int32)]
 
 
 class Model:
@@ -410,6 +422,46 @@ class Batch:
         """Transitions (nominal + perturbed) the last transition_fd call ran (fb_batch_fd_tickets; synchronises the device)."""
         n = C.c_int64(0)
         _check(self.L, self.L.fb_batch_fd_tickets(self.h, C.byref(n)))
+        return n.value
+
+    def rollout(self, ctrl=None, action=None, env_ids=None, n_substeps: int = 0, sensors: bool = False, pool_rows: int = 0,
+                stream=None) -> 'Rollout':
+        """Open-loop rollouts from the listed environments as they stand (fb_batch_rollout, MuJoCo's rollout; env_ids None: rollout r
+        starts from environment r; repeats are allowed -- K samples of one state).  Exactly one input, a contiguous torch tensor on the
+        batch's device: ctrl float64 [n, T, nu], held over the n_substeps physics substeps of each of the T intervals (0: the model's
+        own count, one control step), or action float32 [n, T, nact], which goes through the task's before_step hook as in a control
+        step.  Returns Rollout(state [n, T, nq + nv + na] float64, its views qpos / qvel / act, sensordata [n, T, 33] or None, status
+        int32 [n]: the OR of the WARN bits the rollout raised).  No reward, termination or reset; the environments are only read.
+        Asynchronous on `stream` (None: torch's current stream of the device, so torch work that follows is ordered behind it).  A
+        library without a GPU behind it (the tests' kernel-emulation build) takes and gives CPU tensors: its "device" memory is host
+        memory."""
+        import torch
+        if (ctrl is None) == (action is None):
+            raise ValueError('rollout takes exactly one of ctrl and action')
+        x, dt, width, what = (ctrl, torch.float64, self.model.dim('nu'), 'ctrl') if action is None else (action, torch.float32, self.model.dim('nact'), 'action')
+        emulated = b'emulation' in self.L.fb_version()
+        dev = torch.device('cpu') if emulated else torch.device('cuda', self.device)
+        if not isinstance(x, torch.Tensor) or x.dtype != dt or x.dim() != 3 or x.shape[2] != width or not x.is_contiguous() or x.device != dev:
+            raise ValueError(f'{what} must be a contiguous {dt} tensor [n, T, {width}] on {dev}')
+        n, T = int(x.shape[0]), int(x.shape[1])
+        ids = None if env_ids is None else np.ascontiguousarray(env_ids, np.int32).reshape(-1)
+        if ids is not None and len(ids) != n:
+            raise ValueError(f'env_ids names {len(ids)} environments for {n} rollouts')
+        if stream is None and not emulated:
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+        nq, nv, na = self.model.dim('nq'), self.model.dim('nv'), self.model.dim('na')
+        state = torch.zeros((n, T, nq + nv + na), dtype=torch.float64, device=dev)
+        sens = torch.zeros((n, T, NSENSOR), dtype=torch.float64, device=dev) if sensors else None
+        status = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
+        cfg = _RolloutConfig(n, T, int(n_substeps), None if ids is None else ids.ctypes.data, int(pool_rows))
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        _check(self.L, self.L.fb_batch_rollout(self.h, C.byref(cfg), ptr(ctrl), ptr(action), ptr(state), ptr(sens), ptr(status), stream))
+        return Rollout(state, state[..., :nq], state[..., nq:nq + nv], state[..., nq + nv:], sens, status[:n])
+
+    def rollouts_run(self) -> int:
+        """Rollouts the last rollout call finished (fb_batch_rollouts_run; synchronises the device)."""
+        n = C.c_int64(0)
+        _check(self.L, self.L.fb_batch_rollouts_run(self.h, C.byref(n)))
         return n.value
 
     def clear_forces(self):

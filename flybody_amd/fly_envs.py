@@ -374,6 +374,32 @@ class BatchedFlyEnv:
         control law."""
         return self.batch.transition_fd(env_ids=env_ids, **kw)
 
+    # ---- open-loop rollouts (flybody_amd.rollout, csrc/fb_rollout.hpp) ---------------------------
+    def rollout(self, action=None, ctrl=None, env_ids=None, **kw):
+        """What happens if these inputs are applied from here?  Open-loop rollouts from live environments between two control steps,
+        without disturbing them: engine.Rollout(state, qpos, qvel, act, sensordata, status) as torch tensors on the device
+        (Batch.rollout: n_substeps, sensors, pool_rows, stream).  action: float32 [n, T, nact], one row per control step, through the
+        task's before_step hook as step_tensor's actions go (for the flight task the wing-beat pattern generator advances inside the
+        rollout); or ctrl: float64 [n, T, nu], the actuators' controls themselves.  Rollout r starts from environment env_ids[r] (None:
+        r).  With a sample axis, [n_env_ids, K, T, .], every listed environment (None: all of them) gets K rollouts and the outputs
+        come back as [n_env_ids, K, T, .] (status: [n_env_ids, K]).
+        Modelled: the physics of T control steps and the action-to-control mapping.  NOT modelled: reward, termination and auto-reset
+        (a rollout runs on through what would end the episode, and one from an environment at LAST continues its physics), the
+        action corruptor, control_callback, reward_fn / termination_fn.  The environments are only read -- the steps that follow are
+        bit-identical to those of an environment that never ran a rollout.  FP64 batches without applied forces or a control law."""
+        x = action if action is not None else ctrl
+        if x is None or x.dim() != 4:
+            return self.batch.rollout(ctrl=ctrl, action=action, env_ids=env_ids, **kw)
+        ne, K = int(x.shape[0]), int(x.shape[1])
+        ids = np.arange(self.n_env, dtype=np.int32) if env_ids is None else np.ascontiguousarray(env_ids, np.int32).reshape(-1)
+        if len(ids) != ne:
+            raise ValueError(f'the leading axis of the inputs ({ne}) must match the environments listed ({len(ids)})')
+        flat = x.reshape(ne*K, x.shape[2], x.shape[3])
+        r = self.batch.rollout(ctrl=None if action is not None else flat, action=flat if action is not None else None,
+                               env_ids=np.repeat(ids, K), **kw)
+        back = lambda t: None if t is None else t.reshape((ne, K) + tuple(t.shape[1:]))
+        return engine.Rollout(*(back(t) for t in r))
+
     # ---- the parts of a control step around the kernel ------------------------------------------
     @property
     def _hooks_after(self) -> bool:

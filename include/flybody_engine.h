@@ -309,6 +309,50 @@ typedef struct fb_fd_config {
 int fb_batch_transition_fd(fb_batch* b, const fb_fd_config* cfg, double* A, double* B, double* C, double* D, int32_t* status, void* stream);
 int fb_batch_fd_tickets(fb_batch* b, int64_t* n);
 
+/* Open-loop rollouts (MuJoCo's rollout module for the engine's step): what happens if this input sequence is applied from here?
+ * Rollout r starts from environment env_ids[r] (r when env_ids is NULL) as it stands and runs `horizon` control intervals of n_substeps
+ * physics substeps each, the interval's input held over its substeps.  Exactly one kind of input is given, a DEVICE buffer:
+ *     ctrl   FP64 [n_roll][horizon][nu]     copied to FB_CTRL of the rollout; the actuation stage clamps it to ctrlrange as it clamps FB_CTRL;
+ *     action FP32 [n_roll][horizon][nact]   handed to the task's before_step hook, the one fb_batch_step runs: action scatter, NaN -> 0,
+ *                                           and for the flight task the wing-beat pattern generator's step and the wing commands.
+ * Outputs, caller-provided DEVICE buffers written directly (no staging): state [n_roll][horizon][nq + nv + na] = (qpos', qvel', act')
+ * after every interval; sensordata (optional) [n_roll][horizon][33] = FB_SENSORDATA as the interval's last substep leaves it (the
+ * engine's legacy-step timing: acceleration-stage sensors lag one substep); status (optional) int32 [n_roll] = the OR of the FB_WARN_*
+ * bits the rollout raised (contact / row caps, the solver's iteration limit, ...).
+ * What is copied: the head of the source environment's row -- FB_QPOS, FB_QVEL, FB_ACT, FB_CTRL, the warm start, the simulation time and
+ * the pattern generator's filtered frequency -- and, for an action rollout, the pattern generator's table position.  What is recomputed:
+ * everything else; the position and velocity stages of the copied state run first and no cached stage output is trusted (the mid-phase
+ * neighbour list included).  Then the substeps run in the step's own order (actuation .. acceleration sensors, Euler with implicit
+ * damping, position + velocity stages of the new state; noslip included); with sensordata NULL the position and velocity stages behind
+ * the very last integration are skipped.  Warm start: the first constraint solve starts from the acceleration the environment's next
+ * solve would start from, every later solve from its predecessor.  No other hook runs: no reward, termination, auto-reset, dataset or
+ * ghost logic -- a rollout from an environment whose step type is LAST continues its physics, it does not reset.  A ctrl rollout equals
+ * fb_batch_set(FB_CTRL) + fb_batch_substep(n_substeps) per interval on a copy of the environment, an action rollout equals
+ * fb_batch_step on one (while that copy does not reach LAST), bit for bit.
+ * Nothing a later control step reads changes: the environments' rows are only read; state, caches, warm start, FB_WARN*, FB_SIZE_STATS
+ * and FB_STEP_TICKS stay as they were.  The work runs on the scratch rows fb_batch_transition_fd uses too (allocated on the first call of
+ * either: one workspace row per resident wave slot, never one per rollout; pool_rows uses fewer); a wave takes one rollout after the
+ * other.  Results do not depend on pool_rows or on which wave drew which rollout: two calls give the same bits.  The two users of the
+ * rows are ordered only when they are on one stream: concurrent fb_batch_transition_fd / fb_batch_rollout calls on the same batch from
+ * different streams are the caller's to order.
+ * Refused, with the reason in fb_last_error(): an FP32 batch; a grouped batch of more than one model; a batch with a control law set or
+ * with applied forces allocated; null batch, config or state; both or neither of ctrl and action; n_roll < 1; horizon < 1;
+ * n_substeps < 0; an environment id out of range (env_ids NULL with n_roll > n_env included); pool_rows out of range; an action rollout
+ * of the flight task before fb_batch_set_wbpg.
+ * Asynchronous on `stream` after validation, ordered like any other launch on that stream; after the first call nothing synchronises and
+ * the only upload is env_ids.
+ * fb_batch_rollouts_run: the number of rollouts the last call finished; synchronises the device (a debug counter). */
+typedef struct fb_rollout_config {
+  int32_t n_roll;             /* >= 1 */
+  int32_t horizon;            /* T >= 1 control intervals */
+  int32_t n_substeps;         /* >= 1 physics substeps per interval, input held; 0: the model's own (fb_model_dim "nsubstep") */
+  const int32_t* env_ids;     /* HOST [n_roll]: source environment of every rollout, repeats allowed (K samples of one state); NULL: r */
+  int32_t pool_rows;          /* 0: all scratch rows; otherwise 1 .. that many */
+} fb_rollout_config;
+int fb_batch_rollout(fb_batch* b, const fb_rollout_config* cfg, const double* ctrl, const float* action,
+                     double* state, double* sensordata, int32_t* status, void* stream);
+int fb_batch_rollouts_run(fb_batch* b, int64_t* n);
+
 /* External forces (FB_QFRC_APPLIED, FB_XFRC_APPLIED), MuJoCo's two user inputs for everything that is not an actuator, a contact or the
  * fluid model.  Every substep
  *     qfrc_smooth = qfrc_passive - qfrc_bias + qfrc_actuator + qfrc_applied + sum_b J_b(xipos_b)' xfrc_applied_b
