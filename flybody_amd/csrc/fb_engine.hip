@@ -528,6 +528,8 @@ struct fb_batch {
   // the rollouts' source environments and its own counters
   DevBuf<int> roll_env, roll_counter, roll_sched; int roll_slots = 0;
   std::vector<int> roll_env_host;
+  // fb_batch_rollout_feedback: the rows k_closedloop_rollout keeps resident, and the rollouts' nominals behind their environments in roll_env
+  int roll_fb_slots = 0;
 };
 
 template <typename real, typename T, typename P>
@@ -1319,55 +1321,73 @@ extern "C" int fb_batch_fd_tickets(fb_batch* b, int64_t* n) {
   return 0;
 }
 
-// ------------------------------------------------------------------ open-loop rollouts
-// MuJoCo's rollout for the listed environments (fb_rollout.hpp: k_rollout draws one ticket per rollout onto the scratch rows
-// fb_batch_transition_fd owns too).  Like that call it does not go through launch() and is not a timed launch, and the environments' rows
-// are only read.  Steady state: no host synchronisation, one upload (the rollouts' source environments).
-extern "C" int fb_batch_rollout(fb_batch* b, const fb_rollout_config* cfg, const double* ctrl, const float* action, double* state, double* sensordata,
-                                int32_t* status, void* stream) {
-  if (!b) return fail("fb_batch_rollout: null batch");
-  if (!cfg) return fail("fb_batch_rollout: null config");
-  if (b->precision != 64) return fail("fb_batch_rollout: rollouts need an FP64 batch (precision 64)");
-  if (b->n_models() > 1) return fail("fb_batch_rollout: per-model rollouts are not supported: this batch is a group of " + std::to_string(b->n_models()) + " models (fb_batch_create_group)");
-  if (b->law_coef) return fail("fb_batch_rollout: the rollout kernel knows no control law; call fb_batch_set_control_law(batch, NULL) first");
-  if (b->qfrc_applied) return fail("fb_batch_rollout: the rollout kernel knows no applied forces; call fb_batch_clear_forces first");
-  if (!state) return fail("fb_batch_rollout: the state output is NULL");
-  if (ctrl && action) return fail("fb_batch_rollout: both ctrl and action are given; a rollout takes exactly one of them");
-  if (!ctrl && !action) return fail("fb_batch_rollout: neither ctrl nor action is given; a rollout takes exactly one of them");
-  if (cfg->n_roll < 1) return fail("fb_batch_rollout: n_roll must be >= 1");
-  if (cfg->horizon < 1) return fail("fb_batch_rollout: horizon must be >= 1");
-  if (cfg->n_substeps < 0) return fail("fb_batch_rollout: n_substeps must be >= 0 (0: the model's own)");
-  if (!cfg->env_ids && cfg->n_roll > b->n_env) return fail("fb_batch_rollout: environment id out of range (n_roll exceeds the batch and env_ids is NULL)");
+// ------------------------------------------------------------------ rollouts, open and closed loop
+// MuJoCo's rollout for the listed environments (fb_rollout.hpp: k_rollout / k_closedloop_rollout draw one ticket per rollout onto the scratch
+// rows fb_batch_transition_fd owns too).  Like that call they do not go through launch() and are not timed launches, and the environments'
+// rows are only read.  Steady state: no host synchronisation, one upload (the rollouts' source environments, and their nominals behind them).
+// Both entry points are run_rollout: fbk == NULL is the open-loop one.  fn: the entry point's name, for the refusals.
+static int run_rollout(fb_batch* b, const std::string& fn, const fb_rollout_config* cfg, const double* ctrl, const float* action, const fb_feedback* fbk,
+                       bool feedback, double* state, double* sensordata, double* ctrl_out, int32_t* status, void* stream) {
+  if (!b) return fail(fn + ": null batch");
+  if (!cfg) return fail(fn + ": null config");
+  if (b->precision != 64) return fail(fn + ": rollouts need an FP64 batch (precision 64)");
+  if (b->n_models() > 1) return fail(fn + ": per-model rollouts are not supported: this batch is a group of " + std::to_string(b->n_models()) + " models (fb_batch_create_group)");
+  if (b->law_coef) return fail(fn + ": the rollout kernel knows no control law; call fb_batch_set_control_law(batch, NULL) first");
+  if (b->qfrc_applied) return fail(fn + ": the rollout kernel knows no applied forces; call fb_batch_clear_forces first");
+  if (!state) return fail(fn + ": the state output is NULL");
+  if (!feedback) {
+    if (ctrl && action) return fail(fn + ": both ctrl and action are given; a rollout takes exactly one of them");
+    if (!ctrl && !action) return fail(fn + ": neither ctrl nor action is given; a rollout takes exactly one of them");
+  }
+  if (cfg->n_roll < 1) return fail(fn + ": n_roll must be >= 1");
+  if (cfg->horizon < 1) return fail(fn + ": horizon must be >= 1");
+  if (cfg->n_substeps < 0) return fail(fn + ": n_substeps must be >= 0 (0: the model's own)");
+  if (!cfg->env_ids && cfg->n_roll > b->n_env) return fail(fn + ": environment id out of range (n_roll exceeds the batch and env_ids is NULL)");
   if (cfg->env_ids) for (int k = 0; k < cfg->n_roll; k++) if (cfg->env_ids[k] < 0 || cfg->env_ids[k] >= b->n_env)
-    return fail("fb_batch_rollout: environment id " + std::to_string(cfg->env_ids[k]) + " out of range (rollout " + std::to_string(k) + ")");
-  if (action && b->m->task_id == FB_TASK_FLIGHT_IMITATION && !b->have_wbpg) return fail("fb_batch_rollout: an action rollout of the flight task needs fb_batch_set_wbpg first");
+    return fail(fn + ": environment id " + std::to_string(cfg->env_ids[k]) + " out of range (rollout " + std::to_string(k) + ")");
+  if (action && b->m->task_id == FB_TASK_FLIGHT_IMITATION && !b->have_wbpg) return fail(fn + ": an action rollout of the flight task needs fb_batch_set_wbpg first");
+  if (feedback) {
+    if (!fbk) return fail(fn + ": null feedback");
+    if (!fbk->x_nom) return fail(fn + ": x_nom is NULL");
+    if (!fbk->u_nom) return fail(fn + ": u_nom is NULL");
+    if (fbk->n_nom < 1) return fail(fn + ": n_nom must be >= 1");
+    if (!fbk->nom_ids && fbk->n_nom != cfg->n_roll) return fail(fn + ": nom_ids is NULL and n_nom (" + std::to_string(fbk->n_nom) + ") is not n_roll (" + std::to_string(cfg->n_roll) + ")");
+    if (fbk->nom_ids) for (int k = 0; k < cfg->n_roll; k++) if (fbk->nom_ids[k] < 0 || fbk->nom_ids[k] >= fbk->n_nom)
+      return fail(fn + ": nominal id " + std::to_string(fbk->nom_ids[k]) + " out of range (rollout " + std::to_string(k) + ")");
+    if (2*b->m->nv + b->m->na > FB_WAVE*FeedbackArgs<double>::DXSLOTS)
+      return fail(fn + ": the model's tangent space (2 nv + na) exceeds the feedback kernel's " + std::to_string(FB_WAVE*FeedbackArgs<double>::DXSLOTS) + " dx registers");
+  }
   FB_GUARD_BEGIN
   HIPCHK(hipSetDevice(b->device));
   if (fd_resident_slots(b)) return -1;
-  if (b->roll_slots == 0) {
+  int& slots = feedback ? b->roll_fb_slots : b->roll_slots;
+  if (slots == 0) {
 #ifdef FB_EMULATE
-    b->roll_slots = b->fd_slots;
+    slots = b->fd_slots;
 #else
     hipDeviceProp_t prop; HIPCHK(hipGetDeviceProperties(&prop, b->device));
     int nbk = 0;
-    HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nbk, (const void*)k_rollout<double>, FB_WAVE*LdsCfg<double>::EPB, 0));
-    b->roll_slots = std::max(1, std::min(b->fd_slots, nbk*prop.multiProcessorCount*LdsCfg<double>::EPB));
+    const void* kern = feedback ? (const void*)k_closedloop_rollout<double> : (const void*)k_rollout<double>;
+    HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nbk, kern, FB_WAVE*LdsCfg<double>::EPB, 0));
+    slots = std::max(1, std::min(b->fd_slots, nbk*prop.multiProcessorCount*LdsCfg<double>::EPB));
 #endif
   }
-  if (cfg->pool_rows < 0 || cfg->pool_rows > b->roll_slots) return fail("fb_batch_rollout: pool_rows out of range (0, or 1 .. " + std::to_string(b->roll_slots) + " scratch rows)");
+  if (cfg->pool_rows < 0 || cfg->pool_rows > slots) return fail(fn + ": pool_rows out of range (0, or 1 .. " + std::to_string(slots) + " scratch rows)");
   hipStream_t st = (hipStream_t)stream;
   const int nr = cfg->n_roll;
   if (alloc_zeroed_once(b->fd_pool_r, (size_t)b->fd_slots*b->off.nreal) || alloc_zeroed_once(b->fd_pool_i, (size_t)b->fd_slots*b->off.nint) ||
       alloc_zeroed_once(b->roll_counter, 2)) return -1;
   const int nsub = cfg->n_substeps > 0 ? cfg->n_substeps : b->m->nsubstep;
   const size_t nctr = (size_t)cfg->horizon*nsub;        // one progress counter per substep of a rollout (k_rollout: tail-aware priorities)
-  if (b->roll_env.count() < (size_t)nr || b->roll_sched.count() < nctr) {
+  const size_t nids = (size_t)nr*(feedback ? 2 : 1);    // the environments, and for a closed-loop call the nominals behind them: one upload
+  if (b->roll_env.count() < nids || b->roll_sched.count() < nctr) {
     HIPCHK(hipDeviceSynchronize());                    // (an earlier call may still read them)
-    if (b->roll_env.reserve(nr) || b->roll_sched.reserve(nctr)) return -1;
+    if (b->roll_env.reserve(nids) || b->roll_sched.reserve(nctr)) return -1;
   }
-  b->roll_env_host.resize(nr);
+  b->roll_env_host.resize(nids);
   for (int k = 0; k < nr; k++) b->roll_env_host[k] = cfg->env_ids ? cfg->env_ids[k] : k;
-  HIPCHK(hipMemcpyAsync(b->roll_env.get(), b->roll_env_host.data(), (size_t)nr*sizeof(int), hipMemcpyHostToDevice, st));
+  if (feedback) for (int k = 0; k < nr; k++) b->roll_env_host[nr + k] = fbk->nom_ids ? fbk->nom_ids[k] : k;
+  HIPCHK(hipMemcpyAsync(b->roll_env.get(), b->roll_env_host.data(), nids*sizeof(int), hipMemcpyHostToDevice, st));
   if (sync_model(b)) return -1;
   HIPCHK(hipMemsetAsync(b->roll_counter.get(), 0, 2*sizeof(int), st));
   HIPCHK(hipMemsetAsync(b->roll_sched.get(), 0, nctr*sizeof(int), st));
@@ -1377,15 +1397,31 @@ extern "C" int fb_batch_rollout(fb_batch* b, const fb_rollout_config* cfg, const
   R.roll_env = b->roll_env.get(); R.ctrl = ctrl; R.action = action; R.state = state; R.sens = sensordata; R.status = (int*)status;
   R.counter = b->roll_counter.get();
   R.n_roll = nr; R.horizon = cfg->horizon; R.n_substeps = nsub;
-  R.nwave = std::min(cfg->pool_rows > 0 ? cfg->pool_rows : b->roll_slots, nr);
+  R.nwave = std::min(cfg->pool_rows > 0 ? cfg->pool_rows : slots, nr);
   R.sched = nr <= R.nwave ? b->roll_sched.get() : nullptr;      // (a wave with a second rollout would count into the first one's substeps)
-  hipLaunchKernelGGL((k_rollout<double>), dim3((R.nwave + EPB - 1)/EPB), dim3(FB_WAVE*EPB), 0, st, (const DevModel<double>*)b->dM.get(), R);
+  if (feedback) {
+    FeedbackArgs<double> F;
+    F.roll_nom = b->roll_env.get() + nr; F.x_nom = fbk->x_nom; F.u_nom = fbk->u_nom; F.Kt = fbk->K; F.k = fbk->k; F.alpha = fbk->alpha; F.ctrl_out = ctrl_out;
+    hipLaunchKernelGGL((k_closedloop_rollout<double>), dim3((R.nwave + EPB - 1)/EPB), dim3(FB_WAVE*EPB), 0, st, (const DevModel<double>*)b->dM.get(), R, F);
+  }
+  else hipLaunchKernelGGL((k_rollout<double>), dim3((R.nwave + EPB - 1)/EPB), dim3(FB_WAVE*EPB), 0, st, (const DevModel<double>*)b->dM.get(), R);
   HIPCHK(hipGetLastError());
   return 0;
   FB_GUARD_END
 }
 
-// Rollouts the last fb_batch_rollout call finished.  Synchronises the device.  A debug counter, like fb_batch_fd_tickets.
+extern "C" int fb_batch_rollout(fb_batch* b, const fb_rollout_config* cfg, const double* ctrl, const float* action, double* state, double* sensordata,
+                                int32_t* status, void* stream) {
+  return run_rollout(b, "fb_batch_rollout", cfg, ctrl, action, nullptr, false, state, sensordata, nullptr, status, stream);
+}
+
+// Closed-loop rollouts: the input of interval t is a time-varying affine feedback on the state the rollout has reached (fb_rollout.hpp).
+extern "C" int fb_batch_rollout_feedback(fb_batch* b, const fb_rollout_config* cfg, const fb_feedback* fbk, double* state, double* sensordata,
+                                         double* ctrl_out, int32_t* status, void* stream) {
+  return run_rollout(b, "fb_batch_rollout_feedback", cfg, nullptr, nullptr, fbk, true, state, sensordata, ctrl_out, status, stream);
+}
+
+// Rollouts the last fb_batch_rollout / fb_batch_rollout_feedback call finished.  Synchronises the device.  A debug counter, like fb_batch_fd_tickets.
 extern "C" int fb_batch_rollouts_run(fb_batch* b, int64_t* n) {
   if (!b || !n) return fail("fb_batch_rollouts_run: null argument");
   *n = 0;

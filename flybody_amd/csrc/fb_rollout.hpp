@@ -23,8 +23,23 @@
 // The stage sequence is the kernel's own (NOT a mode of d_run: that would move every step kernel's code).  The kernel runs on the step
 // kernel's LDS layout and under its launch bounds, so the FB_NOINLINE stage functions it shares with k_fly and k_transition_fd are
 // compiled for the same budget and their code does not change.  FP64 only.
+//
+// CLOSED-LOOP rollouts (k_closedloop_rollout): a kernel of its own next to k_rollout -- not a mode of it, for the reason above:
+// a run-time switch would move k_rollout's code -- that differs in one thing, the interval's input.  Tickets, rows, LDS layout, launch
+// bounds, stage sequence, priorities, records and status are rollout_kernel's, stated once; the template argument FEEDBACK selects the
+// input at compile time.  At the start of interval t the wave evaluates a time-varying affine feedback on the row's own state:
+//     dx  = x_t (-) xnom[nom][t]                     the tangent space of fb_deriv.hpp (dq[nv], dv[nv], dact[na]); rotations by fd_sub_quat
+//     u_i = clamp( unom[nom][t][i] + (alpha[r]*k[nom][t][i] + sum_j K[nom][t][i][j]*dx[j]) )
+// clamp = clampr to act_ctrlrange where act_ctrllimited: s_actuation's own function and condition, so the stage's clamp is the identity on
+// it.  u goes to w.ctrl() and to the optional record [r][t][nu].  Mapping: lane == output i (blocks of 64 for nu > 64); dx lives in
+// REGISTERS, element j in slot j/64 of lane j%64 (FeedbackArgs::DXSLOTS slots; the host refuses a model with more), and is broadcast by
+// v_readlane; the gains are read TRANSPOSED, Kt[nom][t][j][i], so that the lanes of one j read consecutive doubles and the j rows
+// follow one another (one stream of ndx*nu doubles per interval; rollouts of one nominal share it through L2).  The sum runs over
+// j = 0 .. ndx-1 in ascending order in ONE accumulator per output, from 0: fixed by the code, the same bits for any pool and any call.
+// No LDS beyond the step kernel's layout.  Feedback is on ctrl only: an action-space law (the pattern generator in the loop) is not offered.
 #pragma once
 #include "fb_step.hpp"
+#include "fb_deriv.hpp"
 
 template <typename real>
 struct RolloutArgs {
@@ -41,8 +56,80 @@ struct RolloutArgs {
   int n_roll, horizon, n_substeps, nwave;
 };
 
+#define FB_FBK_BLOCK 16      // gain rows a wave has in flight at once (s_feedback)
+
+// k_closedloop_rollout's own arguments: everything else is RolloutArgs (ctrl and action null)
 template <typename real>
-__device__ __forceinline__ void rollout_kernel(const DevModel<real>* Mp, const RolloutArgs<real>& A) {
+struct FeedbackArgs {
+  static constexpr int DXSLOTS = 6;             // dx registers per lane: ndx <= 64*DXSLOTS (2*FB_MAXNV + na; the fly: 275)
+  const int* roll_nom;                          // [n_roll] nominal of every rollout
+  const real* x_nom;                            // [n_nom][horizon][nq + nv + na]: the state at the START of interval t
+  const real* u_nom;                            // [n_nom][horizon][nu]
+  const real* Kt;                               // [n_nom][horizon][ndx][nu]: the gains, transposed; null: zero
+  const real* k;                                // [n_nom][horizon][nu], null: zero
+  const real* alpha;                            // [n_roll], null: 1
+  real* ctrl_out;                               // [n_roll][horizon][nu] the inputs applied, or null
+};
+
+// The input of one interval under the feedback law (above): a stage of its own, not inlined, like the stages around it -- its registers
+// (dx, the gain loads in flight) are allocated apart from the kernel's, whose frame stays k_rollout's.  xn, un, Kt (null: zero), kt (null:
+// zero): the interval's rows of the rollout's nominal; out (null: none): its row of the ctrl record.  All 64 lanes call.
+template <typename real> FB_STAGE_C void s_feedback(const DevModel<real>& M_, const WS<real>& w_, const real* xn_, const real* un_, const real* Kt_, const real* kt_,
+                                                    real al, real* out_, int lane) {
+  const DevModel<real>& M = as_constant(M_); const WS<real> w = ws_uniform(w_, M);
+  const real *xn = uniform_p(xn_), *un = uniform_p(un_), *Kt = uniform_p(Kt_), *kt = uniform_p(kt_); real* out = uniform_p(out_);
+  constexpr int NS = FeedbackArgs<real>::DXSLOTS;
+  const int nv = M.nv, na = M.na, nq = M.nq, nu = M.nu, ndx = 2*nv + na;
+  SYNC();
+  real dx[NS];
+#pragma unroll
+  for (int m = 0; m < NS; m++) {
+    const int c = lane + FB_WAVE*m;
+    real v = 0;
+    if (c < nv) {
+      const int j = M.dof_jntid[c], jt = M.jnt_type[j], qa = M.jnt_qposadr[j], kk = c - M.jnt_dofadr[j];
+      if (jt == JNT_FREE && kk >= 3) { real dq[3]; fd_sub_quat(dq, w.qpos() + qa + 3, xn + qa + 3); v = dq[kk - 3]; }
+      else if (jt == JNT_BALL) { real dq[3]; fd_sub_quat(dq, w.qpos() + qa, xn + qa); v = dq[kk]; }
+      else v = w.qpos()[qa + kk] - xn[qa + kk];
+    }
+    else if (c < 2*nv) v = w.qvel()[c - nv] - xn[nq + c - nv];
+    else if (c < ndx) v = w.act()[c - 2*nv] - xn[nq + nv + c - 2*nv];
+    dx[m] = v;
+  }
+  for (int i0 = 0; i0 < nu; i0 += FB_WAVE) {
+    const int i = i0 + lane;
+    const bool on = i < nu;
+    real s = 0;
+    if (Kt) {
+#pragma unroll
+      for (int m = 0; m < NS; m++) {
+        // blocks of FB_FBK_BLOCK rows with a constant trip count: the broadcast is a convergent operation, so the compiler does not
+        // unroll a loop around it whose trip count it does not know, and one load per trip leaves the wave waiting for memory ndx
+        // times per interval.  A block loads its rows together (rows behind ndx: not read, their dx is zero) and adds them in order.
+        const real* Km = Kt + (size_t)FB_WAVE*m*nu + i;
+        for (int q = 0; q < FB_WAVE/FB_FBK_BLOCK; q++) {
+          const int j0 = uniform_int(FB_WAVE*m + FB_FBK_BLOCK*q);
+          if (j0 >= ndx) break;
+          real g[FB_FBK_BLOCK];
+#pragma unroll
+          for (int e = 0; e < FB_FBK_BLOCK; e++) g[e] = (on && j0 + e < ndx) ? Km[(size_t)(FB_FBK_BLOCK*q + e)*nu] : (real)0;
+#pragma unroll
+          for (int e = 0; e < FB_FBK_BLOCK; e++) s += g[e]*rdlane(dx[m], FB_FBK_BLOCK*q + e);
+        }
+      }
+    }
+    if (on) {
+      real u = un[i] + (al*(kt ? kt[i] : (real)0) + s);
+      if (M.act_ctrllimited[i]) u = clampr(u, M.act_ctrlrange[2*i], M.act_ctrlrange[2*i + 1]);
+      w.ctrl()[i] = u;
+      if (out) out[i] = u;
+    }
+  }
+  SYNC();
+}
+
+template <typename real, bool FEEDBACK>
+__device__ __forceinline__ void rollout_kernel(const DevModel<real>* Mp, const RolloutArgs<real>& A, const FeedbackArgs<real>& F) {
   constexpr int EPB = LdsCfg<real>::EPB;
   __shared__ real s_pool[EPB][LdsCfg<real>::POOL];
   __shared__ LdsTab s_tab;
@@ -71,6 +158,9 @@ __device__ __forceinline__ void rollout_kernel(const DevModel<real>* Mp, const R
     r = uniform_int(__shfl(r, 0, FB_WAVE));
     if (r >= total) return;
     const int env = uniform_int(A.roll_env[r]);
+    int nom = 0;
+    real al = 1;
+    if constexpr (FEEDBACK) { nom = uniform_int(F.roll_nom[r]); if (F.alpha) al = F.alpha[r]; }
     const real* src = A.rarena + (size_t)env*M.off.nreal;
     const int* isrc = A.iarena + (size_t)env*M.off.nint + M.off.istate;
     // ---- prepare the row: nothing of the row's previous ticket survives
@@ -87,7 +177,12 @@ __device__ __forceinline__ void rollout_kernel(const DevModel<real>* Mp, const R
     for (int t = 0; t < T; t++) {
       const size_t rec = (size_t)r*T + t;
       // ---- the interval's input
-      if (by_action) s_pre(M, wc, A.action + rec*M.nact, lane);
+      if constexpr (FEEDBACK) {
+        const size_t nt = (size_t)nom*T + t;
+        s_feedback(M, wc, F.x_nom + nt*nx, F.u_nom + nt*nu, F.Kt ? F.Kt + nt*(2*nv + na)*nu : nullptr, F.k ? F.k + nt*nu : nullptr, al,
+                   F.ctrl_out ? F.ctrl_out + rec*nu : nullptr, lane);
+      }
+      else if (by_action) s_pre(M, wc, A.action + rec*M.nact, lane);
       else {
         const real* u = A.ctrl + rec*nu;
         for (int i = lane; i < nu; i += FB_WAVE) w.ctrl()[i] = u[i];
@@ -133,5 +228,10 @@ __device__ __forceinline__ void rollout_kernel(const DevModel<real>* Mp, const R
 
 template <typename real>
 __global__ void __launch_bounds__(FB_WAVE*LdsCfg<real>::EPB, LdsCfg<real>::WAVES_PER_SIMD) k_rollout(const DevModel<real>* Mp, RolloutArgs<real> A) {
-  rollout_kernel<real>(Mp, A);
+  rollout_kernel<real, false>(Mp, A, FeedbackArgs<real>());
+}
+
+template <typename real>
+__global__ void __launch_bounds__(FB_WAVE*LdsCfg<real>::EPB, LdsCfg<real>::WAVES_PER_SIMD) k_closedloop_rollout(const DevModel<real>* Mp, RolloutArgs<real> A, FeedbackArgs<real> F) {
+  rollout_kernel<real, true>(Mp, A, F);
 }

@@ -71,7 +71,12 @@ TransitionFD = collections.namedtuple('TransitionFD', ['A', 'B', 'C', 'D', 'stat
 
 # Batch.rollout / BatchedFlyEnv.rollout: state [n, T, nq + nv + na] and its views qpos / qvel / act, sensordata [n, T, 33] (None: not asked
 # for) and the rollouts' warning bits [n]
-Rollout = collections.namedtuple('Rollout', ['state', 'qpos', 'qvel', 'act', 'sensordata', 'status'])
+Rollout = collections.namedtuple('Rollout', ['state', 'qpos', 'qvel', 'act', 'sensordata', 'status', 'ctrl'], defaults=(None,))
+# ... and of a closed-loop one (Batch.rollout_feedback) ctrl [n, T, nu], the inputs the feedback law applied (an open-loop rollout: None)
+
+# The feedback law of a closed-loop rollout, u_t = clamp(u_nom[t] + alpha k[t] + K[t] (x_t (-) x_nom[t])): the arguments of
+# Batch.rollout_feedback as one value, for BatchedFlyEnv.rollout(feedback=...) and rollout.rollout(feedback=...)
+Feedback = collections.namedtuple('Feedback', ['x_nom', 'u_nom', 'K', 'k', 'alpha', 'nom_ids'], defaults=(None, None, None, None))
 
 _libs: Dict[str, C.CDLL] = {}
 
@@ -146,6 +151,8 @@ def load_library(lib_path: Optional[str] = None) -> C.CDLL:
     if hasattr(L, 'fb_batch_rollout'):
         L.fb_batch_rollout.argtypes = [C.c_void_p] + [C.c_void_p]*7
         L.fb_batch_rollouts_run.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
+    if hasattr(L, 'fb_batch_rollout_feedback'):
+        L.fb_batch_rollout_feedback.argtypes = [C.c_void_p] + [C.c_void_p]*7
     _libs[path] = L
     return L
 
@@ -210,6 +217,12 @@ class _FDConfig(C.Structure):
 class _RolloutConfig(C.Structure):
     """fb_rollout_config (include/flybody_engine.h)."""
     _fields_ = [('n_roll', C.c_int32), ('horizon', C.c_int32), ('n_substeps', C.c_int32), ('env_ids', C.c_void_p), ('pool_rows', C.c_int32)]
+
+
+class _Feedback(C.Structure):
+    """fb_feedback (include/flybody_engine.h)."""
+    _fields_ = [('n_nom', C.c_int32), ('nom_ids', C.c_void_p), ('x_nom', C.c_void_p), ('u_nom', C.c_void_p), ('K', C.c_void_p), ('k', C.c_void_p),
+                ('alpha', C.c_void_p)]
 
 
 class Model:
@@ -458,8 +471,67 @@ class Batch:
         _check(self.L, self.L.fb_batch_rollout(self.h, C.byref(cfg), ptr(ctrl), ptr(action), ptr(state), ptr(sens), ptr(status), stream))
         return Rollout(state, state[..., :nq], state[..., nq:nq + nv], state[..., nq + nv:], sens, status[:n])
 
+    def rollout_feedback(self, x_nom, u_nom, K=None, k=None, alpha=None, nom_ids=None, env_ids=None, n_substeps: int = 0,
+                         sensors: bool = False, pool_rows: int = 0, stream=None) -> 'Rollout':
+        """Closed-loop rollouts from the listed environments as they stand (fb_batch_rollout_feedback): at the start of interval t rollout
+        r applies u = clamp(u_nom[m, t] + alpha[r] k[m, t] + K[m, t] (x_t (-) x_nom[m, t])), m = nom_ids[r], evaluated on the device from
+        the state the rollout has reached; (-) is the tangent-space difference of transition_fd (lqr.state_difference), clamp the
+        actuators' ctrlrange.  Contiguous float64 torch tensors on the batch's device: x_nom [n_nom, T, nq + nv + na] -- the nominal
+        state at the START of interval t --, u_nom [n_nom, T, nu], K [n_nom, T, nu, ndx] (None: zero; transposed once here, on the
+        stream, to the layout the kernel reads), k [n_nom, T, nu] (None: zero), alpha [n] (None: 1; the step length of a line search).
+        nom_ids [n] (None: rollout r follows nominal r, and n_nom == n); env_ids [n] (None: rollout r starts from environment r); the
+        number of rollouts n is that of env_ids, else of nom_ids, else n_nom.  Returns Rollout as rollout() does, with ctrl [n, T, nu]:
+        the inputs applied.  Feedback acts on ctrl only, not on a task's actions.  Asynchronous on `stream` like rollout()."""
+        import torch
+        emulated = b'emulation' in self.L.fb_version()
+        dev = torch.device('cpu') if emulated else torch.device('cuda', self.device)
+        nq, nv, na, nu = (self.model.dim(d) for d in ('nq', 'nv', 'na', 'nu'))
+        nx, ndx = nq + nv + na, 2*nv + na
+
+        def chk(x, what, *tail):
+            if not isinstance(x, torch.Tensor) or x.dtype != torch.float64 or tuple(x.shape[x.dim() - len(tail):]) != tail or x.dim() != len(tail) + 2 \
+                    or not x.is_contiguous() or x.device != dev:
+                raise ValueError(f'{what} must be a contiguous torch.float64 tensor [n_nom, T, {", ".join(map(str, tail))}] on {dev}')
+        chk(x_nom, 'x_nom', nx)
+        n_nom, T = int(x_nom.shape[0]), int(x_nom.shape[1])
+        chk(u_nom, 'u_nom', nu)
+        if K is not None:
+            chk(K, 'K', nu, ndx)
+        if k is not None:
+            chk(k, 'k', nu)
+        for x, what in ((u_nom, 'u_nom'), (K, 'K'), (k, 'k')):
+            if x is not None and tuple(x.shape[:2]) != (n_nom, T):
+                raise ValueError(f'{what} must have the leading axes of x_nom, [{n_nom}, {T}]')
+        ids = None if env_ids is None else np.ascontiguousarray(env_ids, np.int32).reshape(-1)
+        noms = None if nom_ids is None else np.ascontiguousarray(nom_ids, np.int32).reshape(-1)
+        n = len(ids) if ids is not None else len(noms) if noms is not None else n_nom
+        if noms is not None and len(noms) != n:
+            raise ValueError(f'nom_ids names {len(noms)} nominals for {n} rollouts')
+        if alpha is not None and (not isinstance(alpha, torch.Tensor) or alpha.dtype != torch.float64 or tuple(alpha.shape) != (n,)
+                                  or not alpha.is_contiguous() or alpha.device != dev):
+            raise ValueError(f'alpha must be a contiguous torch.float64 tensor [{n}] on {dev}')
+        if stream is None and not emulated:
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+        Kt = None
+        if K is not None:
+            if emulated or stream == torch.cuda.current_stream(self.device).cuda_stream:
+                Kt = K.transpose(2, 3).contiguous()
+            else:                                                                # (allocated on that stream: freed in its order)
+                with torch.cuda.stream(torch.cuda.ExternalStream(stream, device=dev)):
+                    Kt = K.transpose(2, 3).contiguous()
+        state = torch.zeros((n, T, nx), dtype=torch.float64, device=dev)
+        sens = torch.zeros((n, T, NSENSOR), dtype=torch.float64, device=dev) if sensors else None
+        ctrl = torch.zeros((n, T, nu), dtype=torch.float64, device=dev)
+        status = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
+        cfg = _RolloutConfig(n, T, int(n_substeps), None if ids is None else ids.ctypes.data, int(pool_rows))
+        ptr = lambda t: None if t is None else t.data_ptr()
+        fbk = _Feedback(n_nom, None if noms is None else noms.ctypes.data, ptr(x_nom), ptr(u_nom), ptr(Kt), ptr(k), ptr(alpha))
+        cp = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        _check(self.L, self.L.fb_batch_rollout_feedback(self.h, C.byref(cfg), C.byref(fbk), cp(state), cp(sens), cp(ctrl), cp(status), stream))
+        return Rollout(state, state[..., :nq], state[..., nq:nq + nv], state[..., nq + nv:], sens, status[:n], ctrl)
+
     def rollouts_run(self) -> int:
-        """Rollouts the last rollout call finished (fb_batch_rollouts_run; synchronises the device)."""
+        """Rollouts the last rollout / rollout_feedback call finished (fb_batch_rollouts_run; synchronises the device)."""
         n = C.c_int64(0)
         _check(self.L, self.L.fb_batch_rollouts_run(self.h, C.byref(n)))
         return n.value

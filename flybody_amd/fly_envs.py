@@ -375,7 +375,7 @@ class BatchedFlyEnv:
         return self.batch.transition_fd(env_ids=env_ids, **kw)
 
     # ---- open-loop rollouts (flybody_amd.rollout, csrc/fb_rollout.hpp) ---------------------------
-    def rollout(self, action=None, ctrl=None, env_ids=None, **kw):
+    def rollout(self, action=None, ctrl=None, env_ids=None, feedback=None, samples=None, **kw):
         """What happens if these inputs are applied from here?  Open-loop rollouts from live environments between two control steps,
         without disturbing them: engine.Rollout(state, qpos, qvel, act, sensordata, status) as torch tensors on the device
         (Batch.rollout: n_substeps, sensors, pool_rows, stream).  action: float32 [n, T, nact], one row per control step, through the
@@ -386,7 +386,14 @@ class BatchedFlyEnv:
         Modelled: the physics of T control steps and the action-to-control mapping.  NOT modelled: reward, termination and auto-reset
         (a rollout runs on through what would end the episode, and one from an environment at LAST continues its physics), the
         action corruptor, control_callback, reward_fn / termination_fn.  The environments are only read -- the steps that follow are
-        bit-identical to those of an environment that never ran a rollout.  FP64 batches without applied forces or a control law."""
+        bit-identical to those of an environment that never ran a rollout.  FP64 batches without applied forces or a control law.
+        feedback=engine.Feedback(x_nom, u_nom, K, k, alpha): CLOSED-LOOP rollouts instead (Batch.rollout_feedback; neither action nor
+        ctrl is given then) -- one nominal per listed environment, x_nom [n_env_ids, T, nx], u_nom / k [n_env_ids, T, nu],
+        K [n_env_ids, T, nu, ndx]; rollout r of environment env_ids[r] follows nominal r.  samples=K gives every listed environment K
+        rollouts that share its nominal, alpha [n_env_ids, K] (the step lengths of a line search), and the outputs come back as
+        [n_env_ids, K, T, .]; the result carries ctrl, the inputs applied."""
+        if feedback is not None:
+            return self._rollout_feedback(engine.Feedback(*feedback), action, ctrl, env_ids, samples, **kw)
         x = action if action is not None else ctrl
         if x is None or x.dim() != 4:
             return self.batch.rollout(ctrl=ctrl, action=action, env_ids=env_ids, **kw)
@@ -397,6 +404,25 @@ class BatchedFlyEnv:
         flat = x.reshape(ne*K, x.shape[2], x.shape[3])
         r = self.batch.rollout(ctrl=None if action is not None else flat, action=flat if action is not None else None,
                                env_ids=np.repeat(ids, K), **kw)
+        back = lambda t: None if t is None else t.reshape((ne, K) + tuple(t.shape[1:]))
+        return engine.Rollout(*(back(t) for t in r))
+
+    def _rollout_feedback(self, fbk, action, ctrl, env_ids, samples, **kw):
+        if action is not None or ctrl is not None:
+            raise ValueError('a closed-loop rollout computes its inputs: give feedback alone, without action or ctrl')
+        if fbk.nom_ids is not None:
+            raise ValueError('the nominal of a rollout is its environment here (nominal r for env_ids[r]): leave Feedback.nom_ids None')
+        ids = np.arange(self.n_env, dtype=np.int32) if env_ids is None else np.ascontiguousarray(env_ids, np.int32).reshape(-1)
+        ne = len(ids)
+        if int(fbk.x_nom.shape[0]) != ne:
+            raise ValueError(f'the leading axis of the nominals ({int(fbk.x_nom.shape[0])}) must match the environments listed ({ne})')
+        if samples is None and (fbk.alpha is None or fbk.alpha.dim() == 1):
+            return self.batch.rollout_feedback(fbk.x_nom, fbk.u_nom, fbk.K, fbk.k, fbk.alpha, env_ids=ids, **kw)
+        K = int(samples) if samples is not None else int(fbk.alpha.shape[1])
+        if K < 1 or (fbk.alpha is not None and tuple(fbk.alpha.shape) != (ne, K)):
+            raise ValueError(f'alpha must be [{ne}, {K}]: one step length per sample of every listed environment')
+        r = self.batch.rollout_feedback(fbk.x_nom, fbk.u_nom, fbk.K, fbk.k, None if fbk.alpha is None else fbk.alpha.reshape(ne*K),
+                                        nom_ids=np.repeat(np.arange(ne, dtype=np.int32), K), env_ids=np.repeat(ids, K), **kw)
         back = lambda t: None if t is None else t.reshape((ne, K) + tuple(t.shape[1:]))
         return engine.Rollout(*(back(t) for t in r))
 

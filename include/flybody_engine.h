@@ -353,6 +353,37 @@ int fb_batch_rollout(fb_batch* b, const fb_rollout_config* cfg, const double* ct
                      double* state, double* sensordata, int32_t* status, void* stream);
 int fb_batch_rollouts_run(fb_batch* b, int64_t* n);
 
+/* Closed-loop rollouts: fb_batch_rollout with the input of interval t computed on the device from the state the rollout has reached,
+ *     dx  = x_t (-) x_nom[nom][t]
+ *     u_i = clamp( u_nom[nom][t][i] + (alpha[r]*k[nom][t][i] + sum_j K[nom][t][i][j]*dx[j]) )
+ * -- LQR tracking, the forward pass and line search of iLQR, the stability test of a gain.  nom = nom_ids[r] is the rollout's nominal
+ * trajectory; many rollouts may share one.  x = (qpos, qvel, act); dx lives in fb_batch_transition_fd's tangent space (dq[nv], dv[nv],
+ * dact[na]; ndx = 2 nv + na): subtraction for hinge and slide joints and free-joint translation, the local rotation vector that takes
+ * the nominal quaternion to the state's for free- and ball-joint rotation.  x_nom[nom][t] is the nominal state at the START of interval
+ * t; x_0 is the source environment's state as it stands.  clamp: to ctrlrange where the actuator is ctrllimited, the clamp the actuation
+ * stage applies, which therefore leaves u as it is.  u is held over the interval's n_substeps substeps and written to ctrl_out.
+ * LAYOUT OF K: the C-ABI takes the gains TRANSPOSED, K[n_nom][horizon][ndx][nu] (entry [j][i] multiplies dx[j] into u_i), the layout
+ * the kernel streams; a caller with [nu][ndx] matrices transposes them once on its stream (the Python shim does).  The sum runs over
+ * j = 0 .. ndx-1 in ascending order, one accumulator per output: two calls, and any pool_rows, give the same bits.
+ * Everything else is fb_batch_rollout's: fb_rollout_config unchanged, what is copied and recomputed, the records state / sensordata /
+ * status, the scratch rows, the sources only read, fb_batch_rollouts_run.  With K and k NULL (or zero), or alpha = 0 and K zero, the
+ * result has the bits of fb_batch_rollout(ctrl = u_nom); feeding ctrl_out back to fb_batch_rollout reproduces state and sensordata bit
+ * for bit.  Feedback is on ctrl only: an action-space law (the flight task's pattern generator in the loop) is not offered.
+ * Refused, with the reason in fb_last_error(): everything fb_batch_rollout refuses (an input is not asked for), and: null fbk, x_nom or
+ * u_nom; n_nom < 1; a nominal id out of range; nom_ids NULL with n_nom != n_roll; a model whose ndx exceeds the kernel's 384 dx registers.
+ * Asynchronous on `stream` after validation; after the first call nothing synchronises and the only upload is env_ids / nom_ids. */
+typedef struct fb_feedback {
+  int32_t n_nom;            /* >= 1 nominal trajectories */
+  const int32_t* nom_ids;   /* HOST [n_roll], 0 .. n_nom-1: the nominal of every rollout (many rollouts may share one); NULL: r, and n_nom == n_roll */
+  const double* x_nom;      /* DEVICE [n_nom][horizon][nq+nv+na]: state at the START of interval t */
+  const double* u_nom;      /* DEVICE [n_nom][horizon][nu] */
+  const double* K;          /* DEVICE [n_nom][horizon][ndx][nu]: TRANSPOSED (above); NULL: zero */
+  const double* k;          /* DEVICE [n_nom][horizon][nu], NULL: zero */
+  const double* alpha;      /* DEVICE [n_roll], NULL: 1 -- the step length of a line search */
+} fb_feedback;
+int fb_batch_rollout_feedback(fb_batch* b, const fb_rollout_config* cfg, const fb_feedback* fbk,
+                              double* state, double* sensordata, double* ctrl_out, int32_t* status, void* stream);
+
 /* External forces (FB_QFRC_APPLIED, FB_XFRC_APPLIED), MuJoCo's two user inputs for everything that is not an actuator, a contact or the
  * fluid model.  Every substep
  *     qfrc_smooth = qfrc_passive - qfrc_bias + qfrc_actuator + qfrc_applied + sum_b J_b(xipos_b)' xfrc_applied_b
