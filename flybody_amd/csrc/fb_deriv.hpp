@@ -10,26 +10,19 @@
 // from their predecessor.  No task hook runs.
 //
 // Work unit: a TICKET = (frame, column, side), plus one nominal ticket per frame (forward differences divide by it, and so does a centred
-// ctrl column that a range limit made one-sided).  Waves draw tickets with one atomicAdd on a counter the host zeroes on the stream; no
-// ticket waits for another and there is no spin loop.  A wave owns ONE scratch row of the pool (one real + one int arena row per
-// resident wave, never frames x columns); for each ticket it
-//   * prepares the row: the head of the source environment's real row (qpos .. rfac: state, ctrl, warm start) is copied, istate is
-//     zeroed -- the mid-phase neighbour list starts invalid (IS_VL_OK = 0), IS_WARN starts clear -- and everything behind the head is
-//     an output of the position / velocity stages that run first.  The source rows are only read;
-//   * perturbs one coordinate (below), runs the transition with a stage sequence of its own (NOT a mode of d_run: that would move every
-//     step kernel's code) and writes the raw (qpos', qvel', act', sensordata) to the ticket's staging slot.
-// k_fd_assemble, one wave per output column, then forms the quotients in the tangent space.  Which wave drew which ticket does not enter:
-// two calls give the same bits.
+// ctrl column that a range limit made one-sided), drawn onto the pool of scratch rows (fb_side.hpp: the pool, tickets, the row's
+// preparation, the frame the kernel runs in; never frames x columns rows).  For each ticket the wave prepares its row from the frame's
+// environment, perturbs one coordinate (below), runs the transition and writes the raw (qpos', qvel', act', sensordata) to the ticket's
+// staging slot.  k_fd_assemble, one wave per output column, then forms the quotients in the tangent space.  Which wave drew which ticket
+// does not enter: two calls give the same bits.
 //
 // Columns: j < nv: qpos integrated by +-eps e_j; j < 2 nv: qvel; j < ndx = 2 nv + na: act; beyond: ctrl.  Centred: diff(T(x-), T(x+)) / 2 eps,
 // forward: diff(T(x), T(x+)) / eps; diff = differentiatePos on the qpos rows, subtraction elsewhere.  The actuation stage clamps ctrl to
 // ctrlrange, so a ctrl nudge that would leave the range is not taken (MuJoCo's rule): a centred column becomes one-sided on the side that
 // fits, a forward column nudges backwards, and with neither side the column is zero.  fd_ctrl_sides() states the rule once for both kernels.
-//
-// The kernel runs on the step kernel's LDS layout and under its launch bounds, so the FB_NOINLINE stage functions it shares with k_fly are
-// compiled for the same budget and k_fly's code does not change.  FP64 only.
+// FP64 only.
 #pragma once
-#include "fb_step.hpp"
+#include "fb_side.hpp"
 
 // Staging memory of one fb_batch_transition_fd call: the host processes the frames in chunks whose tickets fit this budget
 // (walk_imitation: 669 tickets x 309 doubles = 1.65 MB per centred frame; 4096 frames at once would be 6.8 GB).
@@ -71,30 +64,6 @@ __device__ __forceinline__ int fd_ctrl_sides(const DevModel<real>& M, int i, rea
   return 0;
 }
 
-// q <- q * exp(d e_axis / 2), normalised (mju_quatIntegrate with a unit axis)
-template <typename real>
-__device__ __forceinline__ void fd_rotate_quat(real* q, int axis, real d) {
-  real ax[3] = {0, 0, 0}, qr[4], qq[4] = {q[0], q[1], q[2], q[3]}, res[4];
-  ax[axis] = d < 0 ? (real)-1 : (real)1;
-  axisangle2quat(qr, ax, d < 0 ? -d : d);
-  normquat(qq); mulquat(res, qq, qr); normquat(res);
-  for (int k = 0; k < 4; k++) q[k] = res[k];
-}
-
-// mju_subQuat: the local 3-vector that takes quaternion qa to qb
-template <typename real>
-__device__ __forceinline__ void fd_sub_quat(real* res, const real* qb, const real* qa) {
-  const real ca[4] = {qa[0], -qa[1], -qa[2], -qa[3]};
-  real d[4];
-  mulquat(d, ca, qb);
-  real ax[3] = {d[1], d[2], d[3]};
-  const real s = sqrt(ax[0]*ax[0] + ax[1]*ax[1] + ax[2]*ax[2]);
-  real ang = 2*atan2(s, d[0]);
-  if (ang > (real)3.14159265358979323846) ang -= 2*(real)3.14159265358979323846;
-  const real sc = s > 0 ? ang/s : (real)0;
-  for (int k = 0; k < 3; k++) res[k] = ax[k]*sc;
-}
-
 template <typename real>
 __device__ __forceinline__ void transition_fd_kernel(const DevModel<real>* Mp, const FdArgs<real>& A) {
   constexpr int EPB = LdsCfg<real>::EPB;
@@ -102,13 +71,7 @@ __device__ __forceinline__ void transition_fd_kernel(const DevModel<real>* Mp, c
   __shared__ LdsTab s_tab;
   const DevModel<real>& M = as_constant(*Mp);
   const int tid = threadIdx.x;
-  // the workgroup's elimination-tree tables, staged as fly_kernel stages them
-  for (int i = tid; i < M.nv; i += FB_WAVE*EPB) {
-    s_tab.depth[i] = (uint8_t)M.dof_depth[i]; s_tab.cl[i] = (uint8_t)M.dof_cl[i]; s_tab.gen[i] = (uint8_t)M.dof_gen[i]; s_tab.madr[i] = (uint16_t)M.dof_Madr[i];
-  }
-  for (int i = tid; i < 2*FB_WAVE; i += FB_WAVE*EPB) s_tab.gen[FB_MAXNV + i] = (uint8_t)M.fac_dof[i];
-  for (int i = tid; i < FB_LGEN*FB_MAXCH; i += FB_WAVE*EPB) { s_tab.gk[i] = (uint32_t)M.gen_k[i]; s_tab.gm[2*i] = (uint32_t)M.gen_m[2*i]; s_tab.gm[2*i + 1] = (uint32_t)M.gen_m[2*i + 1]; }
-  __syncthreads();
+  side_stage_tables(M, s_tab, tid);
   const int wave = uniform_int(tid / FB_WAVE), lane = tid % FB_WAVE;
   const int row = uniform_int(blockIdx.x*EPB + wave);
   if (row >= A.nwave) return;
@@ -117,11 +80,8 @@ __device__ __forceinline__ void transition_fd_kernel(const DevModel<real>* Mp, c
   const WS<real> wc = w;
   const int nv = M.nv, na = M.na, nq = M.nq, ndx = 2*nv + na;
   const int per_frame = uniform_int(A.per_frame()), total = uniform_int(A.n_frames*per_frame), nst = fd_nstage(M);
-  const int nhead = (int)M.off.xpos;            // qpos .. rfac: everything in front of the first position-stage output
   for (int guard = 0; guard < (1 << 30); guard++) {
-    int t = 0;
-    if (lane == 0) t = atomicAdd(A.counter, 1);
-    t = uniform_int(__shfl(t, 0, FB_WAVE));
+    const int t = side_draw_ticket(A.counter, lane);
     if (t >= total) return;
     const int f = t / per_frame, k = t - f*per_frame;
     const int env = uniform_int(A.frame_env[f]);
@@ -140,13 +100,7 @@ __device__ __forceinline__ void transition_fd_kernel(const DevModel<real>* Mp, c
       }
       d = sgn*A.eps;
     }
-    // ---- prepare the row: nothing of the row's previous ticket survives
-#ifdef FB_EMULATE
-    for (int i = lane; i < LdsCfg<real>::POOL; i += FB_WAVE) w.lLD[i] = (real)NAN;      // (as on k_fly's ticket path: the LDS pool is not read before it is written)
-#endif
-    for (int i = lane; i < nhead; i += FB_WAVE) w.rb[i] = src[i];
-    for (int i = lane; i < IS_N; i += FB_WAVE) w.istate()[i] = 0;
-    SYNC();
+    side_prepare_row(M, w, src, (const int*)nullptr, false, lane);
     // ---- perturb
     if (lane == 0 && col >= 0) {
       if (col < nv) {
@@ -162,33 +116,17 @@ __device__ __forceinline__ void transition_fd_kernel(const DevModel<real>* Mp, c
     }
     SYNC();
     // ---- the transition: mj_step1 of the state, then n x (mj_step2, Euler, mj_step1)
-    s_kinematics(M, wc, lane); s_com_pos(M, wc, lane); s_crb(M, wc, lane);
-    s_collision(M, wc, lane); s_make_constraint(M, wc, lane);
-    s_velocity(M, wc, false, (int*)nullptr, 0, lane);
+    side_position_velocity(M, wc, lane);
     const int nsub = uniform_int(A.n_substeps);
     for (int s = 0; s < nsub; s++) {
-      s_actuation(M, wc, lane);
-      d_factor(M, wc, false, lane);
-      d_solve(M, wc, true, lane);
-      s_project_constraint(M, wc, 3, lane);
-      const bool need = uniform_int(s_constraint_a(M, wc, lane) ? 1 : 0) != 0;
-      if (need) d_solve(M, wc, false, lane);
-      s_constraint_b(M, wc, lane);
-      s_sensor_acc(M, wc, lane);
-      d_factor(M, wc, true, lane);
-      d_solve(M, wc, true, lane);
-      s_integrate(M, wc, lane);
+      side_substep(M, wc, lane);
       if (s == nsub - 1 && A.skip_tail) break;           // no sensor output wanted: x' is complete behind the Euler stage
-      s_kinematics(M, wc, lane); s_com_pos(M, wc, lane); s_crb(M, wc, lane);
-      s_collision(M, wc, lane); s_make_constraint(M, wc, lane);
-      s_velocity(M, wc, false, (int*)nullptr, 0, lane);
+      side_position_velocity(M, wc, lane);
     }
     SYNC();
     // ---- raw results to the ticket's staging slot
     real* out = A.stage + (size_t)t*nst;
-    for (int i = lane; i < nq; i += FB_WAVE) out[i] = w.qpos()[i];
-    for (int i = lane; i < nv; i += FB_WAVE) out[nq + i] = w.qvel()[i];
-    for (int i = lane; i < na; i += FB_WAVE) out[nq + nv + i] = w.act()[i];
+    side_store_state(M, w, out, lane);
     if (lane < FB_NSENS) out[nq + nv + na + lane] = w.sens()[lane];
     if (lane == 0) {
       const int wbits = w.istate()[IS_WARN];
@@ -235,12 +173,8 @@ __global__ void __launch_bounds__(FB_WAVE) k_fd_assemble(const DevModel<real>* M
     for (int r = lane; r < ndx; r += FB_WAVE) {
       real v = 0;
       if (xa) {
-        if (r < nv) {
-          const int j = M.dof_jntid[r], jt = M.jnt_type[j], qa = M.jnt_qposadr[j], kk = r - M.jnt_dofadr[j];
-          if (jt == JNT_FREE && kk >= 3) { real dq[3]; fd_sub_quat(dq, xb + qa + 3, xa + qa + 3); v = dq[kk - 3]; }
-          else if (jt == JNT_BALL) { real dq[3]; fd_sub_quat(dq, xb + qa, xa + qa); v = dq[kk]; }
-          else v = xb[qa + kk] - xa[qa + kk];
-        } else v = xb[nq + r - nv] - xa[nq + r - nv];     // qvel and act follow qpos in a staging slot
+        if (r < nv) v = side_qpos_diff(M, r, xb, xa);
+        else v = xb[nq + r - nv] - xa[nq + r - nv];       // qvel and act follow qpos in a staging slot
         v /= h;
       }
       Xf[(size_t)r*width + cc] = v;

@@ -1194,15 +1194,65 @@ extern "C" int fb_batch_ik(fb_batch* b, const fb_ik_config* cfg, const double* t
   FB_GUARD_END
 }
 
+// ------------------------------------------------------------------ the calls beside the step (the kernels of fb_side.hpp)
+// fb_batch_inverse, fb_batch_transition_fd and the two rollout calls do not go through launch() and are not timed launches.  Each keeps its own
+// body; what they literally repeated is stated here.
+
+// The refusals of an FP64 side call, in their order.  The texts' words: needs "<what> need(s)", per_model "<what> is / are", kernel the
+// kernel's name, law_why what the inverse adds about the law; forces: applied forces are refused too (the inverse allows them).
+static int side_refusals(const fb_batch* b, const std::string& fn, const char* needs, const char* per_model, const char* kernel, const char* law_why, bool forces) {
+  if (b->precision != 64) return fail(fn + ": " + needs + " an FP64 batch (precision 64)");
+  if (b->n_models() > 1) return fail(fn + ": per-model " + per_model + " not supported: this batch is a group of " + std::to_string(b->n_models()) + " models (fb_batch_create_group)");
+  if (b->law_coef) return fail(fn + ": the " + kernel + " knows no control law" + law_why + "; call fb_batch_set_control_law(batch, NULL) first");
+  if (forces && b->qfrc_applied) return fail(fn + ": the " + kernel + " knows no applied forces; call fb_batch_clear_forces first");
+  return 0;
+}
+// An optional list of n source environments (null: 0 .. n-1); count / item: the texts' names ("n_frames" / "frame").
+static int side_check_env_ids(const fb_batch* b, const std::string& fn, const int32_t* env_ids, int n, const char* count, const char* item) {
+  if (!env_ids && n > b->n_env) return fail(fn + ": environment id out of range (" + count + " exceeds the batch and env_ids is NULL)");
+  if (env_ids) for (int k = 0; k < n; k++) if (env_ids[k] < 0 || env_ids[k] >= b->n_env)
+    return fail(fn + ": environment id " + std::to_string(env_ids[k]) + " out of range (" + item + " " + std::to_string(k) + ")");
+  return 0;
+}
+// Rows `kernel` keeps resident (occupancy x CUs x EPB), at most `cap` where cap > 0, at least 1; cached in `slots`.
+static int side_resident_rows(fb_batch* b, const void* kernel, int cap, int& slots) {
+  if (slots > 0) return 0;
+#ifdef FB_EMULATE
+  (void)kernel; (void)cap; slots = 8;                        // (host emulation has no residency: a few rows, so that the tests can vary the pool)
+#else
+  hipDeviceProp_t prop; HIPCHK(hipGetDeviceProperties(&prop, b->device));
+  constexpr int EPB = LdsCfg<double>::EPB;
+  int nbk = 0;
+  HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nbk, kernel, FB_WAVE*EPB, 0));
+  const int own = nbk*prop.multiProcessorCount*EPB;
+  slots = std::max(1, cap > 0 ? std::min(cap, own) : own);
+#endif
+  return 0;
+}
+// The pool of scratch rows: as many as k_transition_fd keeps resident, at most the step kernel's slots; allocated by the first call that gets that far.
+static int side_pool_rows(fb_batch* b) { return side_resident_rows(b, (const void*)k_transition_fd<double>, b->slots, b->fd_slots); }
+static int side_pool(fb_batch* b) {
+  return alloc_zeroed_once(b->fd_pool_r, (size_t)b->fd_slots*b->off.nreal) || alloc_zeroed_once(b->fd_pool_i, (size_t)b->fd_slots*b->off.nint) ? -1 : 0;
+}
+// Word [1] of a ticket counter {next ticket, tickets finished since the call began}.  Synchronises the device.
+static int side_tickets_done(fb_batch* b, const DevBuf<int>& counter, int64_t* n) {
+  *n = 0;
+  if (!counter) return 0;
+  HIPCHK(hipSetDevice(b->device));
+  HIPCHK(hipDeviceSynchronize());
+  int c[2] = {0, 0};
+  HIPCHK(hipMemcpy(c, counter.get(), sizeof(c), hipMemcpyDeviceToHost));
+  *n = c[1];
+  return 0;
+}
+
 // ------------------------------------------------------------------ inverse dynamics
-// mj_inverse, one frame per environment (fb_inverse.hpp: k_inverse).  Like fb_batch_ik it does not go through launch() and is not a
-// timed launch; it reads FB_QPOS / FB_QVEL / FB_QACC and changes nothing a later control step reads (see fb_inverse.hpp).
+// mj_inverse, one frame per environment (fb_inverse.hpp: k_inverse).  It reads FB_QPOS / FB_QVEL / FB_QACC and changes nothing a later
+// control step reads (see fb_inverse.hpp).
 extern "C" int fb_batch_inverse(fb_batch* b, int flags, void* stream) {
   if (!b) return fail("fb_batch_inverse: null batch");
-  if (b->precision != 64) return fail("fb_batch_inverse: inverse dynamics needs an FP64 batch (precision 64)");
+  if (side_refusals(b, "fb_batch_inverse", "inverse dynamics needs", "inverse dynamics is", "inverse", ": qfrc_inverse would count the law's force as external", false)) return -1;
   if (flags & ~FB_INV_DISCRETE) return fail("fb_batch_inverse: unknown flags");
-  if (b->n_models() > 1) return fail("fb_batch_inverse: per-model inverse dynamics is not supported: this batch is a group of " + std::to_string(b->n_models()) + " models (fb_batch_create_group)");
-  if (b->law_coef) return fail("fb_batch_inverse: the inverse knows no control law: qfrc_inverse would count the law's force as external; call fb_batch_set_control_law(batch, NULL) first");
   FB_GUARD_BEGIN
   const int n = b->n_env, nv = b->m->nv;
   HIPCHK(hipSetDevice(b->device));
@@ -1228,49 +1278,28 @@ extern "C" int fb_batch_inverse(fb_batch* b, int flags, void* stream) {
 
 // ------------------------------------------------------------------ transition derivatives
 // mjd_transitionFD for the listed environments (fb_deriv.hpp: k_transition_fd draws (frame, column, side) tickets onto a pool of scratch rows,
-// k_fd_assemble forms the quotients).  Like fb_batch_ik / fb_batch_inverse it does not go through launch() and is not a timed launch.  The
-// environments' rows are only read: state, caches, warm start, warnings, size statistics and step ticks stay as they were.
-static int fd_resident_slots(fb_batch* b) {
-  if (b->fd_slots > 0) return 0;
-#ifdef FB_EMULATE
-  b->fd_slots = 8;                                           // (host emulation has no residency: a few rows, so that the tests can vary the pool)
-#else
-  hipDeviceProp_t prop; HIPCHK(hipGetDeviceProperties(&prop, b->device));
-  constexpr int EPB = LdsCfg<double>::EPB;
-  int nbk = 0;
-  HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nbk, (const void*)k_transition_fd<double>, FB_WAVE*EPB, 0));
-  const int own = nbk*prop.multiProcessorCount*EPB;
-  b->fd_slots = std::max(1, b->slots > 0 ? std::min(b->slots, own) : own);
-#endif
-  return 0;
-}
-
+// k_fd_assemble forms the quotients).  The environments' rows are only read: state, caches, warm start, warnings, size statistics and step
+// ticks stay as they were.
 extern "C" int fb_batch_transition_fd(fb_batch* b, const fb_fd_config* cfg, double* A, double* Bm, double* Cm, double* Dm, int32_t* status, void* stream) {
   if (!b) return fail("fb_batch_transition_fd: null batch");
   if (!cfg) return fail("fb_batch_transition_fd: null config");
-  if (b->precision != 64) return fail("fb_batch_transition_fd: transition derivatives need an FP64 batch (precision 64)");
-  if (b->n_models() > 1) return fail("fb_batch_transition_fd: per-model derivatives are not supported: this batch is a group of " + std::to_string(b->n_models()) + " models (fb_batch_create_group)");
-  if (b->law_coef) return fail("fb_batch_transition_fd: the derivative kernel knows no control law; call fb_batch_set_control_law(batch, NULL) first");
-  if (b->qfrc_applied) return fail("fb_batch_transition_fd: the derivative kernel knows no applied forces; call fb_batch_clear_forces first");
+  if (side_refusals(b, "fb_batch_transition_fd", "transition derivatives need", "derivatives are", "derivative kernel", "", true)) return -1;
   if (!A && !Bm && !Cm && !Dm) return fail("fb_batch_transition_fd: all four outputs are NULL");
   if (!std::isfinite(cfg->eps) || !(cfg->eps > 0)) return fail("fb_batch_transition_fd: eps must be finite and > 0");
   if (cfg->n_substeps < 1) return fail("fb_batch_transition_fd: n_substeps must be >= 1");
   if (cfg->n_frames < 1) return fail("fb_batch_transition_fd: n_frames must be >= 1");
   if (cfg->centered != 0 && cfg->centered != 1) return fail("fb_batch_transition_fd: centered must be 0 or 1");
-  if (!cfg->env_ids && cfg->n_frames > b->n_env) return fail("fb_batch_transition_fd: environment id out of range (n_frames exceeds the batch and env_ids is NULL)");
-  if (cfg->env_ids) for (int k = 0; k < cfg->n_frames; k++) if (cfg->env_ids[k] < 0 || cfg->env_ids[k] >= b->n_env)
-    return fail("fb_batch_transition_fd: environment id " + std::to_string(cfg->env_ids[k]) + " out of range (frame " + std::to_string(k) + ")");
+  if (side_check_env_ids(b, "fb_batch_transition_fd", cfg->env_ids, cfg->n_frames, "n_frames", "frame")) return -1;
   FB_GUARD_BEGIN
   HIPCHK(hipSetDevice(b->device));
-  if (fd_resident_slots(b)) return -1;
+  if (side_pool_rows(b)) return -1;
   if (cfg->pool_rows < 0 || cfg->pool_rows > b->fd_slots) return fail("fb_batch_transition_fd: pool_rows out of range (0, or 1 .. " + std::to_string(b->fd_slots) + " resident slots)");
   hipStream_t st = (hipStream_t)stream;
   const fb_model* m = b->m;
   const int nf = cfg->n_frames, ndx = 2*m->nv + m->na, nst = m->nq + m->nv + m->na + FB_NSENS;
   const int c0 = (A || Cm) ? 0 : ndx, c1 = (Bm || Dm) ? ndx + m->nu : ndx, sides = cfg->centered ? 2 : 1, per_frame = 1 + sides*(c1 - c0);
   if (c1 <= c0) return fail("fb_batch_transition_fd: the outputs asked for have no column (a model without controls has no B or D)");
-  if (alloc_zeroed_once(b->fd_pool_r, (size_t)b->fd_slots*b->off.nreal) || alloc_zeroed_once(b->fd_pool_i, (size_t)b->fd_slots*b->off.nint) ||
-      alloc_zeroed_once(b->fd_counter, 2)) return -1;
+  if (side_pool(b) || alloc_zeroed_once(b->fd_counter, 2)) return -1;
   // frames per chunk: the tickets' staging slots stay inside the budget
   const size_t frame_bytes = (size_t)per_frame*nst*sizeof(double);
   const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)nf, FB_FD_STAGING_BYTES/frame_bytes));
@@ -1311,29 +1340,18 @@ extern "C" int fb_batch_transition_fd(fb_batch* b, const fb_fd_config* cfg, doub
 // Synchronises the device.  A debug counter: the tests count columns with it instead of timing them.
 extern "C" int fb_batch_fd_tickets(fb_batch* b, int64_t* n) {
   if (!b || !n) return fail("fb_batch_fd_tickets: null argument");
-  *n = 0;
-  if (!b->fd_counter) return 0;
-  HIPCHK(hipSetDevice(b->device));
-  HIPCHK(hipDeviceSynchronize());
-  int c[2] = {0, 0};
-  HIPCHK(hipMemcpy(c, b->fd_counter.get(), sizeof(c), hipMemcpyDeviceToHost));
-  *n = c[1];
-  return 0;
+  return side_tickets_done(b, b->fd_counter, n);
 }
 
 // ------------------------------------------------------------------ rollouts, open and closed loop
 // MuJoCo's rollout for the listed environments (fb_rollout.hpp: k_rollout / k_closedloop_rollout draw one ticket per rollout onto the scratch
-// rows fb_batch_transition_fd owns too).  Like that call they do not go through launch() and are not timed launches, and the environments'
-// rows are only read.  Steady state: no host synchronisation, one upload (the rollouts' source environments, and their nominals behind them).
+// rows fb_batch_transition_fd owns too); the environments' rows are only read.  Steady state: no host synchronisation, one upload (the rollouts' source environments, and their nominals behind them).
 // Both entry points are run_rollout: fbk == NULL is the open-loop one.  fn: the entry point's name, for the refusals.
 static int run_rollout(fb_batch* b, const std::string& fn, const fb_rollout_config* cfg, const double* ctrl, const float* action, const fb_feedback* fbk,
                        bool feedback, double* state, double* sensordata, double* ctrl_out, int32_t* status, void* stream) {
   if (!b) return fail(fn + ": null batch");
   if (!cfg) return fail(fn + ": null config");
-  if (b->precision != 64) return fail(fn + ": rollouts need an FP64 batch (precision 64)");
-  if (b->n_models() > 1) return fail(fn + ": per-model rollouts are not supported: this batch is a group of " + std::to_string(b->n_models()) + " models (fb_batch_create_group)");
-  if (b->law_coef) return fail(fn + ": the rollout kernel knows no control law; call fb_batch_set_control_law(batch, NULL) first");
-  if (b->qfrc_applied) return fail(fn + ": the rollout kernel knows no applied forces; call fb_batch_clear_forces first");
+  if (side_refusals(b, fn, "rollouts need", "rollouts are", "rollout kernel", "", true)) return -1;
   if (!state) return fail(fn + ": the state output is NULL");
   if (!feedback) {
     if (ctrl && action) return fail(fn + ": both ctrl and action are given; a rollout takes exactly one of them");
@@ -1342,9 +1360,7 @@ static int run_rollout(fb_batch* b, const std::string& fn, const fb_rollout_conf
   if (cfg->n_roll < 1) return fail(fn + ": n_roll must be >= 1");
   if (cfg->horizon < 1) return fail(fn + ": horizon must be >= 1");
   if (cfg->n_substeps < 0) return fail(fn + ": n_substeps must be >= 0 (0: the model's own)");
-  if (!cfg->env_ids && cfg->n_roll > b->n_env) return fail(fn + ": environment id out of range (n_roll exceeds the batch and env_ids is NULL)");
-  if (cfg->env_ids) for (int k = 0; k < cfg->n_roll; k++) if (cfg->env_ids[k] < 0 || cfg->env_ids[k] >= b->n_env)
-    return fail(fn + ": environment id " + std::to_string(cfg->env_ids[k]) + " out of range (rollout " + std::to_string(k) + ")");
+  if (side_check_env_ids(b, fn, cfg->env_ids, cfg->n_roll, "n_roll", "rollout")) return -1;
   if (action && b->m->task_id == FB_TASK_FLIGHT_IMITATION && !b->have_wbpg) return fail(fn + ": an action rollout of the flight task needs fb_batch_set_wbpg first");
   if (feedback) {
     if (!fbk) return fail(fn + ": null feedback");
@@ -1359,24 +1375,13 @@ static int run_rollout(fb_batch* b, const std::string& fn, const fb_rollout_conf
   }
   FB_GUARD_BEGIN
   HIPCHK(hipSetDevice(b->device));
-  if (fd_resident_slots(b)) return -1;
-  int& slots = feedback ? b->roll_fb_slots : b->roll_slots;
-  if (slots == 0) {
-#ifdef FB_EMULATE
-    slots = b->fd_slots;
-#else
-    hipDeviceProp_t prop; HIPCHK(hipGetDeviceProperties(&prop, b->device));
-    int nbk = 0;
-    const void* kern = feedback ? (const void*)k_closedloop_rollout<double> : (const void*)k_rollout<double>;
-    HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nbk, kern, FB_WAVE*LdsCfg<double>::EPB, 0));
-    slots = std::max(1, std::min(b->fd_slots, nbk*prop.multiProcessorCount*LdsCfg<double>::EPB));
-#endif
-  }
+  int& slots = feedback ? b->roll_fb_slots : b->roll_slots;       // the rows this call's own kernel keeps resident, at most the pool's
+  if (side_pool_rows(b) ||
+      side_resident_rows(b, feedback ? (const void*)k_closedloop_rollout<double> : (const void*)k_rollout<double>, b->fd_slots, slots)) return -1;
   if (cfg->pool_rows < 0 || cfg->pool_rows > slots) return fail(fn + ": pool_rows out of range (0, or 1 .. " + std::to_string(slots) + " scratch rows)");
   hipStream_t st = (hipStream_t)stream;
   const int nr = cfg->n_roll;
-  if (alloc_zeroed_once(b->fd_pool_r, (size_t)b->fd_slots*b->off.nreal) || alloc_zeroed_once(b->fd_pool_i, (size_t)b->fd_slots*b->off.nint) ||
-      alloc_zeroed_once(b->roll_counter, 2)) return -1;
+  if (side_pool(b) || alloc_zeroed_once(b->roll_counter, 2)) return -1;
   const int nsub = cfg->n_substeps > 0 ? cfg->n_substeps : b->m->nsubstep;
   const size_t nctr = (size_t)cfg->horizon*nsub;        // one progress counter per substep of a rollout (k_rollout: tail-aware priorities)
   const size_t nids = (size_t)nr*(feedback ? 2 : 1);    // the environments, and for a closed-loop call the nominals behind them: one upload
@@ -1424,14 +1429,7 @@ extern "C" int fb_batch_rollout_feedback(fb_batch* b, const fb_rollout_config* c
 // Rollouts the last fb_batch_rollout / fb_batch_rollout_feedback call finished.  Synchronises the device.  A debug counter, like fb_batch_fd_tickets.
 extern "C" int fb_batch_rollouts_run(fb_batch* b, int64_t* n) {
   if (!b || !n) return fail("fb_batch_rollouts_run: null argument");
-  *n = 0;
-  if (!b->roll_counter) return 0;
-  HIPCHK(hipSetDevice(b->device));
-  HIPCHK(hipDeviceSynchronize());
-  int c[2] = {0, 0};
-  HIPCHK(hipMemcpy(c, b->roll_counter.get(), sizeof(c), hipMemcpyDeviceToHost));
-  *n = c[1];
-  return 0;
+  return side_tickets_done(b, b->roll_counter, n);
 }
 
 // ------------------------------------------------------------------ field access

@@ -4,10 +4,8 @@
 // (M with armature; qfrc_passive = springs, dampers and both fluid models, as d_passive computes them; f = the soft-constraint primal map
 // of the limit rows, frictionless contacts and elliptic cones -- no solver runs).
 //
-// The position and velocity stages of a forward pass run unchanged, in d_run's order (s_kinematics, s_com_pos, s_crb, s_collision,
-// s_make_constraint, s_velocity: fb_step.hpp), on the step kernel's LDS layout (pool + elimination-tree tables, EPB environments per
-// workgroup) and under the step kernel's launch bounds, so the stage functions it shares with k_fly are compiled for the same budget and
-// k_fly's code does not change.  Then, new here:
+// The position and velocity stages of a forward pass run unchanged, in the frame every kernel beside k_fly runs in (fb_side.hpp: the step
+// kernel's LDS layout and launch bounds, side_stage_tables, side_position_velocity).  Then, new here:
 //   * FB_INV_DISCRETE (MuJoCo's mjENBL_INVDISCRETE for semi-implicit Euler with implicit joint damping): qacc is read as
 //     (qvel+ - qvel) / h and converted to the continuous acceleration M^-1 (M + h D) qacc = qacc + M^-1 (h D qacc)  (d_factor / d_solve);
 //   * M qacc, lane == dof over the sparse qM: dof i's row holds its ancestors (qM[dof_Madr[i] + depth difference]), its column the
@@ -22,9 +20,9 @@
 //
 // What it writes: the position / velocity stage outputs (derived from qpos / qvel, as fb_batch_forward refreshes them), efc_vel /
 // efc_aref / efc_jar / efc_force, qfrc_constraint, and the two result arrays.  It reads qacc and writes neither qacc nor qacc_ws, so a
-// control step after it starts from the same state.  DESIGN.md 13; tests/test_inverse_resources.py pins its residency.
+// control step after it starts from the same state.  DESIGN.md 13; tests/test_side_kernel_resources.py pins its residency.
 #pragma once
-#include "fb_step.hpp"
+#include "fb_side.hpp"
 
 enum { FB_INV_FLAG_DISCRETE = 1 };
 
@@ -42,25 +40,14 @@ __device__ __forceinline__ void inverse_kernel(const DevModel<real>* Mp, real* r
   __shared__ LdsTab s_tab;
   const DevModel<real>& M = as_constant(*Mp);
   const int tid = threadIdx.x;
-  // the workgroup's elimination-tree tables, staged as fly_kernel stages them
-  for (int i = tid; i < M.nv; i += FB_WAVE*EPB) {
-    s_tab.depth[i] = (uint8_t)M.dof_depth[i]; s_tab.cl[i] = (uint8_t)M.dof_cl[i]; s_tab.gen[i] = (uint8_t)M.dof_gen[i]; s_tab.madr[i] = (uint16_t)M.dof_Madr[i];
-  }
-  for (int i = tid; i < 2*FB_WAVE; i += FB_WAVE*EPB) s_tab.gen[FB_MAXNV + i] = (uint8_t)M.fac_dof[i];
-  for (int i = tid; i < FB_LGEN*FB_MAXCH; i += FB_WAVE*EPB) { s_tab.gk[i] = (uint32_t)M.gen_k[i]; s_tab.gm[2*i] = (uint32_t)M.gen_m[2*i]; s_tab.gm[2*i + 1] = (uint32_t)M.gen_m[2*i + 1]; }
-  __syncthreads();
+  side_stage_tables(M, s_tab, tid);
   const int wave = uniform_int(tid / FB_WAVE), lane = tid % FB_WAVE;
   const int env = uniform_int(blockIdx.x*EPB + wave);
   if (env >= A.n_env) return;
   const WS<real> w = ws_env(M, rarena, iarena, env, s_pool, wave, &s_tab);
   const WS<real> wc = w;
   // ---- mj_invPosition + mj_invVelocity: the forward pass's stages, unchanged
-  s_kinematics(M, wc, lane);
-  s_com_pos(M, wc, lane);
-  s_crb(M, wc, lane);
-  s_collision(M, wc, lane);
-  s_make_constraint(M, wc, lane);
-  s_velocity(M, wc, false, (int*)nullptr, 0, lane);
+  side_position_velocity(M, wc, lane);
   const int nv = M.nv;
   // ---- the continuous acceleration, in the solve vector lx (the LDS pool is free behind the velocity stage)
   FB_LDS real* Q = w.lx();

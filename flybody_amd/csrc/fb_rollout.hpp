@@ -5,30 +5,22 @@
 // s_post, reward, termination, auto-reset, dataset or ghost logic; a rollout from an environment at LAST continues its physics.
 // DESIGN.md 20.
 //
-// Work unit: a TICKET = one rollout.  Waves draw tickets with one atomicAdd on a counter the host zeroes on the stream; no ticket waits
-// for another and there is no spin loop.  A wave owns ONE scratch row of the pool fb_batch_transition_fd owns too (fb_deriv.hpp: one
-// real + one int arena row per resident wave, never one per rollout); for each ticket it
-//   * prepares the row as k_transition_fd does: the head of the source environment's real row (qpos .. rfac: state, ctrl, warm start,
-//     simtime, the pattern generator's filtered frequency) is copied, istate is zeroed -- the mid-phase neighbour list starts invalid,
-//     IS_WARN starts clear -- and, for an action rollout, the two task words s_pre reads from the int row (IS_WB_STEP, IS_WB_FREQ:
-//     fb_task.hpp, d_flight_pre) follow the source's.  Everything behind the head is an output of the position / velocity stages that
-//     run first.  The source rows are only read;
-//   * runs the position and velocity stages of the copied state once, then per interval: the input, n substeps in d_run's order
-//     (actuation .. acceleration sensors, Euler with implicit damping, position + velocity stages of the new state; noslip included),
-//     and the record [r][t] = (qpos', qvel', act') -- and sensordata as the interval's last substep leaves it -- straight into the
-//     caller's buffers.  The first constraint solve warm-starts from the source row's qacc_ws, every later one from its predecessor.
+// Work unit: a TICKET = one rollout, drawn onto the pool of scratch rows (fb_side.hpp: the pool, tickets, the row's preparation, the
+// frame the kernel runs in; never one row per rollout).  For each ticket the wave
+//   * prepares its row from the rollout's source environment; for an action rollout the two pattern-generator words of the int row
+//     follow the source's, because s_pre reads them;
+//   * runs the position and velocity stages of the copied state once, then per interval: the input, n substeps (side_substep and the
+//     position + velocity stages of the new state), and the record [r][t] = (qpos', qvel', act') -- and sensordata as the interval's
+//     last substep leaves it -- straight into the caller's buffers.  The first constraint solve warm-starts from the source row's
+//     qacc_ws, every later one from its predecessor.
 // status[r] = the OR of the FB_WARN_* bits the rollout raised, one plain store at its end.  Which wave drew which rollout does not
-// enter: two calls give the same bits, with any number of rows.
+// enter: two calls give the same bits, with any number of rows.  FP64 only.
 //
-// The stage sequence is the kernel's own (NOT a mode of d_run: that would move every step kernel's code).  The kernel runs on the step
-// kernel's LDS layout and under its launch bounds, so the FB_NOINLINE stage functions it shares with k_fly and k_transition_fd are
-// compiled for the same budget and their code does not change.  FP64 only.
-//
-// CLOSED-LOOP rollouts (k_closedloop_rollout): a kernel of its own next to k_rollout -- not a mode of it, for the reason above:
+// CLOSED-LOOP rollouts (k_closedloop_rollout): a kernel of its own next to k_rollout -- not a mode of it, for fb_side.hpp's reason:
 // a run-time switch would move k_rollout's code -- that differs in one thing, the interval's input.  Tickets, rows, LDS layout, launch
 // bounds, stage sequence, priorities, records and status are rollout_kernel's, stated once; the template argument FEEDBACK selects the
 // input at compile time.  At the start of interval t the wave evaluates a time-varying affine feedback on the row's own state:
-//     dx  = x_t (-) xnom[nom][t]                     the tangent space of fb_deriv.hpp (dq[nv], dv[nv], dact[na]); rotations by fd_sub_quat
+//     dx  = x_t (-) xnom[nom][t]                     the tangent space of fb_side.hpp (dq[nv], dv[nv], dact[na]; side_qpos_diff)
 //     u_i = clamp( unom[nom][t][i] + (alpha[r]*k[nom][t][i] + sum_j K[nom][t][i][j]*dx[j]) )
 // clamp = clampr to act_ctrlrange where act_ctrllimited: s_actuation's own function and condition, so the stage's clamp is the identity on
 // it.  u goes to w.ctrl() and to the optional record [r][t][nu].  Mapping: lane == output i (blocks of 64 for nu > 64); dx lives in
@@ -38,8 +30,7 @@
 // j = 0 .. ndx-1 in ascending order in ONE accumulator per output, from 0: fixed by the code, the same bits for any pool and any call.
 // No LDS beyond the step kernel's layout.  Feedback is on ctrl only: an action-space law (the pattern generator in the loop) is not offered.
 #pragma once
-#include "fb_step.hpp"
-#include "fb_deriv.hpp"
+#include "fb_side.hpp"
 
 template <typename real>
 struct RolloutArgs {
@@ -86,12 +77,7 @@ template <typename real> FB_STAGE_C void s_feedback(const DevModel<real>& M_, co
   for (int m = 0; m < NS; m++) {
     const int c = lane + FB_WAVE*m;
     real v = 0;
-    if (c < nv) {
-      const int j = M.dof_jntid[c], jt = M.jnt_type[j], qa = M.jnt_qposadr[j], kk = c - M.jnt_dofadr[j];
-      if (jt == JNT_FREE && kk >= 3) { real dq[3]; fd_sub_quat(dq, w.qpos() + qa + 3, xn + qa + 3); v = dq[kk - 3]; }
-      else if (jt == JNT_BALL) { real dq[3]; fd_sub_quat(dq, w.qpos() + qa, xn + qa); v = dq[kk]; }
-      else v = w.qpos()[qa + kk] - xn[qa + kk];
-    }
+    if (c < nv) v = side_qpos_diff(M, c, (const real*)w.qpos(), xn);
     else if (c < 2*nv) v = w.qvel()[c - nv] - xn[nq + c - nv];
     else if (c < ndx) v = w.act()[c - 2*nv] - xn[nq + nv + c - 2*nv];
     dx[m] = v;
@@ -135,13 +121,7 @@ __device__ __forceinline__ void rollout_kernel(const DevModel<real>* Mp, const R
   __shared__ LdsTab s_tab;
   const DevModel<real>& M = as_constant(*Mp);
   const int tid = threadIdx.x;
-  // the workgroup's elimination-tree tables, staged as fly_kernel stages them
-  for (int i = tid; i < M.nv; i += FB_WAVE*EPB) {
-    s_tab.depth[i] = (uint8_t)M.dof_depth[i]; s_tab.cl[i] = (uint8_t)M.dof_cl[i]; s_tab.gen[i] = (uint8_t)M.dof_gen[i]; s_tab.madr[i] = (uint16_t)M.dof_Madr[i];
-  }
-  for (int i = tid; i < 2*FB_WAVE; i += FB_WAVE*EPB) s_tab.gen[FB_MAXNV + i] = (uint8_t)M.fac_dof[i];
-  for (int i = tid; i < FB_LGEN*FB_MAXCH; i += FB_WAVE*EPB) { s_tab.gk[i] = (uint32_t)M.gen_k[i]; s_tab.gm[2*i] = (uint32_t)M.gen_m[2*i]; s_tab.gm[2*i + 1] = (uint32_t)M.gen_m[2*i + 1]; }
-  __syncthreads();
+  side_stage_tables(M, s_tab, tid);
   const int wave = uniform_int(tid / FB_WAVE), lane = tid % FB_WAVE;
   const int row = uniform_int(blockIdx.x*EPB + wave);
   if (row >= A.nwave) return;
@@ -149,13 +129,10 @@ __device__ __forceinline__ void rollout_kernel(const DevModel<real>* Mp, const R
   const WS<real> w = ws_env(M, A.pool_r, A.pool_i, row, s_pool, wave, &s_tab);
   const WS<real> wc = w;
   const int nv = M.nv, na = M.na, nq = M.nq, nu = M.nu, nx = nq + nv + na;
-  const int nhead = (int)M.off.xpos;            // qpos .. rfac: everything in front of the first position-stage output
   const int total = uniform_int(A.n_roll), T = uniform_int(A.horizon), nsub = uniform_int(A.n_substeps);
   const bool by_action = uniform_int(A.action ? 1 : 0) != 0, want_sens = uniform_int(A.sens ? 1 : 0) != 0;
   for (int guard = 0; guard < (1 << 30); guard++) {
-    int r = 0;
-    if (lane == 0) r = atomicAdd(A.counter, 1);
-    r = uniform_int(__shfl(r, 0, FB_WAVE));
+    const int r = side_draw_ticket(A.counter, lane);
     if (r >= total) return;
     const int env = uniform_int(A.roll_env[r]);
     int nom = 0;
@@ -163,17 +140,8 @@ __device__ __forceinline__ void rollout_kernel(const DevModel<real>* Mp, const R
     if constexpr (FEEDBACK) { nom = uniform_int(F.roll_nom[r]); if (F.alpha) al = F.alpha[r]; }
     const real* src = A.rarena + (size_t)env*M.off.nreal;
     const int* isrc = A.iarena + (size_t)env*M.off.nint + M.off.istate;
-    // ---- prepare the row: nothing of the row's previous ticket survives
-#ifdef FB_EMULATE
-    for (int i = lane; i < LdsCfg<real>::POOL; i += FB_WAVE) w.lLD[i] = (real)NAN;      // (as on k_fly's ticket path: the LDS pool is not read before it is written)
-#endif
-    for (int i = lane; i < nhead; i += FB_WAVE) w.rb[i] = src[i];
-    for (int i = lane; i < IS_N; i += FB_WAVE) w.istate()[i] = (by_action && (i == IS_WB_STEP || i == IS_WB_FREQ)) ? isrc[i] : 0;
-    SYNC();
-    // ---- mj_step1 of the copied state
-    s_kinematics(M, wc, lane); s_com_pos(M, wc, lane); s_crb(M, wc, lane);
-    s_collision(M, wc, lane); s_make_constraint(M, wc, lane);
-    s_velocity(M, wc, false, (int*)nullptr, 0, lane);
+    side_prepare_row(M, w, src, isrc, by_action, lane);
+    side_position_velocity(M, wc, lane);
     for (int t = 0; t < T; t++) {
       const size_t rec = (size_t)r*T + t;
       // ---- the interval's input
@@ -190,20 +158,9 @@ __device__ __forceinline__ void rollout_kernel(const DevModel<real>* Mp, const R
       }
       // ---- n x (mj_step2, Euler, mj_step1)
       for (int s = 0; s < nsub; s++) {
-        s_actuation(M, wc, lane);
-        d_factor(M, wc, false, lane);
-        d_solve(M, wc, true, lane);
-        s_project_constraint(M, wc, 3, lane);
-        const bool need = uniform_int(s_constraint_a(M, wc, lane) ? 1 : 0) != 0;
-        if (need) d_solve(M, wc, false, lane);
-        s_constraint_b(M, wc, lane);
-        s_sensor_acc(M, wc, lane);
-        d_factor(M, wc, true, lane);
-        d_solve(M, wc, true, lane);
-        s_integrate(M, wc, lane);
+        side_substep(M, wc, lane);
         if (s == nsub - 1 && t == T - 1 && !want_sens) break;      // no sensor output wanted: x' is complete behind the Euler stage, and nothing follows
-        s_kinematics(M, wc, lane); s_com_pos(M, wc, lane); s_crb(M, wc, lane);
-        s_collision(M, wc, lane); s_make_constraint(M, wc, lane);
+        side_position(M, wc, lane);
         // tail-aware issue priority, as in d_run: with a rollout per row the launch ends with its slowest rollout, and every wave is
         // resident from the start; each wave counts itself into the substep's counter, and the more were there before it, the higher its
         // priority for the next substep
@@ -212,10 +169,7 @@ __device__ __forceinline__ void rollout_kernel(const DevModel<real>* Mp, const R
       }
       SYNC();
       // ---- the record [r][t], straight to the caller's buffers
-      real* out = A.state + rec*nx;
-      for (int i = lane; i < nq; i += FB_WAVE) out[i] = w.qpos()[i];
-      for (int i = lane; i < nv; i += FB_WAVE) out[nq + i] = w.qvel()[i];
-      for (int i = lane; i < na; i += FB_WAVE) out[nq + nv + i] = w.act()[i];
+      side_store_state(M, w, A.state + rec*nx, lane);
       if (want_sens && lane < FB_NSENS) A.sens[rec*FB_NSENS + lane] = w.sens()[lane];
     }
     if (lane == 0) {
