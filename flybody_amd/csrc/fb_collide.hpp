@@ -20,7 +20,11 @@ FBD void support(const CGeom<real>& g, const real* dir, real* out) {
   mulmatT3(l, g.mat, dir);
   // Round 5: all four shapes by SELECTS.  The lanes of a narrow-phase pass hold different geom types, so a branch per type made the
   // wave run every branch anyway -- plus a saveexec / branch / restore around each, twice per support pair and ~25 times per pass.
-  // Same arithmetic per shape (the unused shapes' square roots are computed and dropped).
+  // Same arithmetic per shape.  What the compiler makes of it on gfx950 (both FP64 builds and FP32, narrow_mpr_pair): the sphere / capsule
+  // expression and the zeroing are selects; the ellipsoid chain (s0..s2, ne, nie, its products) and the cylinder chain (nc, nic, its
+  // products) are each sunk under their class predicate, behind s_and_saveexec / s_cbranch_execz.  So a class whose last lane has left
+  // the refinement loop is ALREADY skipped: a wave-uniform class mask in front of the two chains removes no vector instruction
+  // (tried and measured: profiles/ab_support_classes.txt).
   const bool caps = g.type == GEOM_CAPSULE, ell = g.type == GEOM_ELLIPSOID, cyl = g.type == GEOM_CYLINDER, sph = g.type == GEOM_SPHERE;
   const real s0 = g.size[0]*l[0], s1 = g.size[1]*l[1], s2 = g.size[2]*l[2];
   real nie, nic;                                                       // (reciprocals: used only where the norm is >= FB_MINV)
@@ -251,30 +255,62 @@ __device__ __forceinline__ bool mpr_penetration(const S& sup, real* depth, real*
     sub3(va, P.v[1], P.v[0]); sub3(vb, P.v[2], P.v[0]);
     cross3(d, va, vb); normalize3(d);
   }
-  for (int it = 0;; it++) {
-    portal_dir(P, d);
-    if (dot3(d, P.v[1]) >= 0) break;
-    sup.support_md(d, v4);
-    FB_STAT(21);
-    if (it > MPR_ITER) *hit_cap = 1;
-    if (dot3(v4.v, d) < 0 || reach_tol(P, v4.v, d) || it > MPR_ITER) { FB_STAT(13); return false; }
-    expand_portal(P, v4);
-  }
-  for (int it = 0;; it++) {
-    portal_dir(P, d);
-    sup.support_md(d, v4);
-    FB_STAT(22);
-    if (reach_tol(P, v4.v, d) || it > MPR_ITER) {
-      FB_STAT(14);
-      if (it > MPR_ITER && !reach_tol(P, v4.v, d)) *hit_cap = 1;
-      real wit[3];
-      real d2 = origin_tri_dist2(P.v[1], P.v[2], P.v[3], wit);
-      *depth = fb_sqrt(d2);
-      if (*depth < MPR_EPS) copy3(dir, d); else { copy3(dir, wit); normalize3(dir); }
-      find_pos<real, S>(sup, P, pos);
-      return true;
+  // The two refinement phases in ONE loop.  Phase A pushes the portal outwards until the origin lies behind it (dot(d, v1) >= 0; a
+  // support point short of the origin or within tolerance of the portal on the way: no penetration), phase B pushes on until the
+  // portal is within tolerance of the surface.  Both iterate portal_dir -> support -> reach_tol -> expand_portal.  As two loops one
+  // after the other the WAVE ran max(A) + max(B) iterations over its pairs -- a pair that misses spends all its iterations in A, a
+  // pair that penetrates nearly all of them in B, so lanes done with A idled until the last miss was decided.  In one loop with the
+  // phase as lane state the wave runs max(A + B).  A lane sees the same portal, direction and support point in the same order as
+  // before (phase B's first direction is the one phase A ended on: same portal, same value), with its own iteration count per phase.
+  // FP64 only.  In FP32 the compiler forms the portal algebra with packed instructions and contracts the two loops' copies of it
+  // differently (phase A: v_pk_mul + v_pk_add, phase B: v_pk_fma; the norm's sum in another order), so phase B's first direction is
+  // NOT the last bits of the one phase A ended on and no single loop reproduces both: the FP32 build keeps the two loops.
+  if constexpr (sizeof(real) != 8) {
+    for (int it = 0;; it++) {
+      portal_dir(P, d);
+      if (dot3(d, P.v[1]) >= 0) break;
+      sup.support_md(d, v4);
+      FB_STAT(21);
+      if (it > MPR_ITER) *hit_cap = 1;
+      if (dot3(v4.v, d) < 0 || reach_tol(P, v4.v, d) || it > MPR_ITER) { FB_STAT(13); return false; }
+      expand_portal(P, v4);
     }
-    expand_portal(P, v4);
+    for (int it = 0;; it++) {
+      portal_dir(P, d);
+      sup.support_md(d, v4);
+      FB_STAT(22);
+      if (reach_tol(P, v4.v, d) || it > MPR_ITER) {
+        FB_STAT(14);
+        if (it > MPR_ITER && !reach_tol(P, v4.v, d)) *hit_cap = 1;
+        real wit[3];
+        real d2 = origin_tri_dist2(P.v[1], P.v[2], P.v[3], wit);
+        *depth = fb_sqrt(d2);
+        if (*depth < MPR_EPS) copy3(dir, d); else { copy3(dir, wit); normalize3(dir); }
+        find_pos<real, S>(sup, P, pos);
+        return true;
+      }
+      expand_portal(P, v4);
+    }
+  } else {
+    bool refine = false, reached, over;
+    for (int it = 0;; it++) {
+      portal_dir(P, d);
+      if (!refine && dot3(d, P.v[1]) >= 0) { refine = true; it = 0; }
+      sup.support_md(d, v4);
+      if (refine) FB_STAT(22); else FB_STAT(21);
+      reached = reach_tol(P, v4.v, d); over = it > MPR_ITER;
+      if (reached || over || (!refine && dot3(v4.v, d) < 0)) break;
+      expand_portal(P, v4);
+    }
+    if (!refine) { if (over) *hit_cap = 1; FB_STAT(13); return false; }
+    FB_STAT(14);
+    if (over && !reached) *hit_cap = 1;
+    real wit[3];
+    real d2 = origin_tri_dist2(P.v[1], P.v[2], P.v[3], wit);
+    *depth = fb_sqrt(d2);
+    if (*depth < MPR_EPS) copy3(dir, d); else { copy3(dir, wit); normalize3(dir); }
+    find_pos<real, S>(sup, P, pos);
+    return true;
   }
 }
 
@@ -601,7 +637,9 @@ __device__ __forceinline__ void d_collision(const DevModel<real>& M, const WS<re
   const int vskip = (vld > 0) ? uniform_int(w.istate()[IS_VL_SKIP]) : 0;
   if (vld > 0 && vskip == 0) {
     okf = w.istate()[IS_VL_OK]; nlist = w.istate()[IS_VL_N];
-    const real lim = (real)0.999999*vld*vld;
+    // (the slack factor covers the rounding of the displacement test itself: in FP32 the differences of world coordinates of order 1 carry ~1e-7
+    //  absolute error against a delta of ~1e-2, which 1 - 1e-6 does not cover)
+    const real lim = (real)(sizeof(real) == 4 ? 0.99 : 0.999999)*vld*vld;
     bool moved = false;
     for (int g = lane; g < M.ngeom; g += FB_WAVE) {
       const real dx = G[4*g] - w.vl_pos()[3*g], dy = G[4*g + 1] - w.vl_pos()[3*g + 1], dz = G[4*g + 2] - w.vl_pos()[3*g + 2];

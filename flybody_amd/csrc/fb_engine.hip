@@ -624,6 +624,8 @@ static int build_devmodel(fb_batch* b, const fb_model* m, DevModel<real>& M) {
     for (int g = 0; g < m->ngeom; g++) if (r_[g] > 0) rb.push_back(r_[g]);
     std::sort(rb.begin(), rb.end());
     M.vl_delta = (rb.empty() || m->npair <= 4*FB_WAVE) ? (real)0 : (real)(FB_VL_SCALE*rb[rb.size()/2]);
+    // the list's validity test watches the geom centres only: a plane on a moving body could turn its normal without moving its centre -- no list then
+    { const int* gt_ = m->i("geom_type"); const int* gb_ = m->i("geom_bodyid"); for (int g = 0; g < m->ngeom; g++) if (gt_[g] == GEOM_PLANE && gb_[g] != 0) M.vl_delta = 0; }
     { const char* e_ = getenv("FB_NO_NEIGHBOUR_LIST"); if (e_ && e_[0] == '1') M.vl_delta = 0; }      // (read at model load: the tests compare the two paths bit for bit)
   }
   M.ar_entry_lanes = 1;
