@@ -28,6 +28,7 @@ extern "C" { long long fb_stats[64]; }
 #include "fb_inverse.hpp"
 #include "fb_deriv.hpp"
 #include "fb_rollout.hpp"
+#include "fb_riccati.hpp"
 #include "fb_host.hpp"                    // g_err / fail / HIPCHK, DevBuf, DevEvent
 #include "fb_model.hpp"                   // fb_model and the C-ABI's model entry points
 
@@ -530,6 +531,8 @@ struct fb_batch {
   std::vector<int> roll_env_host;
   // fb_batch_rollout_feedback: the rows k_closedloop_rollout keeps resident, and the rollouts' nominals behind their environments in roll_env
   int roll_fb_slots = 0;
+  // fb_batch_lqr_backward (fb_riccati.hpp): the products' workspace of all nominals, grown as needed
+  DevBuf<double> lqr_ws;
 };
 
 template <typename real, typename T, typename P>
@@ -1432,6 +1435,134 @@ extern "C" int fb_batch_rollout_feedback(fb_batch* b, const fb_rollout_config* c
 extern "C" int fb_batch_rollouts_run(fb_batch* b, int64_t* n) {
   if (!b || !n) return fail("fb_batch_rollouts_run: null argument");
   return side_tickets_done(b, b->roll_counter, n);
+}
+
+// ------------------------------------------------------------------ LQR / iLQR backward pass
+// fb_riccati.hpp: the horizon loop runs here and enqueues the interval's products, its gain kernel and the symmetrisation on the caller's
+// stream.  The batch gives the device and owns the workspace; no environment is read.  Steady state (the shapes of the call before): no
+// allocation, no upload, no synchronisation.
+static void ric_gemm(hipStream_t st, int n_nom, int M, int N, int K, const double* X, long long sX, long long xi, long long xk,
+                     const double* Y, long long sY, long long yk, long long yj, const double* D, long long sD, int ldd, double* C, long long sC,
+                     const int* status) {
+  RicGemm g;
+  g.X = X; g.Y = Y; g.D = D; g.C = C; g.sX = sX; g.sY = sY; g.sD = sD; g.sC = sC; g.xi = xi; g.xk = xk; g.yk = yk; g.yj = yj;
+  g.M = M; g.N = N; g.K = K; g.ldd = ldd; g.ldc = N; g.tm = (M + FB_RIC_TILE - 1)/FB_RIC_TILE; g.tn = (N + FB_RIC_TILE - 1)/FB_RIC_TILE; g.status = status;
+  hipLaunchKernelGGL(k_riccati_gemm, dim3((unsigned)((size_t)n_nom*g.tm*g.tn)), dim3(64), 0, st, g);
+}
+
+// doubles of workspace per nominal (the header states the layout)
+static size_t lqr_ws_per_nominal(int ndx, int nu) { return 3*(size_t)ndx*ndx + 3*(size_t)ndx*nu + (size_t)nu*nu + 2*(size_t)ndx; }
+
+extern "C" int fb_batch_lqr_backward(fb_batch* b, const fb_lqr_config* cfg, const double* A, const double* B, const double* Q, const double* R,
+                                     const double* Qf, const double* q, const double* r, const double* mu, double* Kt, double* k, double* P,
+                                     double* p, double* dV, int32_t* status, void* stream) {
+  const std::string fn = "fb_batch_lqr_backward";
+  if (!b) return fail(fn + ": null batch");
+  if (!cfg) return fail(fn + ": null config");
+  if (!A) return fail(fn + ": A is NULL");
+  if (!B) return fail(fn + ": B is NULL");
+  if (!Q) return fail(fn + ": Q is NULL");
+  if (!R) return fail(fn + ": R is NULL");
+  if (!Kt) return fail(fn + ": the Kt output is NULL");
+  if (!status) return fail(fn + ": the status output is NULL");
+  if (cfg->n_nom < 1) return fail(fn + ": n_nom must be >= 1");
+  if (cfg->horizon < 1) return fail(fn + ": horizon must be >= 1");
+  if (cfg->ndx < 1) return fail(fn + ": ndx must be >= 1");
+  if (cfg->nu < 1) return fail(fn + ": nu must be >= 1");
+  if (cfg->ndx > FB_RIC_NDXMAX) return fail(fn + ": ndx " + std::to_string(cfg->ndx) + " exceeds the gain kernel's " + std::to_string(FB_RIC_NDXMAX) + " Qx registers per workgroup");
+  if (cfg->nu > FB_RIC_NUMAX) return fail(fn + ": nu " + std::to_string(cfg->nu) + " exceeds the " + std::to_string(FB_RIC_NUMAX) + " rows of the Cholesky factor in LDS and of a lane's right-hand side");
+  if (cfg->stationary != 0 && cfg->stationary != 1) return fail(fn + ": stationary must be 0 or 1");
+  const int n = cfg->n_nom, T = cfg->horizon, ndx = cfg->ndx, nu = cfg->nu; const bool stat = cfg->stationary == 1;
+  const size_t nn = (size_t)ndx*ndx, nm = (size_t)ndx*nu;
+  if ((size_t)n*((nn + 32*32 - 1)/(32*32) + 1) > (size_t)INT_MAX/4 || (size_t)n*(T + 1)*nn > ((size_t)1 << 46))
+    return fail(fn + ": n_nom " + std::to_string(n) + " x horizon x ndx^2 exceeds the kernels' grids");
+  FB_GUARD_BEGIN
+  HIPCHK(hipSetDevice(b->device));
+  hipStream_t st = (hipStream_t)stream;
+  const size_t need = (size_t)n*lqr_ws_per_nominal(ndx, nu);
+  if (b->lqr_ws.count() < need) {
+    HIPCHK(hipDeviceSynchronize());                    // (an earlier call may still use the block)
+    if (b->lqr_ws.reserve(need)) return -1;
+  }
+  // the workspace, one array [n_nom][..] after the other: three ndx x ndx buffers whose roles rotate (P_{t+1}, W then P_t, S), Y, Qux, G, Quu, p x 2
+  double* w = b->lqr_ws.get();
+  double* big[3]; for (int i = 0; i < 3; i++) { big[i] = w; w += (size_t)n*nn; }
+  double* Yb = w; w += (size_t)n*nm; double* Qux = w; w += (size_t)n*nm; double* G = w; w += (size_t)n*nm;
+  double* Quu = w; w += (size_t)n*nu*nu; double* pv[2]; pv[0] = w; w += (size_t)n*ndx; pv[1] = w;
+  const int Tout = stat ? 1 : T, TP = stat ? 2 : T + 1;
+  // outputs start from zero: a failed nominal's intervals are never written
+  HIPCHK(hipMemsetAsync(Kt, 0, (size_t)n*Tout*nm*sizeof(double), st));
+  if (k) HIPCHK(hipMemsetAsync(k, 0, (size_t)n*Tout*nu*sizeof(double), st));
+  if (P) HIPCHK(hipMemsetAsync(P, 0, (size_t)n*TP*nn*sizeof(double), st));
+  if (p) HIPCHK(hipMemsetAsync(p, 0, (size_t)n*TP*ndx*sizeof(double), st));
+  // where P_j and p_j live: in the output when it has a slot for them, else in the workspace
+  auto P_out = [&](int j, long long* s) -> double* { if (!P || (stat && j > 1)) return nullptr; *s = (long long)TP*nn; return P + (size_t)j*nn; };
+  auto p_slot = [&](int j, long long* s) -> double* { if (!p || (stat && j > 1)) return nullptr; *s = (long long)TP*ndx; return p + (size_t)j*ndx; };
+  const int chunks = (int)std::min<size_t>(64, (nn + FB_RIC_THREADS - 1)/FB_RIC_THREADS);
+  const int* stat_ro = (const int*)status;
+  long long sPn = (long long)nn, spn = ndx; int cur = 0, pcur = 0;          // P_{t+1}: big[cur] unless in the output; p_{t+1} likewise
+  double* Pn = P_out(T, &sPn); if (Pn) cur = -1; else Pn = big[0];
+  double* pn = p_slot(T, &spn); if (pn) pcur = -1; else pn = pv[0];
+  const long long qT = stat ? 1 : T;                                         // q: [n_nom][T + 1][ndx]; stationary: [n_nom][2][ndx] (running, terminal)
+  {
+    RicInit g;
+    g.Qf = Qf ? Qf : Q; g.P = Pn; g.sP = sPn; g.qT = q ? q + (size_t)qT*ndx : nullptr; g.sqT = (qT + 1)*ndx; g.p = pn; g.sp = spn;
+    g.dV = dV; g.status = (int*)status; g.ndx = ndx; g.chunks = chunks;
+    hipLaunchKernelGGL(k_riccati_init, dim3((unsigned)(n*chunks)), dim3(FB_RIC_THREADS), 0, st, g);
+  }
+  const long long sA = (long long)(stat ? 1 : T)*nn, sB = (long long)(stat ? 1 : T)*nm, sN = (long long)nn, sM = (long long)nm;
+  for (int t = T - 1; t >= 0; t--) {
+    const int to = stat ? 0 : t;
+    const double* At = A + (size_t)to*nn; const double* Bt = B + (size_t)to*nm;
+    const int iw = cur == 0 ? 1 : 0; int is = 0;                       // two workspace buffers that do not hold P_{t+1}
+    while (is == cur || is == iw) is++;
+    double* W = big[iw]; double* S = big[is];
+    double* Ktt = Kt + (size_t)to*nm; const long long sK = (long long)Tout*nm;
+    ric_gemm(st, n, ndx, ndx, ndx, Pn, sPn, ndx, 1, At, sA, ndx, 1, nullptr, 0, 0, W, sN, stat_ro);              // W = P A
+    ric_gemm(st, n, ndx, nu, ndx, Pn, sPn, ndx, 1, Bt, sB, nu, 1, nullptr, 0, 0, Yb, sM, stat_ro);               // Y = P B
+    ric_gemm(st, n, ndx, ndx, ndx, At, sA, 1, ndx, W, sN, ndx, 1, Q, 0, ndx, S, sN, stat_ro);                    // S = Q + A'W   (Qxx)
+    ric_gemm(st, n, nu, ndx, ndx, Bt, sB, 1, nu, W, sN, ndx, 1, nullptr, 0, 0, Qux, sM, stat_ro);                // Qux = B'W
+    ric_gemm(st, n, nu, nu, ndx, Bt, sB, 1, nu, Yb, sM, nu, 1, R, 0, nu, Quu, (long long)nu*nu, stat_ro);        // Quu = R + B'Y
+    long long spo = ndx; double* po = p_slot(t, &spo); int pnext = -1;
+    if (!po) { pnext = pcur == 0 ? 1 : 0; po = pv[pnext]; }
+    {
+      RicGain g;
+      g.A = At; g.B = Bt; g.sA = sA; g.sB = sB; g.Qux = Qux; g.Quu = Quu; g.sQux = sM; g.sQuu = (long long)nu*nu;
+      g.q = q ? q + (size_t)to*ndx : nullptr; g.sq = (qT + 1)*ndx; g.r = r ? r + (size_t)to*nu : nullptr; g.sr = (long long)Tout*nu; g.mu = mu;
+      g.p_next = pn; g.sp_next = spn; g.p_out = po; g.sp_out = spo; g.Kt = Ktt; g.sKt = sK; g.k = k ? k + (size_t)to*nu : nullptr; g.sk = (long long)Tout*nu;
+      g.dV = dV; g.status = (int*)status; g.ndx = ndx; g.nu = nu; g.t = t;
+      hipLaunchKernelGGL(k_riccati_gain, dim3((unsigned)n), dim3(FB_RIC_THREADS), 0, st, g);
+    }
+    if (mu) {                                                                                                     // the general form (header)
+      ric_gemm(st, n, nu, ndx, nu, Quu, (long long)nu*nu, nu, 1, Ktt, sK, 1, nu, Qux, sM, ndx, G, sM, stat_ro);   // G = Qux + Quu K
+      ric_gemm(st, n, ndx, ndx, nu, Ktt, sK, nu, 1, G, sM, ndx, 1, S, sN, ndx, S, sN, stat_ro);                   // S += K'G
+    }
+    ric_gemm(st, n, ndx, ndx, nu, Qux, sM, 1, ndx, Ktt, sK, 1, nu, S, sN, ndx, S, sN, stat_ro);                   // S += Qux'K
+    long long sPo = sN; double* Po = P_out(t, &sPo); int next = -1;
+    if (!Po) { next = iw; Po = W; }                                                                              // (W is dead behind Qux)
+    {
+      RicSym g; g.S = S; g.sS = sN; g.P = Po; g.sP = sPo; g.status = stat_ro; g.ndx = ndx; g.chunks = chunks;
+      hipLaunchKernelGGL(k_riccati_sym, dim3((unsigned)(n*chunks)), dim3(FB_RIC_THREADS), 0, st, g);
+    }
+    Pn = Po; sPn = sPo; cur = next; pn = po; spn = spo; pcur = pnext;
+  }
+  HIPCHK(hipGetLastError());
+  return 0;
+  FB_GUARD_END
+}
+
+// The product kernel of fb_batch_lqr_backward alone, for the tests of its tile map and edges: C = op(X) op(Y) (+ D), one matrix each.
+extern "C" int fb_riccati_gemm(fb_batch* b, int m, int n, int k, int trans_x, int trans_y, const double* X, const double* Y, const double* D,
+                               double* C, void* stream) {
+  if (!b) return fail("fb_riccati_gemm: null batch");
+  if (!X || !Y || !C) return fail("fb_riccati_gemm: X, Y or C is NULL");
+  if (m < 1 || n < 1 || k < 1 || m > 4096 || n > 4096 || k > 4096) return fail("fb_riccati_gemm: m, n and k must be 1 .. 4096");
+  FB_GUARD_BEGIN
+  HIPCHK(hipSetDevice(b->device));
+  ric_gemm((hipStream_t)stream, 1, m, n, k, X, 0, trans_x ? 1 : k, trans_x ? m : 1, Y, 0, trans_y ? 1 : n, trans_y ? k : 1, D, 0, n, C, 0, nullptr);
+  HIPCHK(hipGetLastError());
+  return 0;
+  FB_GUARD_END
 }
 
 // ------------------------------------------------------------------ field access

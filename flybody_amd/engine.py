@@ -78,6 +78,12 @@ Rollout = collections.namedtuple('Rollout', ['state', 'qpos', 'qvel', 'act', 'se
 # Batch.rollout_feedback as one value, for BatchedFlyEnv.rollout(feedback=...) and rollout.rollout(feedback=...)
 Feedback = collections.namedtuple('Feedback', ['x_nom', 'u_nom', 'K', 'k', 'alpha', 'nom_ids'], defaults=(None, None, None, None))
 
+# Batch.lqr_backward: the gains K [n_nom, T, nu, ndx] (a transposed view of the Kt the kernel wrote: K.transpose(2, 3) is contiguous and is
+# what Batch.rollout_feedback streams, without a copy), k [n_nom, T, nu], the value's P [n_nom, T + 1, ndx, ndx] and p [n_nom, T + 1, ndx]
+# (None: not asked for), the predicted change of the cost dV [n_nom, 2] and status [n_nom] (0, or 1 + the interval whose Quu + mu I was
+# not positive definite); in stationary mode the time axes are 1 (K, k) and 2 (P, p)
+LQRBackward = collections.namedtuple('LQRBackward', ['K', 'k', 'P', 'p', 'dV', 'status'])
+
 _libs: Dict[str, C.CDLL] = {}
 
 
@@ -153,6 +159,9 @@ def load_library(lib_path: Optional[str] = None) -> C.CDLL:
         L.fb_batch_rollouts_run.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
     if hasattr(L, 'fb_batch_rollout_feedback'):
         L.fb_batch_rollout_feedback.argtypes = [C.c_void_p] + [C.c_void_p]*7
+    if hasattr(L, 'fb_batch_lqr_backward'):
+        L.fb_batch_lqr_backward.argtypes = [C.c_void_p]*17
+        L.fb_riccati_gemm.argtypes = [C.c_void_p] + [C.c_int]*5 + [C.c_void_p]*5
     _libs[path] = L
     return L
 
@@ -223,6 +232,11 @@ class _Feedback(C.Structure):
     """fb_feedback (include/flybody_engine.h)."""
     _fields_ = [('n_nom', C.c_int32), ('nom_ids', C.c_void_p), ('x_nom', C.c_void_p), ('u_nom', C.c_void_p), ('K', C.c_void_p), ('k', C.c_void_p),
                 ('alpha', C.c_void_p)]
+
+
+class _LQRConfig(C.Structure):
+    """fb_lqr_config (include/flybody_engine.h)."""
+    _fields_ = [('n_nom', C.c_int32), ('horizon', C.c_int32), ('ndx', C.c_int32), ('nu', C.c_int32), ('stationary', C.c_int32)]
 
 
 class Model:
@@ -496,7 +510,10 @@ class Batch:
         n_nom, T = int(x_nom.shape[0]), int(x_nom.shape[1])
         chk(u_nom, 'u_nom', nu)
         if K is not None:
-            chk(K, 'K', nu, ndx)
+            if isinstance(K, torch.Tensor) and K.dim() == 4 and not K.is_contiguous() and K.transpose(2, 3).is_contiguous():
+                chk(K.transpose(2, 3), 'K (behind transpose(2, 3))', ndx, nu)     # lqr_backward's view of the array the kernel streams: no copy below
+            else:
+                chk(K, 'K', nu, ndx)
         if k is not None:
             chk(k, 'k', nu)
         for x, what in ((u_nom, 'u_nom'), (K, 'K'), (k, 'k')):
@@ -529,6 +546,94 @@ class Batch:
         cp = lambda t: None if t is None else C.c_void_p(t.data_ptr())
         _check(self.L, self.L.fb_batch_rollout_feedback(self.h, C.byref(cfg), C.byref(fbk), cp(state), cp(sens), cp(ctrl), cp(status), stream))
         return Rollout(state, state[..., :nq], state[..., nq:nq + nv], state[..., nq + nv:], sens, status[:n], ctrl)
+
+    def _torch_device(self):
+        """(torch.device of this batch's arrays, emulated): the emulation build computes on CPU tensors."""
+        import torch
+        emulated = b'emulation' in self.L.fb_version()
+        return (torch.device('cpu') if emulated else torch.device('cuda', self.device)), emulated
+
+    def lqr_backward(self, A, B, Q, R, Qf=None, q=None, r=None, mu=None, stationary: bool = False, horizon: Optional[int] = None,
+                     want_P: bool = False, stream=None) -> 'LQRBackward':
+        """The backward pass of LQR / iLQR for n_nom independent nominals on the device (fb_batch_lqr_backward; the formulas and the
+        conventions of lqr.backward_pass).  Contiguous float64 torch tensors on the batch's device: A [n_nom, T, ndx, ndx],
+        B [n_nom, T, ndx, nu] (what transition_fd returns, stacked), Q / Qf [ndx, ndx] (Qf None: Q), R [nu, nu]; optional q [n_nom, T + 1, ndx],
+        r [n_nom, T, nu] (the cost's gradient along the nominal: iLQR) and mu [n_nom] (the regularisation of Quu).  stationary=True:
+        A [n_nom, ndx, ndx], B [n_nom, ndx, nu], the recursion runs `horizon` times (required then) and only t = 0 is kept -- time axes
+        1 (K, k) and 2 (P, p: P_0 and P_1), q [n_nom, 2, ndx] (running, terminal), r [n_nom, 1, nu].  ndx and nu are the arrays' own: the
+        batch gives the device and the workspace only.  want_P: also return P and p.  Returns LQRBackward(K, k, P, p, dV, status);
+        K [n_nom, T, nu, ndx] is a view whose transpose(2, 3) is contiguous -- the layout rollout_feedback streams, so the hand-over
+        copies nothing.  A nominal whose Quu + mu I is not positive definite at interval t has status 1 + t and zero outputs from t
+        down.  Asynchronous on `stream` (None: torch's current stream)."""
+        import torch
+        dev, emulated = self._torch_device()
+
+        def chk(x, what, shape, names):
+            if not isinstance(x, torch.Tensor) or x.dtype != torch.float64 or not x.is_contiguous() or x.device != dev \
+                    or (shape is not None and tuple(x.shape) != tuple(shape)):
+                raise ValueError(f'{what} must be a contiguous torch.float64 tensor [{names}] on {dev}')
+        chk(A, 'A', None, 'n_nom, ndx, ndx' if stationary else 'n_nom, T, ndx, ndx')
+        if A.dim() != (3 if stationary else 4) or A.shape[-1] != A.shape[-2] or min(A.shape) < 1:
+            raise ValueError('A must be [n_nom, ndx, ndx] (stationary) or [n_nom, T, ndx, ndx]')
+        n_nom, ndx = int(A.shape[0]), int(A.shape[-1])
+        if stationary:
+            if horizon is None or int(horizon) < 1:
+                raise ValueError('stationary mode needs horizon >= 1: the number of Riccati steps')
+            T, lead, Tout, TP = int(horizon), (n_nom,), 1, 2
+        else:
+            T = int(A.shape[1])
+            if horizon is not None and int(horizon) != T:
+                raise ValueError(f'horizon {horizon} is not the time axis of A ({T})')
+            lead, Tout, TP = (n_nom, T), T, T + 1
+        chk(B, 'B', None, 'n_nom, ndx, nu' if stationary else 'n_nom, T, ndx, nu')
+        if B.dim() != A.dim() or tuple(B.shape[:-1]) != lead + (ndx,) or B.shape[-1] < 1:
+            raise ValueError(f'B must be [{", ".join(map(str, lead + (ndx,)))}, nu]')
+        nu = int(B.shape[-1])
+        chk(Q, 'Q', (ndx, ndx), 'ndx, ndx'); chk(R, 'R', (nu, nu), 'nu, nu')
+        if Qf is not None:
+            chk(Qf, 'Qf', (ndx, ndx), 'ndx, ndx')
+        if q is not None:
+            chk(q, 'q', (n_nom, TP, ndx), 'n_nom, T + 1 (stationary: 2), ndx')
+        if r is not None:
+            chk(r, 'r', (n_nom, Tout, nu), 'n_nom, T (stationary: 1), nu')
+        if mu is not None:
+            chk(mu, 'mu', (n_nom,), 'n_nom')
+        if stream is None and not emulated:
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+
+        def outputs():
+            e = lambda *shape, dtype=torch.float64: torch.empty(shape, dtype=dtype, device=dev)        # (the call zeroes what it needs zero)
+            return (e(n_nom, Tout, ndx, nu), e(n_nom, Tout, nu), e(n_nom, TP, ndx, ndx) if want_P else None, e(n_nom, TP, ndx) if want_P else None,
+                    e(n_nom, 2), e(n_nom, dtype=torch.int32))
+        if emulated or stream == torch.cuda.current_stream(self.device).cuda_stream:
+            Kt, k, P, p, dV, status = outputs()
+        else:                                                                    # (allocated on that stream: freed in its order)
+            with torch.cuda.stream(torch.cuda.ExternalStream(stream, device=dev)):
+                Kt, k, P, p, dV, status = outputs()
+        cfg = _LQRConfig(n_nom, T, ndx, nu, 1 if stationary else 0)
+        cp = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        _check(self.L, self.L.fb_batch_lqr_backward(self.h, C.byref(cfg), cp(A), cp(B), cp(Q), cp(R), cp(Qf), cp(q), cp(r), cp(mu),
+                                                    cp(Kt), cp(k), cp(P), cp(p), cp(dV), cp(status), stream))
+        return LQRBackward(Kt.transpose(2, 3), k, P, p, dV, status)
+
+    def riccati_gemm(self, X, Y, D=None, trans_x: bool = False, trans_y: bool = False, stream=None):
+        """C = op(X) op(Y) (+ D) through the product kernel of lqr_backward alone (fb_riccati_gemm; a test entry): contiguous float64
+        2-D torch tensors on the batch's device."""
+        import torch
+        dev, emulated = self._torch_device()
+        for x, what in ((X, 'X'), (Y, 'Y')) + (((D, 'D'),) if D is not None else ()):
+            if not isinstance(x, torch.Tensor) or x.dtype != torch.float64 or x.dim() != 2 or not x.is_contiguous() or x.device != dev:
+                raise ValueError(f'{what} must be a contiguous 2-D torch.float64 tensor on {dev}')
+        m, k = (X.shape[1], X.shape[0]) if trans_x else X.shape
+        k2, n = (Y.shape[1], Y.shape[0]) if trans_y else Y.shape
+        if k != k2 or (D is not None and tuple(D.shape) != (m, n)):
+            raise ValueError(f'op(X) is {m} x {k}, op(Y) {k2} x {n}: the inner sizes must agree and D be [{m}, {n}]')
+        if stream is None and not emulated:
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+        Cm = torch.empty((m, n), dtype=torch.float64, device=dev)
+        _check(self.L, self.L.fb_riccati_gemm(self.h, int(m), int(n), int(k), int(trans_x), int(trans_y), C.c_void_p(X.data_ptr()),
+                                              C.c_void_p(Y.data_ptr()), None if D is None else C.c_void_p(D.data_ptr()), C.c_void_p(Cm.data_ptr()), stream))
+        return Cm
 
     def rollouts_run(self) -> int:
         """Rollouts the last rollout / rollout_feedback call finished (fb_batch_rollouts_run; synchronises the device)."""

@@ -374,6 +374,21 @@ class BatchedFlyEnv:
         control law."""
         return self.batch.transition_fd(env_ids=env_ids, **kw)
 
+    def lqr_gains(self, lin, Q, R, horizon, mu=None):
+        """Stationary LQR gains around the linearisations `lin` = env.linearize(ids, ...), one model per listed environment, without
+        leaving the device (Batch.lqr_backward in stationary mode: `horizon` Riccati steps from the terminal weight Q).  Q [ndx, ndx],
+        R [nu, nu] (numpy or torch), mu [n] (None: no regularisation).  Returns engine.LQRBackward with P = (P_0, P_1) -- their
+        difference tells convergence -- and K [n, 1, nu, ndx]: K.expand(-1, T, -1, -1).contiguous() is the gain of
+        env.rollout(feedback=engine.Feedback(x_nom, u_nom, K)) over T intervals of the substeps `lin` was taken over."""
+        import torch
+        if lin.A is None or lin.B is None:
+            raise ValueError('lqr_gains needs both A and B of the linearisation')
+        dev = lin.A.device
+        on = lambda x: None if x is None else torch.as_tensor(np.asarray(x, np.float64) if not isinstance(x, torch.Tensor) else x, dtype=torch.float64,
+                                                              device=dev).contiguous()
+        return self.batch.lqr_backward(lin.A.contiguous(), lin.B.contiguous(), on(Q), on(R), mu=on(mu), stationary=True, horizon=int(horizon),
+                                       want_P=True)
+
     # ---- open-loop rollouts (flybody_amd.rollout, csrc/fb_rollout.hpp) ---------------------------
     def rollout(self, action=None, ctrl=None, env_ids=None, feedback=None, samples=None, **kw):
         """What happens if these inputs are applied from here?  Open-loop rollouts from live environments between two control steps,

@@ -384,6 +384,57 @@ typedef struct fb_feedback {
 int fb_batch_rollout_feedback(fb_batch* b, const fb_rollout_config* cfg, const fb_feedback* fbk,
                               double* state, double* sensordata, double* ctrl_out, int32_t* status, void* stream);
 
+/* The backward pass of LQR / iLQR for n_nom independent nominals, on the device: from the transition derivatives of
+ * fb_batch_transition_fd to the gains fb_batch_rollout_feedback streams, without a trip to the host.  Conventions: no 1/2 in the cost,
+ * u = u_nom + K dx, linear model dx_{t+1} = A_t dx_t + B_t du_t.  For the cost
+ *     J = sum_t ( dx'Q dx + du'R du + 2 q_t'dx + 2 r_t'du ) + dx_T'Qf dx_T + 2 q_T'dx_T
+ * and the value V_t = dx'P_t dx + 2 p_t'dx + const, from P_T = Qf, p_T = q_T and for t = T-1 .. 0:
+ *     W   = P_{t+1} A_t                 Y   = P_{t+1} B_t
+ *     Qxx = Q + A_t'W                   Qux = B_t'W               Quu = R + B_t'Y
+ *     Qx  = q_t + A_t'p_{t+1}           Qu  = r_t + B_t'p_{t+1}
+ *     Quu_reg = Quu + mu[m] I           (Cholesky)
+ *     K_t = -Quu_reg^-1 Qux             k_t = -Quu_reg^-1 Qu
+ *     P_t = sym( Qxx + K'Quu K + K'Qux + Qux'K )          -- the general form: runs when mu is given (whatever its values)
+ *     P_t = sym( Qxx + Qux'K )                            -- the short form, equal to it when Quu_reg = Quu: runs when mu is NULL
+ *     p_t = Qx + K'(Quu k + Qu) + Qux'k                   -- always this form
+ *     dV[m] += ( 2 k'Qu , k'Quu k )     (the predicted change of J for step length alpha is alpha dV[0] + alpha^2 dV[1])
+ * With mu, q and r NULL this is the time-varying LQR recursion, K = -(R + B'PB)^-1 B'PA.
+ * LAYOUT (all arrays DEVICE, contiguous doubles, row-major matrices):
+ *     A  [n_nom][horizon][ndx][ndx]   B  [n_nom][horizon][ndx][nu]   Q, Qf [ndx][ndx]   R [nu][nu]   (one each for the call; Qf NULL: Q)
+ *     q  [n_nom][horizon+1][ndx]      r  [n_nom][horizon][nu]        mu [n_nom]         (optional: NULL is zero)
+ *     Kt [n_nom][horizon][ndx][nu]    -- K_t TRANSPOSED, the layout fb_feedback.K takes: the two calls hand over without a copy
+ *     k  [n_nom][horizon][nu]         P  [n_nom][horizon+1][ndx][ndx]   p [n_nom][horizon+1][ndx]   dV [n_nom][2]   status [n_nom]
+ * STATIONARY MODE (stationary = 1), the batched fixed-point iteration of infinite-horizon LQR: A [n_nom][ndx][ndx] and B [n_nom][ndx][nu]
+ * serve every t, the recursion runs `horizon` times and only the outputs of t = 0 are kept: Kt [n_nom][1][ndx][nu], k [n_nom][1][nu],
+ * P [n_nom][2][ndx][ndx] = (P_0, P_1) -- max |P_0 - P_1| tells convergence --, p [n_nom][2][ndx] likewise; q is [n_nom][2][ndx] (the
+ * running q, then q_T) and r [n_nom][1][nu].
+ * FAILURE IS DATA: when a pivot of the Cholesky of Quu_reg is <= 0 or not finite, nothing faults and no NaN is written: status[m] = 1 + t
+ * of the first such interval, that nominal's Kt, k, P, p are zero for all intervals <= t and dV[m] = 0; every other nominal is unaffected.
+ * status[m] = 0 otherwise.
+ * The batch supplies the device, the stream convention and ownership of the workspace only: the call reads no environment and works on
+ * any batch (FP32, grouped, with forces or a control law).  ndx and nu are the caller's.  WORKSPACE, a block of the batch that grows on
+ * demand (ordered on the device when it does) and is freed with it: 3 ndx^2 + 3 ndx nu + nu^2 + 2 ndx doubles per nominal -- three
+ * ndx x ndx buffers whose roles rotate (P_{t+1}; W, then P_t; the sum under sym), Y, Qux, Quu K + Qux, Quu, p twice: 2.2 MB for the
+ * walking fly (ndx 275, nu 59).  The Cholesky factor lives in LDS.
+ * Refused, with the reason in fb_last_error(): null batch, cfg, A, B, Q, R, Kt or status; n_nom, horizon, ndx or nu < 1; ndx > 1024;
+ * nu > 64 (the factor's rows in LDS and a lane's right-hand side in registers); stationary not 0 or 1.
+ * Asynchronous on `stream` after validation; with the shapes of the call before: no allocation, no upload, no synchronisation.  Sums run
+ * in a fixed order: two calls give the same bits, and a nominal's bits do not depend on the others in the call. */
+typedef struct fb_lqr_config {
+  int32_t n_nom, horizon, ndx, nu;   /* ndx, nu are the caller's: the call does not read the model */
+  int32_t stationary;                /* 0 / 1 (above) */
+} fb_lqr_config;
+int fb_batch_lqr_backward(fb_batch* b, const fb_lqr_config* cfg,
+                          const double* A, const double* B,
+                          const double* Q, const double* R, const double* Qf,
+                          const double* q, const double* r, const double* mu,
+                          double* Kt, double* k, double* P, double* p,
+                          double* dV, int32_t* status, void* stream);
+/* The product kernel of the call above on its own, for tests of its tile map and edges: C [m][n] = op(X) op(Y) (+ D [m][n]; NULL: none),
+ * X stored [m][k] (trans_x: [k][m]), Y stored [k][n] (trans_y: [n][k]); all DEVICE, row-major doubles; m, n, k in 1 .. 4096. */
+int fb_riccati_gemm(fb_batch* b, int m, int n, int k, int trans_x, int trans_y,
+                    const double* X, const double* Y, const double* D, double* C, void* stream);
+
 /* External forces (FB_QFRC_APPLIED, FB_XFRC_APPLIED), MuJoCo's two user inputs for everything that is not an actuator, a contact or the
  * fluid model.  Every substep
  *     qfrc_smooth = qfrc_passive - qfrc_bias + qfrc_actuator + qfrc_applied + sum_b J_b(xipos_b)' xfrc_applied_b
