@@ -16,19 +16,7 @@ import numpy as np
 
 from . import engine
 from .engine import TransitionFD
-
-_JNT_FREE, _JNT_BALL = 0, 1
-
-
-def _model(model):
-    return engine.Model.from_asset(model) if isinstance(model, str) else model
-
-
-def _quat_mul(a, b):
-    w1, x1, y1, z1 = np.moveaxis(a, -1, 0)
-    w2, x2, y2, z2 = np.moveaxis(b, -1, 0)
-    return np.stack([w1*w2 - x1*x2 - y1*y2 - z1*z2, w1*x2 + x1*w2 + y1*z2 - z1*y2,
-                     w1*y2 - x1*z2 + y1*w2 + z1*x2, w1*z2 + x1*y2 - y1*x2 + z1*w2], axis=-1)
+from .inverse_dynamics import _JNT_BALL, _JNT_FREE, _quat_mul
 
 
 def _quat_integrate(q, w):
@@ -45,7 +33,7 @@ def integrate_pos(model: Union['engine.Model', str], qpos: np.ndarray, dq: np.nd
     ``inverse_dynamics.differentiate_pos`` (``differentiate_pos(m, q, integrate_pos(m, q, dq), 1) == dq`` for rotations below half a
     turn).  Free joint: translation added, rotation q exp(dq_rot / 2) with dq_rot in the body frame; ball joint: the rotation;
     hinge and slide joints: sums.  qpos (nq,) or (n, nq) with dq (nv,) or (n, nv); returns a new array."""
-    a = _model(model).arrays
+    a = engine.as_model(model).arrays
     q = np.array(qpos, np.float64); d = np.asarray(dq, np.float64)
     if q.shape[-1] != len(a['qpos0']) or d.shape[-1] != len(a['dof_bodyid']) or q.shape[:-1] != d.shape[:-1]:
         raise ValueError(f'qpos must be (..., {len(a["qpos0"])}) and dq (..., {len(a["dof_bodyid"])}) with equal leading shape, got {q.shape} and {d.shape}')
@@ -65,7 +53,7 @@ def tangent_names(model: Union['engine.Model', str]) -> List[str]:
     """Labels of the ndx = 2 nv + na tangent entries (rows and columns of A, rows of B, columns of C) followed by the nu controls (columns
     of B and D): 'dq:<joint>' (free joint: ':tx', ':ty', ':tz', ':rx', ':ry', ':rz'; ball joint: ':rx' ..), 'dv:<joint>...',
     'act:<actuator>' for the actuators that have an activation, 'ctrl:<actuator>'."""
-    a = _model(model).arrays
+    a = engine.as_model(model).arrays
     dof = [''] * len(a['dof_bodyid'])
     for j, t in enumerate(a['jnt_type']):
         name, d = str(a['names_jnt'][j]), int(a['jnt_dofadr'][j])
@@ -95,7 +83,7 @@ def transition_fd(model_or_task_name: Union['engine.Model', str], qpos: np.ndarr
     defines the warm start w of every perturbed constraint solve (its acceleration).  status: the OR of the engine's WARN bits
     (engine.WARN_BITS) over the frame's transitions -- non-zero means a cap or an iteration limit was hit and the frame's matrices are
     not derivatives."""
-    model = _model(model_or_task_name)
+    model = engine.as_model(model_or_task_name)
     nq, nv, na, nu = (model.dim(k) for k in ('nq', 'nv', 'na', 'nu'))
     q = np.asarray(qpos, np.float64); v = np.asarray(qvel, np.float64)
     single = q.ndim == 1
@@ -106,17 +94,11 @@ def transition_fd(model_or_task_name: Union['engine.Model', str], qpos: np.ndarr
     u = np.zeros((nf, nu)) if ctrl is None else np.asarray(ctrl, np.float64).reshape(nf, -1)
     if q.ndim != 2 or q.shape[1] != nq or v.shape != (nf, nv) or a_.shape != (nf, na) or u.shape != (nf, nu):
         raise ValueError(f'qpos must be ({nq},) or (n, {nq}); qvel ({nv},), act ({na},) and ctrl ({nu},) or (n, ...) with the same n')
-    if int(batch_size) < 1:
-        raise ValueError('batch_size must be >= 1')
     ndx = 2*nv + na
     A = np.empty((nf, ndx, ndx)); B = np.empty((nf, ndx, nu)); status = np.empty(nf, np.int32)
     Cs = np.empty((nf, engine.NSENSOR, ndx)) if sensors else None
     Ds = np.empty((nf, engine.NSENSOR, nu)) if sensors else None
-    batch, bn = None, 0
-    for lo in range(0, nf, int(batch_size)):
-        hi = min(nf, lo + int(batch_size))
-        if batch is None or bn != hi - lo:
-            batch, bn = engine.Batch(model, hi - lo, device=device, precision=64), hi - lo
+    for batch, lo, hi in engine.helper_batches(model, nf, batch_size, device):
         batch.set('QPOS', q[lo:hi]); batch.set('QVEL', v[lo:hi]); batch.set('CTRL', u[lo:hi])
         if na:
             batch.set('ACT', a_[lo:hi])

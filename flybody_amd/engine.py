@@ -189,6 +189,86 @@ def _check(L, rc):
         raise EngineError(L.fb_last_error().decode())
 
 
+def _ptr(t):
+    """The address of a tensor's data as the C calls take it (None stays None)."""
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def as_env_ids(env_ids, n_all: Optional[int] = None):
+    """Environment (or nominal) ids as the C calls read them, a contiguous int32 vector; None: all `n_all` of them, or None without it."""
+    if env_ids is None:
+        return None if n_all is None else np.arange(n_all, dtype=np.int32)
+    return np.ascontiguousarray(env_ids, np.int32).reshape(-1)
+
+
+def _check_tensor(x, dtype, device, shape, message):
+    """ValueError(message) unless x is a contiguous torch tensor of `dtype` on `device` whose shape is `shape`: an entry None leaves that
+    axis free (so (None, None, nu) is a trailing shape), shape None leaves all of it to the caller."""
+    import torch
+    if not isinstance(x, torch.Tensor) or x.dtype != dtype or not x.is_contiguous() or x.device != device or (
+            shape is not None and (x.dim() != len(shape) or any(s is not None and s != d for s, d in zip(shape, x.shape)))):
+        raise ValueError(message)
+
+
+def state_views(state, nq: int, nv: int):
+    """(state, qpos, qvel, act): the leading fields of a Rollout, the last three views into state [..., nq + nv + na]."""
+    return state, state[..., :nq], state[..., nq:nq + nv], state[..., nq + nv:]
+
+
+def as_model(name_or_model) -> 'Model':
+    """The array API's model argument: an asset name loads that asset; a Model (or anything with its `.arrays`) is itself."""
+    return Model.from_asset(name_or_model) if isinstance(name_or_model, str) else name_or_model
+
+
+def helper_batches(model: 'Model', n: int, batch_size: int, device: int = 0, rows: Optional[int] = None):
+    """The array API's helper batch: yields (batch, lo, hi) over n frames in chunks [lo, hi) of at most `batch_size`.  A chunk's FP64 batch
+    has `rows` environments (None: one per frame of the chunk); it is reused while that count stays, so only a shorter last chunk makes
+    another."""
+    if int(batch_size) < 1:
+        raise ValueError('batch_size must be >= 1')
+    batch = None
+    for lo in range(0, n, int(batch_size)):
+        hi = min(n, lo + int(batch_size))
+        need = hi - lo if rows is None else rows
+        if batch is None or batch.n_env != need:
+            batch = Batch(model, need, device=device, precision=64)
+        yield batch, lo, hi
+
+
+class _DeviceCall:
+    """The surroundings of one torch-facing device call of a batch (transition_fd, rollout, rollout_feedback, lqr_backward, riccati_gemm):
+    `device`, the torch.device the batch computes on -- the CPU for the kernel-emulation build (`emulated`), whose "device" memory is host
+    memory --; `stream`, the handle the C call gets: the caller's, else torch's current stream of that device (None when emulated); and
+    the call's outputs and temporaries, made in that stream's order: zero-filled before the kernel writes them and freed behind it.  A
+    consumer on another stream orders itself behind the call's stream."""
+
+    def __init__(self, batch: 'Batch', stream=None):
+        import torch
+        self.emulated = b'emulation' in batch.L.fb_version()
+        self.device = torch.device('cpu') if self.emulated else torch.device('cuda', batch.device)
+        current = None if self.emulated else torch.cuda.current_stream(batch.device).cuda_stream
+        self.stream = current if stream is None else stream
+        self._aside = not self.emulated and self.stream != current
+
+    def _ordered(self, make):
+        import torch
+        if not self._aside:
+            return make()
+        with torch.cuda.stream(torch.cuda.ExternalStream(self.stream, device=self.device)):
+            return make()
+
+    def zeros(self, *shape, dtype=None):
+        import torch
+        return self._ordered(lambda: torch.zeros(shape, dtype=dtype or torch.float64, device=self.device))
+
+    def empty(self, *shape, dtype=None):
+        import torch
+        return self._ordered(lambda: torch.empty(shape, dtype=dtype or torch.float64, device=self.device))
+
+    def contiguous(self, t):
+        return self._ordered(t.contiguous)
+
+
 def observation_layout(model: 'Model', future_steps: int, ball: bool = False):
     """({observable: (offset, size, shape)}, width) of the packed observation vector (fb_task.hpp: d_pack_obs writes it).  The buffer is in
     sorted-key order (tasks/task_utils.py:12); walk_on_ball (ball=True) has no reference observables, its ball's velocity instead;
@@ -429,20 +509,16 @@ class Batch:
         current stream of the device, so torch work that follows is ordered behind it).  A library without a GPU behind it (the tests'
         kernel-emulation build) gets CPU tensors: its "device" memory is host memory."""
         import torch
-        ids = np.arange(self.n_env, dtype=np.int32) if env_ids is None else np.ascontiguousarray(env_ids, np.int32).reshape(-1)
+        call = _DeviceCall(self, stream)
+        ids = as_env_ids(env_ids, self.n_env)
         n, nv, na, nu = len(ids), self.model.dim('nv'), self.model.dim('na'), self.model.dim('nu')
         ndx = 2*nv + na
-        emulated = b'emulation' in self.L.fb_version()
-        dev = 'cpu' if emulated else 'cuda:%d' % self.device
-        if stream is None and not emulated:
-            stream = torch.cuda.current_stream(self.device).cuda_stream
-        new = lambda want, *shape: torch.zeros((n,) + shape, dtype=torch.float64, device=dev) if want and n else None
+        new = lambda want, *shape: call.zeros(n, *shape) if want and n else None
         A, B = new(want_A, ndx, ndx), new(want_B, ndx, nu)
         Cs, Ds = new(want_A and sensors, NSENSOR, ndx), new(want_B and sensors, NSENSOR, nu)
-        status = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
+        status = call.zeros(max(n, 1), dtype=torch.int32)
         cfg = _FDConfig(float(eps), int(bool(centered)), int(n_substeps), n, ids.ctypes.data, int(pool_rows))
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-        _check(self.L, self.L.fb_batch_transition_fd(self.h, C.byref(cfg), ptr(A), ptr(B), ptr(Cs), ptr(Ds), ptr(status), stream))
+        _check(self.L, self.L.fb_batch_transition_fd(self.h, C.byref(cfg), _ptr(A), _ptr(B), _ptr(Cs), _ptr(Ds), _ptr(status), call.stream))
         return TransitionFD(A, B, Cs, Ds, status[:n])
 
     def fd_tickets(self) -> int:
@@ -466,24 +542,19 @@ class Batch:
         if (ctrl is None) == (action is None):
             raise ValueError('rollout takes exactly one of ctrl and action')
         x, dt, width, what = (ctrl, torch.float64, self.model.dim('nu'), 'ctrl') if action is None else (action, torch.float32, self.model.dim('nact'), 'action')
-        emulated = b'emulation' in self.L.fb_version()
-        dev = torch.device('cpu') if emulated else torch.device('cuda', self.device)
-        if not isinstance(x, torch.Tensor) or x.dtype != dt or x.dim() != 3 or x.shape[2] != width or not x.is_contiguous() or x.device != dev:
-            raise ValueError(f'{what} must be a contiguous {dt} tensor [n, T, {width}] on {dev}')
+        call = _DeviceCall(self, stream)
+        _check_tensor(x, dt, call.device, (None, None, width), f'{what} must be a contiguous {dt} tensor [n, T, {width}] on {call.device}')
         n, T = int(x.shape[0]), int(x.shape[1])
-        ids = None if env_ids is None else np.ascontiguousarray(env_ids, np.int32).reshape(-1)
+        ids = as_env_ids(env_ids)
         if ids is not None and len(ids) != n:
             raise ValueError(f'env_ids names {len(ids)} environments for {n} rollouts')
-        if stream is None and not emulated:
-            stream = torch.cuda.current_stream(self.device).cuda_stream
         nq, nv, na = self.model.dim('nq'), self.model.dim('nv'), self.model.dim('na')
-        state = torch.zeros((n, T, nq + nv + na), dtype=torch.float64, device=dev)
-        sens = torch.zeros((n, T, NSENSOR), dtype=torch.float64, device=dev) if sensors else None
-        status = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
+        state = call.zeros(n, T, nq + nv + na)
+        sens = call.zeros(n, T, NSENSOR) if sensors else None
+        status = call.zeros(max(n, 1), dtype=torch.int32)
         cfg = _RolloutConfig(n, T, int(n_substeps), None if ids is None else ids.ctypes.data, int(pool_rows))
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-        _check(self.L, self.L.fb_batch_rollout(self.h, C.byref(cfg), ptr(ctrl), ptr(action), ptr(state), ptr(sens), ptr(status), stream))
-        return Rollout(state, state[..., :nq], state[..., nq:nq + nv], state[..., nq + nv:], sens, status[:n])
+        _check(self.L, self.L.fb_batch_rollout(self.h, C.byref(cfg), _ptr(ctrl), _ptr(action), _ptr(state), _ptr(sens), _ptr(status), call.stream))
+        return Rollout(*state_views(state, nq, nv), sens, status[:n])
 
     def rollout_feedback(self, x_nom, u_nom, K=None, k=None, alpha=None, nom_ids=None, env_ids=None, n_substeps: int = 0,
                          sensors: bool = False, pool_rows: int = 0, stream=None) -> 'Rollout':
@@ -497,15 +568,14 @@ class Batch:
         number of rollouts n is that of env_ids, else of nom_ids, else n_nom.  Returns Rollout as rollout() does, with ctrl [n, T, nu]:
         the inputs applied.  Feedback acts on ctrl only, not on a task's actions.  Asynchronous on `stream` like rollout()."""
         import torch
-        emulated = b'emulation' in self.L.fb_version()
-        dev = torch.device('cpu') if emulated else torch.device('cuda', self.device)
+        call = _DeviceCall(self, stream)
+        dev = call.device
         nq, nv, na, nu = (self.model.dim(d) for d in ('nq', 'nv', 'na', 'nu'))
         nx, ndx = nq + nv + na, 2*nv + na
 
         def chk(x, what, *tail):
-            if not isinstance(x, torch.Tensor) or x.dtype != torch.float64 or tuple(x.shape[x.dim() - len(tail):]) != tail or x.dim() != len(tail) + 2 \
-                    or not x.is_contiguous() or x.device != dev:
-                raise ValueError(f'{what} must be a contiguous torch.float64 tensor [n_nom, T, {", ".join(map(str, tail))}] on {dev}')
+            _check_tensor(x, torch.float64, dev, (None, None) + tail,
+                          f'{what} must be a contiguous torch.float64 tensor [n_nom, T, {", ".join(map(str, tail))}] on {dev}')
         chk(x_nom, 'x_nom', nx)
         n_nom, T = int(x_nom.shape[0]), int(x_nom.shape[1])
         chk(u_nom, 'u_nom', nu)
@@ -519,39 +589,25 @@ class Batch:
         for x, what in ((u_nom, 'u_nom'), (K, 'K'), (k, 'k')):
             if x is not None and tuple(x.shape[:2]) != (n_nom, T):
                 raise ValueError(f'{what} must have the leading axes of x_nom, [{n_nom}, {T}]')
-        ids = None if env_ids is None else np.ascontiguousarray(env_ids, np.int32).reshape(-1)
-        noms = None if nom_ids is None else np.ascontiguousarray(nom_ids, np.int32).reshape(-1)
+        ids, noms = as_env_ids(env_ids), as_env_ids(nom_ids)
         n = len(ids) if ids is not None else len(noms) if noms is not None else n_nom
         if noms is not None and len(noms) != n:
             raise ValueError(f'nom_ids names {len(noms)} nominals for {n} rollouts')
-        if alpha is not None and (not isinstance(alpha, torch.Tensor) or alpha.dtype != torch.float64 or tuple(alpha.shape) != (n,)
-                                  or not alpha.is_contiguous() or alpha.device != dev):
-            raise ValueError(f'alpha must be a contiguous torch.float64 tensor [{n}] on {dev}')
-        if stream is None and not emulated:
-            stream = torch.cuda.current_stream(self.device).cuda_stream
-        Kt = None
-        if K is not None:
-            if emulated or stream == torch.cuda.current_stream(self.device).cuda_stream:
-                Kt = K.transpose(2, 3).contiguous()
-            else:                                                                # (allocated on that stream: freed in its order)
-                with torch.cuda.stream(torch.cuda.ExternalStream(stream, device=dev)):
-                    Kt = K.transpose(2, 3).contiguous()
-        state = torch.zeros((n, T, nx), dtype=torch.float64, device=dev)
-        sens = torch.zeros((n, T, NSENSOR), dtype=torch.float64, device=dev) if sensors else None
-        ctrl = torch.zeros((n, T, nu), dtype=torch.float64, device=dev)
-        status = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
+        if alpha is not None:
+            _check_tensor(alpha, torch.float64, dev, (n,), f'alpha must be a contiguous torch.float64 tensor [{n}] on {dev}')
+        Kt = None if K is None else call.contiguous(K.transpose(2, 3))
+        state, ctrl = call.zeros(n, T, nx), call.zeros(n, T, nu)
+        sens = call.zeros(n, T, NSENSOR) if sensors else None
+        status = call.zeros(max(n, 1), dtype=torch.int32)
         cfg = _RolloutConfig(n, T, int(n_substeps), None if ids is None else ids.ctypes.data, int(pool_rows))
-        ptr = lambda t: None if t is None else t.data_ptr()
-        fbk = _Feedback(n_nom, None if noms is None else noms.ctypes.data, ptr(x_nom), ptr(u_nom), ptr(Kt), ptr(k), ptr(alpha))
-        cp = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-        _check(self.L, self.L.fb_batch_rollout_feedback(self.h, C.byref(cfg), C.byref(fbk), cp(state), cp(sens), cp(ctrl), cp(status), stream))
-        return Rollout(state, state[..., :nq], state[..., nq:nq + nv], state[..., nq + nv:], sens, status[:n], ctrl)
+        fbk = _Feedback(n_nom, None if noms is None else noms.ctypes.data, _ptr(x_nom), _ptr(u_nom), _ptr(Kt), _ptr(k), _ptr(alpha))
+        _check(self.L, self.L.fb_batch_rollout_feedback(self.h, C.byref(cfg), C.byref(fbk), _ptr(state), _ptr(sens), _ptr(ctrl), _ptr(status),
+                                                        call.stream))
+        return Rollout(*state_views(state, nq, nv), sens, status[:n], ctrl)
 
     def _torch_device(self):
-        """(torch.device of this batch's arrays, emulated): the emulation build computes on CPU tensors."""
-        import torch
-        emulated = b'emulation' in self.L.fb_version()
-        return (torch.device('cpu') if emulated else torch.device('cuda', self.device)), emulated
+        """The torch.device of this batch's arrays (the emulation build computes on CPU tensors)."""
+        return _DeviceCall(self).device
 
     def lqr_backward(self, A, B, Q, R, Qf=None, q=None, r=None, mu=None, stationary: bool = False, horizon: Optional[int] = None,
                      want_P: bool = False, stream=None) -> 'LQRBackward':
@@ -566,12 +622,10 @@ class Batch:
         copies nothing.  A nominal whose Quu + mu I is not positive definite at interval t has status 1 + t and zero outputs from t
         down.  Asynchronous on `stream` (None: torch's current stream)."""
         import torch
-        dev, emulated = self._torch_device()
+        call = _DeviceCall(self, stream)
 
         def chk(x, what, shape, names):
-            if not isinstance(x, torch.Tensor) or x.dtype != torch.float64 or not x.is_contiguous() or x.device != dev \
-                    or (shape is not None and tuple(x.shape) != tuple(shape)):
-                raise ValueError(f'{what} must be a contiguous torch.float64 tensor [{names}] on {dev}')
+            _check_tensor(x, torch.float64, call.device, shape, f'{what} must be a contiguous torch.float64 tensor [{names}] on {call.device}')
         chk(A, 'A', None, 'n_nom, ndx, ndx' if stationary else 'n_nom, T, ndx, ndx')
         if A.dim() != (3 if stationary else 4) or A.shape[-1] != A.shape[-2] or min(A.shape) < 1:
             raise ValueError('A must be [n_nom, ndx, ndx] (stationary) or [n_nom, T, ndx, ndx]')
@@ -598,41 +652,27 @@ class Batch:
             chk(r, 'r', (n_nom, Tout, nu), 'n_nom, T (stationary: 1), nu')
         if mu is not None:
             chk(mu, 'mu', (n_nom,), 'n_nom')
-        if stream is None and not emulated:
-            stream = torch.cuda.current_stream(self.device).cuda_stream
-
-        def outputs():
-            e = lambda *shape, dtype=torch.float64: torch.empty(shape, dtype=dtype, device=dev)        # (the call zeroes what it needs zero)
-            return (e(n_nom, Tout, ndx, nu), e(n_nom, Tout, nu), e(n_nom, TP, ndx, ndx) if want_P else None, e(n_nom, TP, ndx) if want_P else None,
-                    e(n_nom, 2), e(n_nom, dtype=torch.int32))
-        if emulated or stream == torch.cuda.current_stream(self.device).cuda_stream:
-            Kt, k, P, p, dV, status = outputs()
-        else:                                                                    # (allocated on that stream: freed in its order)
-            with torch.cuda.stream(torch.cuda.ExternalStream(stream, device=dev)):
-                Kt, k, P, p, dV, status = outputs()
+        e = call.empty                                                           # (the call zeroes what it needs zero)
+        Kt, k, dV, status = e(n_nom, Tout, ndx, nu), e(n_nom, Tout, nu), e(n_nom, 2), e(n_nom, dtype=torch.int32)
+        P, p = (e(n_nom, TP, ndx, ndx), e(n_nom, TP, ndx)) if want_P else (None, None)
         cfg = _LQRConfig(n_nom, T, ndx, nu, 1 if stationary else 0)
-        cp = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-        _check(self.L, self.L.fb_batch_lqr_backward(self.h, C.byref(cfg), cp(A), cp(B), cp(Q), cp(R), cp(Qf), cp(q), cp(r), cp(mu),
-                                                    cp(Kt), cp(k), cp(P), cp(p), cp(dV), cp(status), stream))
+        _check(self.L, self.L.fb_batch_lqr_backward(self.h, C.byref(cfg), _ptr(A), _ptr(B), _ptr(Q), _ptr(R), _ptr(Qf), _ptr(q), _ptr(r), _ptr(mu),
+                                                    _ptr(Kt), _ptr(k), _ptr(P), _ptr(p), _ptr(dV), _ptr(status), call.stream))
         return LQRBackward(Kt.transpose(2, 3), k, P, p, dV, status)
 
     def riccati_gemm(self, X, Y, D=None, trans_x: bool = False, trans_y: bool = False, stream=None):
         """C = op(X) op(Y) (+ D) through the product kernel of lqr_backward alone (fb_riccati_gemm; a test entry): contiguous float64
         2-D torch tensors on the batch's device."""
         import torch
-        dev, emulated = self._torch_device()
+        call = _DeviceCall(self, stream)
         for x, what in ((X, 'X'), (Y, 'Y')) + (((D, 'D'),) if D is not None else ()):
-            if not isinstance(x, torch.Tensor) or x.dtype != torch.float64 or x.dim() != 2 or not x.is_contiguous() or x.device != dev:
-                raise ValueError(f'{what} must be a contiguous 2-D torch.float64 tensor on {dev}')
+            _check_tensor(x, torch.float64, call.device, (None, None), f'{what} must be a contiguous 2-D torch.float64 tensor on {call.device}')
         m, k = (X.shape[1], X.shape[0]) if trans_x else X.shape
         k2, n = (Y.shape[1], Y.shape[0]) if trans_y else Y.shape
         if k != k2 or (D is not None and tuple(D.shape) != (m, n)):
             raise ValueError(f'op(X) is {m} x {k}, op(Y) {k2} x {n}: the inner sizes must agree and D be [{m}, {n}]')
-        if stream is None and not emulated:
-            stream = torch.cuda.current_stream(self.device).cuda_stream
-        Cm = torch.empty((m, n), dtype=torch.float64, device=dev)
-        _check(self.L, self.L.fb_riccati_gemm(self.h, int(m), int(n), int(k), int(trans_x), int(trans_y), C.c_void_p(X.data_ptr()),
-                                              C.c_void_p(Y.data_ptr()), None if D is None else C.c_void_p(D.data_ptr()), C.c_void_p(Cm.data_ptr()), stream))
+        Cm = call.empty(m, n)
+        _check(self.L, self.L.fb_riccati_gemm(self.h, int(m), int(n), int(k), int(trans_x), int(trans_y), _ptr(X), _ptr(Y), _ptr(D), _ptr(Cm), call.stream))
         return Cm
 
     def rollouts_run(self) -> int:

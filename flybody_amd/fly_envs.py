@@ -413,21 +413,25 @@ class BatchedFlyEnv:
         if x is None or x.dim() != 4:
             return self.batch.rollout(ctrl=ctrl, action=action, env_ids=env_ids, **kw)
         ne, K = int(x.shape[0]), int(x.shape[1])
-        ids = np.arange(self.n_env, dtype=np.int32) if env_ids is None else np.ascontiguousarray(env_ids, np.int32).reshape(-1)
+        ids = engine.as_env_ids(env_ids, self.n_env)
         if len(ids) != ne:
             raise ValueError(f'the leading axis of the inputs ({ne}) must match the environments listed ({len(ids)})')
         flat = x.reshape(ne*K, x.shape[2], x.shape[3])
-        r = self.batch.rollout(ctrl=None if action is not None else flat, action=flat if action is not None else None,
-                               env_ids=np.repeat(ids, K), **kw)
-        back = lambda t: None if t is None else t.reshape((ne, K) + tuple(t.shape[1:]))
-        return engine.Rollout(*(back(t) for t in r))
+        return self._per_sample(ids, K, self.batch.rollout, ctrl=None if action is not None else flat, action=flat if action is not None else None, **kw)
+
+    @staticmethod
+    def _per_sample(ids, K, call, *args, **kw):
+        """The sample axis: `call` runs K rollouts from every listed environment, rollout e K + s being sample s of ids[e], and its
+        outputs [ne K, ...] come back as [ne, K, ...]."""
+        r = call(*args, env_ids=np.repeat(ids, K), **kw)
+        return engine.Rollout(*(None if t is None else t.reshape((len(ids), K) + tuple(t.shape[1:])) for t in r))
 
     def _rollout_feedback(self, fbk, action, ctrl, env_ids, samples, **kw):
         if action is not None or ctrl is not None:
             raise ValueError('a closed-loop rollout computes its inputs: give feedback alone, without action or ctrl')
         if fbk.nom_ids is not None:
             raise ValueError('the nominal of a rollout is its environment here (nominal r for env_ids[r]): leave Feedback.nom_ids None')
-        ids = np.arange(self.n_env, dtype=np.int32) if env_ids is None else np.ascontiguousarray(env_ids, np.int32).reshape(-1)
+        ids = engine.as_env_ids(env_ids, self.n_env)
         ne = len(ids)
         if int(fbk.x_nom.shape[0]) != ne:
             raise ValueError(f'the leading axis of the nominals ({int(fbk.x_nom.shape[0])}) must match the environments listed ({ne})')
@@ -436,10 +440,8 @@ class BatchedFlyEnv:
         K = int(samples) if samples is not None else int(fbk.alpha.shape[1])
         if K < 1 or (fbk.alpha is not None and tuple(fbk.alpha.shape) != (ne, K)):
             raise ValueError(f'alpha must be [{ne}, {K}]: one step length per sample of every listed environment')
-        r = self.batch.rollout_feedback(fbk.x_nom, fbk.u_nom, fbk.K, fbk.k, None if fbk.alpha is None else fbk.alpha.reshape(ne*K),
-                                        nom_ids=np.repeat(np.arange(ne, dtype=np.int32), K), env_ids=np.repeat(ids, K), **kw)
-        back = lambda t: None if t is None else t.reshape((ne, K) + tuple(t.shape[1:]))
-        return engine.Rollout(*(back(t) for t in r))
+        return self._per_sample(ids, K, self.batch.rollout_feedback, fbk.x_nom, fbk.u_nom, fbk.K, fbk.k,
+                                None if fbk.alpha is None else fbk.alpha.reshape(ne*K), nom_ids=np.repeat(np.arange(ne, dtype=np.int32), K), **kw)
 
     # ---- the parts of a control step around the kernel ------------------------------------------
     @property

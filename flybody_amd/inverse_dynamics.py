@@ -20,11 +20,7 @@ InverseResult = namedtuple('InverseResult', ['qfrc_inverse', 'qfrc_constraint', 
                                              'contact_geoms', 'ncon', 'root_residual'])
 TrajectoryInverseResult = namedtuple('TrajectoryInverseResult', ['frames', 'qvel', 'qacc', 'joint_torques', 'result'])
 
-_JNT_FREE, _JNT_BALL = 0, 1
-
-
-def _model(model):
-    return engine.Model.from_asset(model) if isinstance(model, str) else model
+_JNT_FREE, _JNT_BALL = 0, 1               # (mjJNT_*; derivatives.py imports them and _quat_mul)
 
 
 def _quat_mul(a, b):
@@ -49,7 +45,7 @@ def differentiate_pos(model: Union['engine.Model', str], qa: np.ndarray, qb: np.
     """mj_differentiatePos: the velocity that takes qa to qb in time dt, the exact inverse of the engine's position integration
     (semi-implicit Euler: qpos <- integratePos(qpos, qvel_new, h)).  Free joint: world-frame linear velocity and the body-frame angular
     velocity log(qa^-1 qb) / dt; ball joint: the angular part; hinge and slide joints: differences.  qa, qb: (nq,) or (n, nq)."""
-    a = _model(model).arrays
+    a = engine.as_model(model).arrays
     qa = np.asarray(qa, np.float64); qb = np.asarray(qb, np.float64)
     if qa.shape != qb.shape or qa.shape[-1] != len(a['qpos0']):
         raise ValueError(f'qa and qb must both be (..., {len(a["qpos0"])}), got {qa.shape} and {qb.shape}')
@@ -78,7 +74,7 @@ def inverse_dynamics(model: Union['engine.Model', str], qpos: np.ndarray, qvel: 
     Returns InverseResult: qfrc_inverse, qfrc_constraint (n, nv); contact_force (n, 64, 3) in each contact's frame (normal, tangent 1,
     tangent 2); contact_pos (n, 64, 3), contact_normal (n, 64, 3), contact_geoms (n, 64, 2) geom ids (-1 beyond ncon); ncon (n,);
     root_residual (n, 6) = qfrc_inverse[:, :6] for a model whose first joint is free (the wrench nothing actuates), else None."""
-    model = _model(model)
+    model = engine.as_model(model)
     a = model.arrays
     nq, nv = len(a['qpos0']), len(a['dof_bodyid'])
     q = np.asarray(qpos, np.float64); v = np.asarray(qvel, np.float64); acc = np.asarray(qacc, np.float64)
@@ -87,16 +83,10 @@ def inverse_dynamics(model: Union['engine.Model', str], qpos: np.ndarray, qvel: 
         q, v, acc = q[None], v[None], acc[None]
     if q.ndim != 2 or q.shape[1] != nq or v.shape != (len(q), nv) or acc.shape != (len(q), nv):
         raise ValueError(f'qpos must be ({nq},) or (n, {nq}); qvel and qacc ({nv},) or (n, {nv}) with the same n')
-    if int(batch_size) < 1:
-        raise ValueError('batch_size must be >= 1')
     nf = len(q)
     qi = np.empty((nf, nv)); qc = np.empty((nf, nv)); cf = np.empty((nf, engine.MAXCON, 3)); con = np.empty((nf, engine.MAXCON, 8))
     ncon = np.empty(nf, np.int32)
-    batch, bn = None, 0
-    for lo in range(0, nf, int(batch_size)):
-        hi = min(nf, lo + int(batch_size))
-        if batch is None or bn != hi - lo:
-            batch, bn = engine.Batch(model, hi - lo, device=device, precision=64), hi - lo
+    for batch, lo, hi in engine.helper_batches(model, nf, batch_size, device):
         batch.set('QPOS', q[lo:hi]); batch.set('QVEL', v[lo:hi]); batch.set('QACC', acc[lo:hi])
         batch.inverse(discrete=discrete)
         qi[lo:hi] = batch.get('QFRC_INVERSE'); qc[lo:hi] = batch.get('QFRC_CONSTRAINT')
@@ -123,7 +113,7 @@ def trajectory_inverse_dynamics(model: Union['engine.Model', str], qpos_traj: np
     approximation (the discrete conversion always uses the model's timestep).
     Returns TrajectoryInverseResult: frames (the frame indices), qvel, qacc, joint_torques {joint name: qfrc_inverse of the joint's
     dofs, (n,) for one-dof joints, (n, k) otherwise} and the InverseResult of those frames."""
-    model = _model(model)
+    model = engine.as_model(model)
     a = model.arrays
     q = np.asarray(qpos_traj, np.float64)
     if q.ndim != 2 or q.shape[1] != len(a['qpos0']) or len(q) < 3:

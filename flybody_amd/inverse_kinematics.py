@@ -54,8 +54,7 @@ def qpos_from_site_xpos(model: Union['engine.Model', str], site_names: Sequence[
     independently, per-frame result arrays.  qpos_init: starting pose, (nq,) or (n_frames, nq); default the model's qpos0.
     Frames go through batches of at most `batch_size` environments on GPU `device`.
     Returns IKResult(qpos, err_norm, err_norm_first_term, steps, success)."""
-    if isinstance(model, str):
-        model = engine.Model.from_asset(model)
+    model = engine.as_model(model)
     a = model.arrays
     sites = _ids(site_names, a['names_site'], 'site')
     joints = _ids(joint_names, a['names_jnt'], 'joint')
@@ -71,14 +70,8 @@ def qpos_from_site_xpos(model: Union['engine.Model', str], site_names: Sequence[
         raise ValueError(f'qpos_init must be ({nq},) or ({nf}, {nq})')
     q0 = np.broadcast_to(q0, (nf, nq))
     mask = _include_mask(include_inds, 3*len(sites))
-    if int(batch_size) < 1:
-        raise ValueError('batch_size must be >= 1')
     qpos = np.empty((nf, nq)); err = np.empty((nf, 2)); steps = np.empty((nf, 2), np.int32)
-    batch, bn = None, 0
-    for lo in range(0, nf, int(batch_size)):
-        hi = min(nf, lo + int(batch_size))
-        if batch is None or bn != hi - lo:
-            batch, bn = engine.Batch(model, hi - lo, device=device, precision=64), hi - lo
+    for batch, lo, hi in engine.helper_batches(model, nf, batch_size, device):
         batch.set('QPOS', q0[lo:hi])
         batch.ik(sites, joints, t[lo:hi], include=mask, reg_strength=reg_strength, lr=lr, beta=beta,
                  progress_threshold=progress_threshold, max_steps=max_steps)

@@ -17,7 +17,7 @@ from typing import Optional, Tuple
 
 import numpy as np
 
-from . import inverse_dynamics
+from . import engine, inverse_dynamics
 
 
 def state_difference(model, x: np.ndarray, x_nom: np.ndarray) -> np.ndarray:
@@ -25,7 +25,7 @@ def state_difference(model, x: np.ndarray, x_nom: np.ndarray) -> np.ndarray:
     hinge and slide joints and free-joint translation, the body-frame rotation vector that takes the nominal quaternion to the state's
     for free- and ball-joint rotation -- and plain differences of qvel and act.  What the feedback kernel multiplies the gains with.
     x, x_nom: (..., nq + nv + na), leading axes broadcast; model: an engine.Model, an asset name, or anything with the model's `.arrays`."""
-    a = inverse_dynamics._model(model).arrays
+    a = engine.as_model(model).arrays
     nq = len(a['qpos0'])
     x = np.asarray(x, np.float64); xn = np.asarray(x_nom, np.float64)
     if x.shape[-1:] != xn.shape[-1:] or x.shape[-1] < nq:
@@ -58,7 +58,7 @@ def _riccati_step(A, B, Q, R, P):
 def _on_device(batch, *arrays):
     """The arrays as contiguous FP64 torch tensors where `batch` computes (None stays None)."""
     import torch
-    dev, _ = batch._torch_device()
+    dev = batch._torch_device()
     return [None if a is None else torch.from_numpy(np.ascontiguousarray(a, np.float64)).to(dev) for a in arrays]
 
 

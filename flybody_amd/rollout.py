@@ -23,10 +23,6 @@ from . import engine
 RolloutResult = collections.namedtuple('RolloutResult', ['state', 'qpos', 'qvel', 'act', 'sensordata', 'status', 'ctrl'], defaults=(None,))
 
 
-def _model(model):
-    return engine.Model.from_asset(model) if isinstance(model, str) else model
-
-
 def _feedback_arrays(feedback, nx, nu, ndx):
     """engine.Feedback of numpy arrays with the leading nominal axis ([n_nom, T, .]; one nominal may come without it)."""
     f = engine.Feedback(*feedback)
@@ -38,8 +34,7 @@ def _feedback_arrays(feedback, nx, nu, ndx):
             or (K is not None and K.shape != x.shape[:2] + (nu, ndx)) or (k is not None and k.shape != u.shape):
         raise ValueError(f'feedback: x_nom (T, {nx}) or (n_nom, T, {nx}) with T >= 1, u_nom and k (.., T, {nu}), K (.., T, {nu}, {ndx})')
     alpha = None if f.alpha is None else np.ascontiguousarray(np.asarray(f.alpha, np.float64).reshape(-1))
-    noms = None if f.nom_ids is None else np.ascontiguousarray(np.asarray(f.nom_ids, np.int32).reshape(-1))
-    return x, u, K, k, alpha, noms
+    return x, u, K, k, alpha, engine.as_env_ids(f.nom_ids)
 
 
 def rollout(model_or_task_name: Union['engine.Model', str], qpos: np.ndarray, qvel: np.ndarray, act: Optional[np.ndarray] = None,
@@ -64,7 +59,7 @@ def rollout(model_or_task_name: Union['engine.Model', str], qpos: np.ndarray, qv
     of the states if there are several, else of nom_ids, alpha, or the nominals.  The result carries ctrl (n, T, nu), the inputs applied,
     and comes without the leading axis only for one state and one nominal given without theirs."""
     import torch
-    model = _model(model_or_task_name)
+    model = engine.as_model(model_or_task_name)
     nq, nv, na, nu = (model.dim(k) for k in ('nq', 'nv', 'na', 'nu'))
     q = np.asarray(qpos, np.float64); v = np.asarray(qvel, np.float64)
     one_state = q.ndim == 1
@@ -98,21 +93,14 @@ def rollout(model_or_task_name: Union['engine.Model', str], qpos: np.ndarray, qv
         n, T = u.shape[0], u.shape[1]
         if not one_state and ns != n:
             raise ValueError(f'{ns} initial states for {n} control sequences: give one state, or one per sequence')
-    if int(batch_size) < 1:
-        raise ValueError('batch_size must be >= 1')
-    dev = 'cpu' if b'emulation' in model.L.fb_version() else f'cuda:{device}'      # (the tests' kernel-emulation build: "device" memory is host memory)
     state = np.empty((n, T, nx)); status = np.empty(n, np.int32)
     sens = np.empty((n, T, engine.NSENSOR)) if sensors else None
     applied = np.empty((n, T, nu)) if feedback is not None else None
-    if feedback is not None:
-        to = lambda a: None if a is None else torch.from_numpy(a).to(dev)
-        xn_d, un_d, Kn_d, kn_d = to(xn), to(un), to(Kn), to(kn)
-    batch, bn = None, 0
-    for lo in range(0, n, int(batch_size)):
-        hi = min(n, lo + int(batch_size))
-        rows = 1 if one_state else hi - lo               # environments of the helper batch: the distinct states of this chunk
-        if batch is None or bn != rows:
-            batch, bn = engine.Batch(model, rows, device=device, precision=64), rows
+    # (environments of the helper batch: the distinct states of a chunk)
+    for batch, lo, hi in engine.helper_batches(model, n, batch_size, device, rows=1 if one_state else None):
+        to = lambda a: None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(batch._torch_device())
+        if lo == 0 and feedback is not None:
+            nominal = [to(a) for a in (xn, un, Kn, kn)]
         if lo == 0 or not one_state:
             s = slice(0, 1) if one_state else slice(lo, hi)
             batch.set('QPOS', q[s]); batch.set('QVEL', v[s])
@@ -121,11 +109,10 @@ def rollout(model_or_task_name: Union['engine.Model', str], qpos: np.ndarray, qv
             batch.forward()
         ids = np.zeros(hi - lo, np.int32) if one_state else np.arange(hi - lo, dtype=np.int32)
         if feedback is not None:
-            r = batch.rollout_feedback(xn_d, un_d, Kn_d, kn_d, None if alpha is None else torch.from_numpy(alpha[lo:hi].copy()).to(dev),
-                                       nom_ids=noms[lo:hi], env_ids=ids, n_substeps=n_substeps, sensors=sensors)
+            r = batch.rollout_feedback(*nominal, to(None if alpha is None else alpha[lo:hi]), nom_ids=noms[lo:hi], env_ids=ids,
+                                       n_substeps=n_substeps, sensors=sensors)
         else:
-            r = batch.rollout(ctrl=torch.from_numpy(np.ascontiguousarray(u[lo:hi])).to(dev), env_ids=ids, n_substeps=n_substeps,
-                              sensors=sensors)
+            r = batch.rollout(ctrl=to(u[lo:hi]), env_ids=ids, n_substeps=n_substeps, sensors=sensors)
         batch.synchronize()
         state[lo:hi] = r.state.cpu().numpy(); status[lo:hi] = r.status.cpu().numpy()
         if sensors:
@@ -135,4 +122,4 @@ def rollout(model_or_task_name: Union['engine.Model', str], qpos: np.ndarray, qv
     if single:
         state, status, sens = state[0], int(status[0]), None if sens is None else sens[0]
         applied = None if applied is None else applied[0]
-    return RolloutResult(state, state[..., :nq], state[..., nq:nq + nv], state[..., nq + nv:], sens, status, applied)
+    return RolloutResult(*engine.state_views(state, nq, nv), sens, status, applied)
