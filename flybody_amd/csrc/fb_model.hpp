@@ -486,5 +486,10 @@ extern "C" int fb_model_dim(const fb_model* m, const char* name) {
 #undef X
   if (!strcmp(name, "nact")) return m->nu + (m->i("user_action_idx")[0] >= 0 ? 1 : 0);
   if (!strcmp(name, "nobs_base")) return obs_width(m, 0, false);
+  // where this build places the Delassus matrix (LdsCfg; d_constraint_a): rows of the LDS matrix slot, rows of the wide LDS placement
+  if (!strcmp(name, "lds_ar_rows_f64")) return LdsCfg<double>::AR_ROWS;
+  if (!strcmp(name, "lds_wide_rows_f64")) return LdsCfg<double>::WIDE_ROWS;
+  if (!strcmp(name, "lds_ar_rows_f32")) return LdsCfg<float>::AR_ROWS;
+  if (!strcmp(name, "lds_wide_rows_f32")) return LdsCfg<float>::WIDE_ROWS;
   return -1;
 }

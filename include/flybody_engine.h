@@ -102,7 +102,9 @@ enum { FB_WARN_CONTACT_CAP = 1, FB_WARN_EFC_CAP = 2, FB_WARN_SOLVER_MAXITER = 4,
        FB_WARN_MODEL_ID = 64 /* grouped batch: the environment's FB_ENV_MODEL entry was outside [0, n_models) when the kernel picked the
                                 environment up (only possible through the device pointer); it was clamped into range for that launch. */ };
 
-/* model dimensions by name: "nq","nv","nu","na","nbody","nobs","nsubstep", ... ; -1 if unknown */
+/* model dimensions by name: "nq","nv","nu","na","nbody","nobs","nsubstep", ... ; -1 if unknown.
+   Also the build's constraint-matrix placement: "lds_ar_rows_f64" / "lds_ar_rows_f32" (largest system whose Delassus matrix lives in the
+   LDS matrix slot) and "lds_wide_rows_f64" / "lds_wide_rows_f32" (largest system solved from LDS at all; at most 64). */
 int fb_model_dim(const fb_model* m, const char* name);
 
 /* Load a compiled-model blob (flybody_amd/model_blob.py: "FBM1"). */

@@ -5,7 +5,8 @@ Tolerances (written here, as the task statement requires):
     stage output (different summation orders only) and 1e-6 on solver-dependent outputs (the Newton
     solver -- the model's default, fb_newton.hpp / fbo_constraint.c: solve_newton -- stops on a 1e-8
     bound on the scaled cost decrement, so the last iteration may differ; Newton runs at EVERY system size on both sides since
-    round 5 -- d_newton_wide beyond one row per lane -- and block PGS, behind opt_solver = 0, stops on the same threshold);
+    round 5 -- d_newton_wide beyond one row per lane -- and block PGS, behind opt_solver = 0, stops on the same threshold: it is held
+    against the oracle's PGS at these tolerances in tests/test_pgs_solver.py, CPU emulation and GPU);
   * FP64 kernel vs oracle over 20 ... 100 control steps (contacts, Newton, noslip):  1e-6 relative
     on qpos / qvel (contact-rich dynamics amplify rounding differences; measured ~1e-11);
   * FP32 kernel vs oracle, single forward evaluation:  2e-3 relative on accelerations.
