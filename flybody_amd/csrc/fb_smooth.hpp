@@ -357,7 +357,7 @@ __device__ __forceinline__ void d_kinematics(const DevModel<real>& M, const WS<r
   }
   PROF(26);
   K_PROF(2);
-  // centre of mass of the (single) kinematic tree
+  // centre of mass of the whole model (every body of every kinematic tree): the reference point of cdof, cvel and the wrenches
   real c[3] = {0, 0, 0};
   for (int b = lane; b < M.nbody; b += FB_WAVE) {
     real bp[3] = {S[7*b], S[7*b + 1], S[7*b + 2]}, bq[4] = {S[7*b + 3], S[7*b + 4], S[7*b + 5], S[7*b + 6]};
@@ -1197,7 +1197,8 @@ __device__ __forceinline__ void d_com_vel(const DevModel<real>& M, const WS<real
   SYNC_LDS();
 }
 
-// 6-D velocity of a frame (pos, rot) rigidly attached to a body with spatial velocity cv (about the tree CoM), expressed in that frame
+// 6-D velocity of a frame (pos, rot) rigidly attached to a body with spatial velocity cv (about com = w.com(), the CoM of the whole
+// model: one reference point for every kinematic tree), expressed in that frame
 template <typename real, typename CV>
 FBD void frame_velocity(const CV cv, const real* com, const real* pos, const real* rot, real* lvel) {
   const real c6[6] = {cv[0], cv[1], cv[2], cv[3], cv[4], cv[5]};

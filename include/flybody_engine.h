@@ -53,10 +53,15 @@ enum {
   FB_QFRC_ACTUATOR = 21,
   FB_QFRC_CONSTRAINT = 22,
   FB_STEP_COUNT = 23, /* [n_env] int32 control steps since reset */
-  FB_SUBTREE_COM = 24,/* [n_env][3] */
+  FB_SUBTREE_COM = 24,/* [n_env][3] centre of mass of the WHOLE model (MuJoCo's subtree_com[0]: every body of every kinematic tree,
+                         in walk_on_ball the ball included); the one reference point of FB_CVEL */
   FB_GEOM_XPOS = 27,  /* [n_env][ngeom][3] */
   FB_GEOM_XMAT = 28,  /* [n_env][ngeom][9] */
-  FB_CVEL = 29,       /* [n_env][nbody][6] spatial velocity [angular, linear] about the tree CoM */
+  FB_CVEL = 29,       /* [n_env][nbody][6] spatial velocity [angular, linear] of every body about FB_SUBTREE_COM, in a model with
+                         several kinematic trees as well.  MuJoCo's cvel refers body b to subtree_com[body_rootid[b]], its own tree's
+                         CoM: with two trees (walk_on_ball) the linear parts differ from MuJoCo's, the angular parts and every point
+                         velocity do not -- the velocity of a point p of body b is linear + angular x (p - FB_SUBTREE_COM)
+                         (flybody_amd/fluid.py: object_velocity; tests/test_smooth_stages.py) */
   FB_STEP_TICKS = 30, /* [n_env] int32: duration of the environment's last control step on the GPU (100 MHz ticks) */
   FB_LAUNCH_ORDER = 31, /* [n_env] int32: environment ids in the order the next full-batch step launches them
                            (longest last step first; scheduling only, results do not depend on it) */
