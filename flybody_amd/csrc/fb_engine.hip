@@ -535,28 +535,20 @@ struct fb_batch {
   DevBuf<double> lqr_ws;
 };
 
-template <typename real, typename T, typename P>
+// one table of n elements, converted to E (int, or the batch's real), in a device allocation of its own that the batch keeps
+template <typename E, typename T, typename P>
 static int upload(fb_batch* b, const T* src, size_t n, P* dst) {
-  std::vector<real> tmp(n ? n : 1);
-  for (size_t k = 0; k < n; k++) tmp[k] = (real)src[k];
+  std::vector<E> tmp(n ? n : 1);      // an EMPTY table keeps one ZERO entry: the kernels read entry 0 of a table unpredicated in places
+                                      // (flight_imitation has no force sensors: a garbage site id from here indexed site_bodyid wildly)
+  for (size_t k = 0; k < n; k++) tmp[k] = (E)src[k];
   DevBuf<void> d;
-  if (d.alloc(tmp.size()*sizeof(real))) return -1;
-  HIPCHK(hipMemcpy(d.get(), tmp.data(), tmp.size()*sizeof(real), hipMemcpyHostToDevice));
-  *dst = (const real*)d.get();
+  if (d.alloc(tmp.size()*sizeof(E))) return -1;
+  HIPCHK(hipMemcpy(d.get(), tmp.data(), tmp.size()*sizeof(E), hipMemcpyHostToDevice));
+  *dst = (const E*)d.get();
   b->allocs.push_back(std::move(d));
   return 0;
 }
-template <typename P>
-static int upload_i(fb_batch* b, const int* src, size_t n, P* dst) {
-  DevBuf<void> d;
-  if (d.alloc((n ? n : 1)*sizeof(int))) return -1;
-  if (n) HIPCHK(hipMemcpy(d.get(), src, n*sizeof(int), hipMemcpyHostToDevice));
-  else HIPCHK(hipMemset(d.get(), 0, sizeof(int)));  // an EMPTY table keeps one ZERO entry: the kernels read entry 0 of a table unpredicated in places
-                                                    // (flight_imitation has no force sensors: a garbage site id from here indexed site_bodyid wildly)
-  *dst = (const int*)d.get();
-  b->allocs.push_back(std::move(d));
-  return 0;
-}
+template <typename P> static int upload_i(fb_batch* b, const int* src, size_t n, P* dst) { return upload<int>(b, src, n, dst); }
 
 // f(M) on the batch's model at its precision: M64 for an FP64 batch, M32 for an FP32 one (the other one is never built or read).
 // Inside f, `using real = decltype(M.timestep);` names the precision.
@@ -606,97 +598,58 @@ static int alloc_obs(fb_batch* b, int nobs) {
   return 0;
 }
 
+// The environment's test and measurement switches, read in one place, once, when a batch is created (batch_create_impl declares one).  Two truth
+// rules, as ever: env_is1 -- in force when the variable's value begins with '1'; env_is_set -- in force when the variable exists, whatever it holds.
+static bool env_is1(const char* n) { const char* e_ = getenv(n); return e_ && e_[0] == '1'; }
+static bool env_is_set(const char* n) { return getenv(n) != nullptr; }
+struct Switches {
+  bool no_neighbour_list = env_is1("FB_NO_NEIGHBOUR_LIST");      // vl_delta = 0 (the tests compare the two mid phases bit for bit)
+  bool no_ar_entry_lanes = env_is1("FB_NO_AR_ENTRY_LANES");      // ar_entry_lanes = 0 (... the two builds of the Delassus matrix bit for bit)
+  bool no_solver_handover = env_is1("FB_NO_SOLVER_HANDOVER");    // solver_handover = 0 (... the two hand-overs against the oracle and each other)
+  bool no_reorder = env_is1("FB_NO_REORDER");                    // environments and tickets keep their order
+  bool no_fk_merge = env_is_set("FB_NO_FK_MERGE");               // fk_second = null: separate kinematics passes (the tests run both paths)
+  bool no_tickets = env_is_set("FB_NO_TICKETS");                 // the per-wave path whatever the batch's size
+  bool no_prio = env_is_set("FB_NO_PRIO");
+  const char* ticket_slots = getenv("FB_TICKET_SLOTS");          // set: its value replaces the resident slot count (the tests pretend fewer slots)
+};
+
+// The device struct of model m at one precision: the scalars copied, the real ones converted, the switches applied, the tables uploaded.
+// Nothing is derived here: whatever follows from the model alone is fb_model_load's (fb_model.hpp).
 template <typename real>
-static int build_devmodel(fb_batch* b, const fb_model* m, DevModel<real>& M) {
+static int build_devmodel(fb_batch* b, const fb_model* m, const Switches& sw, DevModel<real>& M) {
   memset(&M, 0, sizeof(M));
   M.nq = m->nq; M.nv = m->nv; M.nbody = m->nbody; M.njnt = m->njnt; M.ngeom = m->ngeom; M.nsite = m->nsite;
   M.nu = m->nu; M.na = m->na; M.ntendon = m->ntendon; M.npair = m->npair; M.nM = m->nM; M.nsubstep = m->nsubstep;
   M.nobsjnt = m->nobsjnt; M.napp = m->napp; M.nforce = m->nforce; M.ntouch = m->ntouch;
-  M.site_thorax = m->i("sensor_site_thorax")[0]; M.nadh = (int)m->adh_act.size();
-  M.iterations = m->i("opt_iterations")[0]; M.noslip_iterations = m->i("opt_noslip_iterations")[0];
-  // opt_solver is optional: a blob without it gets MuJoCo's default, Newton -- what the reference XML selects (fruitfly.xml:4)
-  M.solver = (m->has("opt_solver", 1) && m->i("opt_solver")[0] == FB_SOLVER_PGS) ? FB_SOLVER_PGS : FB_SOLVER_NEWTON;
-  M.timestep = (real)m->d("opt_timestep")[0]; M.control_timestep = (real)m->d("opt_control_timestep")[0];
-  for (int k = 0; k < 3; k++) M.grav[k] = (real)m->d("opt_gravity")[k];
-  M.density = (real)m->d("opt_density")[0]; M.viscosity = (real)m->d("opt_viscosity")[0];
-  M.impratio = (real)m->d("opt_impratio")[0]; M.tolerance = (real)m->d("opt_tolerance")[0];
-  {
-    // neighbour-list slack: half the median bounding radius of the geoms that have one (planes: 0) -- the fruit fly: 0.0083 model units; measured best of
-    // 0.002 ... 0.06 (profiles/r6/ab_neighbour_list.txt).  No list for models whose pair count fits a few wave passes anyway.
-    std::vector<double> rb; const double* r_ = m->d("geom_rbound");
-    for (int g = 0; g < m->ngeom; g++) if (r_[g] > 0) rb.push_back(r_[g]);
-    std::sort(rb.begin(), rb.end());
-    M.vl_delta = (rb.empty() || m->npair <= 4*FB_WAVE) ? (real)0 : (real)(FB_VL_SCALE*rb[rb.size()/2]);
-    // the list's validity test watches the geom centres only: a plane on a moving body could turn its normal without moving its centre -- no list then
-    { const int* gt_ = m->i("geom_type"); const int* gb_ = m->i("geom_bodyid"); for (int g = 0; g < m->ngeom; g++) if (gt_[g] == GEOM_PLANE && gb_[g] != 0) M.vl_delta = 0; }
-    { const char* e_ = getenv("FB_NO_NEIGHBOUR_LIST"); if (e_ && e_[0] == '1') M.vl_delta = 0; }      // (read at model load: the tests compare the two paths bit for bit)
-  }
-  M.ar_entry_lanes = 1;
-  { const char* e_ = getenv("FB_NO_AR_ENTRY_LANES"); if (e_ && e_[0] == '1') M.ar_entry_lanes = 0; }      // (read at model load, like the switch above: the tests compare the two builds of the Delassus matrix bit for bit)
-  M.solver_handover = 1;
-  { const char* e_ = getenv("FB_NO_SOLVER_HANDOVER"); if (e_ && e_[0] == '1') M.solver_handover = 0; }      // (read at model load, like the two above: the tests compare the two hand-overs against the oracle and each other)
-  M.noslip_tolerance = (real)m->d("opt_noslip_tolerance")[0]; M.meaninertia = (real)m->d("stat_meaninertia")[0];
-  M.totalmass = (real)m->totalmass;
-  size_t c;
-#define UI(field, name) { const int* s_ = m->i(name, &c); if (upload_i(b, s_, c, &M.field)) return -1; }
-#define UV(field, vec) { if (upload_i(b, m->vec.data(), m->vec.size(), &M.field)) return -1; }
-#define UD(field, name) { const double* s_ = m->d(name, &c); if (upload<real>(b, s_, c, &M.field)) return -1; }
-  UI(body_parent, "body_parent") UI(body_dofadr, "body_dofadr")
-  UV(body_nsub, body_nsub) UV(body_depth, body_depth) UV(body_chlen, body_chlen) UV(body_chain, body_chain) UV(body_common, body_common)
-  UI(jnt_type, "jnt_type") UI(jnt_qposadr, "jnt_qposadr") UI(jnt_dofadr, "jnt_dofadr") UI(jnt_bodyid, "jnt_bodyid") UI(jnt_limited, "jnt_limited")
-  UI(dof_bodyid, "dof_bodyid") UI(dof_jntid, "dof_jntid") UI(dof_Madr, "dof_Madr") UV(dof_depth, dof_depth)
-  UV(dof_ndesc, dof_ndesc) UV(body_fluid_geom, body_fluid_geom) UV(sens_body, sens_body) M.nsensbody = (int)m->sens_body.size();
-  UV(dof_jump, dof_jump) UV(dof_vbef, dof_vbef) UV(body_veldof, body_veldof)
-  UV(dof_cl, dof_cl) UV(dof_gen, dof_gen) UV(gen_k, gen_k) UV(gen_m, gen_m) UV(fwd_tab, fwd_tab) UV(fwd_pack, fwd_pack) UV(fac_w, fac_w) UV(fac_band, fac_band) UV(fac_dof, fac_dof) M.ntrunk = m->ntrunk; M.prefix_split = m->prefix_split;
-  { int dmax = 0, d2 = 1 << 20; for (int bq = 1; bq < m->nbody; bq++) { dmax = std::max(dmax, m->body_depth[bq]); if (bq >= FB_WAVE) d2 = std::min(d2, m->body_depth[bq]); } M.fk_dmax = dmax; M.fk2_dlo = d2; }
-  { int cm = 0; for (int bq = 0; bq < m->nbody; bq++) cm = std::max(cm, m->body_chlen[bq]); M.chmax = cm; }
-  {
-    // kinematics level loop: bodies beyond the wavefront width ride along on lanes whose own body sits on a
-    // SHALLOWER level, so one trip down the levels covers every body (fb_smooth.hpp fk_pass)
-    std::vector<int> second(FB_WAVE, -1);
-    bool ok = m->nbody > FB_WAVE && m->nbody <= 2*FB_WAVE && getenv("FB_NO_FK_MERGE") == nullptr;      // (switch: tests run both paths)
-    for (int bq = FB_WAVE; ok && bq < m->nbody; bq++) {
-      int pick = -1;
-      for (int l = 0; l < FB_WAVE && pick < 0; l++) if (second[l] < 0 && (l == 0 || m->body_depth[l] < m->body_depth[bq])) pick = l;      // (deeper than the lane's own body: fk_pass reuses the record registers)
-      if (pick < 0) ok = false; else second[pick] = bq;
-    }
-    M.fk_second = nullptr;
-    if (ok && upload_i(b, second.data(), second.size(), &M.fk_second)) return -1;
-  }
-  UI(wing_act_idx, "wing_action_idx")
-  // leg joints (optional array: models compiled before the flight-with-legs variant do not carry it)
-  if (m->has("leg_joints", 1)) { UI(leg_jnt, "leg_joints") M.nlegjnt = (int)c; for (size_t k = 0; k < c; k++) if (m->i("leg_joints")[k] < 0 || m->i("leg_joints")[k] >= m->njnt) return fail("fb_batch_create: leg_joints out of range"); }
-  else { UV(leg_jnt, adh_act) M.nlegjnt = 0; }
+  M.site_thorax = m->i("sensor_site_thorax")[0]; M.nadh = (int)m->adh_act.size(); M.nplane = m->nplane; M.nsensbody = (int)m->sens_body.size();
+  M.iterations = m->i("opt_iterations")[0]; M.noslip_iterations = m->i("opt_noslip_iterations")[0]; M.solver = m->solver;
+  M.nlevel = m->nlevel; M.ntrunk = m->ntrunk; M.prefix_split = m->prefix_split; M.chmax = m->chmax; M.fk_dmax = m->fk_dmax; M.fk2_dlo = m->fk2_dlo;
   M.task = m->task_id; M.user_idx = m->i("user_action_idx")[0]; M.nact = m->nu + (M.user_idx >= 0 ? 1 : 0);
-  for (int k = 0; k < 3; k++) M.com_offset[k] = (real)m->d("com_offset")[k];
-  M.nlevel = m->nlevel;
-  UI(geom_type, "geom_type") UI(geom_bodyid, "geom_bodyid") UI(site_bodyid, "site_bodyid") UI(site_type, "site_type")
-  UI(tendon_adr, "tendon_adr") UI(tendon_num, "tendon_num")
-  UI(act_trntype, "actuator_trntype") UI(act_trnid, "actuator_trnid") UI(act_dyntype, "actuator_dyntype") UI(act_biastype, "actuator_biastype")
-  UI(act_ctrllimited, "actuator_ctrllimited") UI(act_forcelimited, "actuator_forcelimited") UI(act_actadr, "actuator_actadr")
-  UV(adh_act, adh_act) UI(action_to_ctrl, "action_to_ctrl")
-  UV(wrap_qadr, wrap_qadr) UV(act_wn, act_wn) UV(act_wdof, act_wdof) UV(act_lenadr, act_lenadr)
-  if (upload<real>(b, m->act_wcoef.data(), m->act_wcoef.size(), &M.act_wcoef)) return -1;
-  UI(pair_geom1, "pair_geom1") UI(pair_geom2, "pair_geom2") UI(pair_condim, "pair_condim")
-  UV(pair_word, pair_word) UV(pair_body, pair_body) UV(plane_geoms, plane_geoms)
-  { const int* gt_ = m->i("geom_type"); int np_ = 0; for (int g = 0; g < m->ngeom; g++) np_ += gt_[g] == GEOM_PLANE; M.nplane = np_; }
-  UI(obs_jnt, "observable_joints") UI(app_sites, "appendage_sites") UI(force_sites, "sensor_force_sites") UI(touch_sites, "sensor_touch_sites") UI(wing_jnt, "wing_jnt")
-  UD(body_mass, "body_mass")
-  UD(body_inertia, "body_inertia") UD(body_invweight0, "body_invweight0")
-  if (upload<real>(b, m->body_box.data(), m->body_box.size(), &M.body_box)) return -1;
-  if (upload<real>(b, m->geom_box.data(), m->geom_box.size(), &M.geom_box)) return -1;
-  if (upload<real>(b, m->body_rec.data(), m->body_rec.size(), &M.body_rec)) return -1;
-  UD(jnt_axis, "jnt_axis") UD(jnt_stiffness, "jnt_stiffness") UD(jnt_range, "jnt_range") UD(jnt_solref, "jnt_solref")
-  UD(jnt_solimp, "jnt_solimp") UD(jnt_margin, "jnt_margin") UD(qpos0, "qpos0") UD(qpos_spring, "qpos_spring")
-  UD(dof_armature, "dof_armature") UD(dof_damping, "dof_damping") UD(dof_invweight0, "dof_invweight0")
-  UD(geom_pos, "geom_pos") UD(geom_quat, "geom_quat") UD(geom_size, "geom_size") UD(geom_rbound, "geom_rbound") UD(geom_fluid, "geom_fluid")
-  UD(site_pos, "site_pos") UD(site_quat, "site_quat") UD(site_size, "site_size") UD(wrap_coef, "wrap_coef")
-  UD(act_dynprm, "actuator_dynprm") UD(act_gainprm, "actuator_gainprm") UD(act_biasprm, "actuator_biasprm") UD(act_ctrlrange, "actuator_ctrlrange") UD(act_forcerange, "actuator_forcerange")
-  UD(pair_friction, "pair_friction") UD(pair_solref, "pair_solref") UD(pair_solimp, "pair_solimp") UD(pair_margin, "pair_margin") UD(pair_gap, "pair_gap")
-#undef UI
-#undef UV
-#undef UD
-  return 0;
+  M.timestep = (real)m->d("opt_timestep")[0]; M.control_timestep = (real)m->d("opt_control_timestep")[0];
+  for (int k = 0; k < 3; k++) { M.grav[k] = (real)m->d("opt_gravity")[k]; M.com_offset[k] = (real)m->d("com_offset")[k]; }
+  M.density = (real)m->d("opt_density")[0]; M.viscosity = (real)m->d("opt_viscosity")[0]; M.impratio = (real)m->d("opt_impratio")[0]; M.tolerance = (real)m->d("opt_tolerance")[0];
+  M.noslip_tolerance = (real)m->d("opt_noslip_tolerance")[0]; M.meaninertia = (real)m->d("stat_meaninertia")[0]; M.totalmass = (real)m->totalmass;
+  M.vl_delta = sw.no_neighbour_list ? (real)0 : (real)m->vl_delta; M.ar_entry_lanes = sw.no_ar_entry_lanes ? 0 : 1; M.solver_handover = sw.no_solver_handover ? 0 : 1;
+  size_t c;                             // the tables of FB_MODEL_TABLES (fb_types.hpp), one allocation each
+#define FB_GET_int i
+#define FB_GET_real d
+#define FB_SRC_blob(kind, s) m->FB_GET_##kind(#s, &c)
+#define FB_SRC_vec(kind, s) (c = m->s.size(), m->s.data())
+#define X(member, kind, from, s) { const auto* s_ = FB_SRC_##from(kind, s); if (upload<kind>(b, s_, c, &M.member)) return -1; }
+  FB_MODEL_TABLES(X)
+#undef X
+  // fk_second: a nullable raw pointer -- null where the model has no lane pairing (fb_model.hpp: derive_topology) or the switch is set
+  if (!m->fk_second.empty() && !sw.no_fk_merge && upload_i(b, m->fk_second.data(), m->fk_second.size(), &M.fk_second)) return -1;
+  // leg_jnt: an optional blob array (models compiled before the flight-with-legs variant do not carry it); without it a valid table that nobody reads
+  const bool legs = m->has("leg_joints", 1);
+  const int* lj = legs ? FB_SRC_blob(int, leg_joints) : FB_SRC_vec(int, adh_act);
+  for (size_t k = 0; legs && k < c; k++) if (lj[k] < 0 || lj[k] >= m->njnt) return fail("fb_batch_create: leg_joints out of range");
+  M.nlegjnt = legs ? (int)c : 0;
+#undef FB_GET_int
+#undef FB_GET_real
+#undef FB_SRC_blob
+#undef FB_SRC_vec
+  return upload_i(b, lj, c, &M.leg_jnt);
 }
 
 template <typename real>
@@ -776,15 +729,16 @@ extern "C" int fb_batch_n_models(const fb_batch* b) {
 
 static int batch_create_impl(fb_batch* b) {
   const fb_model* m = b->m; const int n_env = b->n_env;
+  const Switches sw{};                  // (the environment as it is now)
   if (with_model(b, [&](auto& M) {
-        if (build_devmodel(b, m, M)) return -1;
+        if (build_devmodel(b, m, sw, M)) return -1;
         compute_offsets(M, b->off); M.off = b->off;
         // a group of more than one model: the structs of all of them (element 0 is refreshed from M by sync_model); every model gets tables of
         // its own, so whatever the host derives from real constants (vl_delta, body_box, geom_box, body_fluid_geom, totalmass) is per model
         if (b->models.size() > 1) {
           auto& G = group_models(b, M);
           G.assign(b->models.size(), M);
-          for (size_t k = 1; k < G.size(); k++) { if (build_devmodel(b, b->models[k], G[k])) return -1; G[k].off = b->off; }
+          for (size_t k = 1; k < G.size(); k++) { if (build_devmodel(b, b->models[k], sw, G[k])) return -1; G[k].off = b->off; }
         }
         return 0; })) return -1;
   if (!b->models.empty()) {
@@ -797,7 +751,7 @@ static int batch_create_impl(fb_batch* b) {
   if (b->rarena.alloc_zeroed((size_t)n_env*b->off.nreal*rs) || b->iarena.alloc_zeroed((size_t)n_env*b->off.nint)) return -1;
   if (b->reward.alloc_zeroed(n_env) || b->discount.alloc_zeroed(n_env) || b->step_type.alloc_zeroed(n_env)) return -1;
   if (b->d_ids.alloc(n_env) || b->sched.alloc(FB_NSCHED) || b->cost.alloc_zeroed(n_env) || b->order.alloc(n_env)) return -1;
-  { const char* e_ = getenv("FB_NO_REORDER"); b->reorder = !(e_ && e_[0] == '1'); b->ticket_order = b->reorder; }
+  b->reorder = b->ticket_order = !sw.no_reorder;
   // substep scheduler: for batches larger than the resident wave slots (k_fly)
   {
 #ifdef FB_EMULATE
@@ -824,15 +778,15 @@ static int batch_create_impl(fb_batch* b) {
     // the hand-over protocol of the scheduler (k_fly) is written against the cache hierarchy of gfx942 / gfx950: write-through vector
     // L1, one L2 per XCD, HW_REG_XCC_ID.  Any other architecture takes the per-wave path.
     if (strncmp(prop.gcnArchName, "gfx942", 6) != 0 && strncmp(prop.gcnArchName, "gfx950", 6) != 0) b->nq = 0;
-    if (const char* e_ = getenv("FB_TICKET_SLOTS")) b->slots = atoi(e_);             // (test switch: pretend fewer resident slots)
+    if (sw.ticket_slots) b->slots = atoi(sw.ticket_slots);
 #endif
     if (b->tick.alloc(16*16) || b->done.alloc(n_env) || b->torder.alloc((size_t)n_env + 16) || b->sched_err.alloc_zeroed(1) || b->probe_word.alloc(1)) return -1;
     // (round 3 kept flight_imitation -- equal-cost environments, short substeps -- on the per-wave path: tickets cost 3 % there.  With
     // the round-4 kernel they win for flight too: 8192 FP64 environments 2.21 -> 2.25 M env-steps/s on the default build, 2.52 -> 2.63 M
     // on the 12-per-CU build, profiles/r4/flight_variants.txt.  FB_NO_TICKETS=1 still forces the per-wave path.)
-    b->tickets = b->nq > 0 && b->slots > 0 && n_env > b->slots && getenv("FB_NO_TICKETS") == nullptr;
+    b->tickets = b->nq > 0 && b->slots > 0 && n_env > b->slots && !sw.no_tickets;
   }
-  b->use_prio = getenv("FB_NO_PRIO") == nullptr;
+  b->use_prio = !sw.no_prio;
   // initial state: qpos0 everywhere (fb_batch_reset overrides it once a reference is set)
   if (with_model(b, [&](auto& M) {
         std::vector<decltype(M.timestep)> rows((size_t)n_env*m->nq);

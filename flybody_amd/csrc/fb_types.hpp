@@ -199,6 +199,38 @@ struct DevModel {
   WSOff off;                 // layout of one environment's workspace row (fb_engine.hip: compute_offsets)
 };
 
+// The tables of DevModel that a new batch uploads (fb_engine.hip: build_devmodel walks this list), in the struct's order:
+// X(member, element kind: int | real, source: blob | vec, name of the blob array | of the fb_model vector (fb_model.hpp)).  One device
+// allocation per line.  Beside the list: fk_second and leg_jnt (build_devmodel), and the tables the setters upload later (ref_*, wb_*, ds_*).
+#define FB_MODEL_TABLES(X) \
+  X(body_parent, int, blob, body_parent) X(body_dofadr, int, blob, body_dofadr) X(body_nsub, int, vec, body_nsub) X(body_depth, int, vec, body_depth) \
+  X(body_chlen, int, vec, body_chlen) X(body_chain, int, vec, body_chain) X(body_common, int, vec, body_common) \
+  X(jnt_type, int, blob, jnt_type) X(jnt_qposadr, int, blob, jnt_qposadr) X(jnt_dofadr, int, blob, jnt_dofadr) X(jnt_bodyid, int, blob, jnt_bodyid) X(jnt_limited, int, blob, jnt_limited) \
+  X(dof_bodyid, int, blob, dof_bodyid) X(dof_jntid, int, blob, dof_jntid) X(dof_Madr, int, blob, dof_Madr) X(dof_depth, int, vec, dof_depth) X(dof_ndesc, int, vec, dof_ndesc) \
+  X(dof_cl, int, vec, dof_cl) X(dof_gen, int, vec, dof_gen) X(gen_k, int, vec, gen_k) X(gen_m, int, vec, gen_m) X(fwd_tab, int, vec, fwd_tab) X(fwd_pack, int, vec, fwd_pack) \
+  X(fac_w, int, vec, fac_w) X(fac_band, int, vec, fac_band) X(fac_dof, int, vec, fac_dof) \
+  X(geom_type, int, blob, geom_type) X(geom_bodyid, int, blob, geom_bodyid) X(site_bodyid, int, blob, site_bodyid) X(site_type, int, blob, site_type) \
+  X(tendon_adr, int, blob, tendon_adr) X(tendon_num, int, blob, tendon_num) \
+  X(act_trntype, int, blob, actuator_trntype) X(act_trnid, int, blob, actuator_trnid) X(act_dyntype, int, blob, actuator_dyntype) X(act_biastype, int, blob, actuator_biastype) \
+  X(act_ctrllimited, int, blob, actuator_ctrllimited) X(act_forcelimited, int, blob, actuator_forcelimited) X(act_actadr, int, blob, actuator_actadr) \
+  X(adh_act, int, vec, adh_act) X(wrap_qadr, int, vec, wrap_qadr) X(act_wn, int, vec, act_wn) X(act_wdof, int, vec, act_wdof) X(act_lenadr, int, vec, act_lenadr) \
+  X(act_wcoef, real, vec, act_wcoef) X(action_to_ctrl, int, blob, action_to_ctrl) \
+  X(pair_geom1, int, blob, pair_geom1) X(pair_geom2, int, blob, pair_geom2) X(pair_condim, int, blob, pair_condim) \
+  X(pair_body, int, vec, pair_body) X(pair_word, int, vec, pair_word) X(plane_geoms, int, vec, plane_geoms) \
+  X(obs_jnt, int, blob, observable_joints) X(app_sites, int, blob, appendage_sites) X(force_sites, int, blob, sensor_force_sites) X(touch_sites, int, blob, sensor_touch_sites) \
+  X(wing_jnt, int, blob, wing_jnt) X(dof_jump, int, vec, dof_jump) X(dof_vbef, int, vec, dof_vbef) X(body_veldof, int, vec, body_veldof) X(sens_body, int, vec, sens_body) \
+  X(body_mass, real, blob, body_mass) X(body_inertia, real, blob, body_inertia) X(body_invweight0, real, blob, body_invweight0) X(body_box, real, vec, body_box) \
+  X(body_rec, real, vec, body_rec) \
+  X(jnt_axis, real, blob, jnt_axis) X(jnt_stiffness, real, blob, jnt_stiffness) X(jnt_range, real, blob, jnt_range) X(jnt_solref, real, blob, jnt_solref) \
+  X(jnt_solimp, real, blob, jnt_solimp) X(jnt_margin, real, blob, jnt_margin) \
+  X(qpos0, real, blob, qpos0) X(qpos_spring, real, blob, qpos_spring) X(dof_armature, real, blob, dof_armature) X(dof_damping, real, blob, dof_damping) X(dof_invweight0, real, blob, dof_invweight0) \
+  X(geom_pos, real, blob, geom_pos) X(geom_quat, real, blob, geom_quat) X(geom_size, real, blob, geom_size) X(geom_rbound, real, blob, geom_rbound) X(geom_fluid, real, blob, geom_fluid) \
+  X(geom_box, real, vec, geom_box) X(site_pos, real, blob, site_pos) X(site_quat, real, blob, site_quat) X(site_size, real, blob, site_size) X(wrap_coef, real, blob, wrap_coef) \
+  X(act_dynprm, real, blob, actuator_dynprm) X(act_gainprm, real, blob, actuator_gainprm) X(act_biasprm, real, blob, actuator_biasprm) \
+  X(act_ctrlrange, real, blob, actuator_ctrlrange) X(act_forcerange, real, blob, actuator_forcerange) \
+  X(pair_friction, real, blob, pair_friction) X(pair_solref, real, blob, pair_solref) X(pair_solimp, real, blob, pair_solimp) X(pair_margin, real, blob, pair_margin) X(pair_gap, real, blob, pair_gap) \
+  X(wing_act_idx, int, blob, wing_action_idx) X(body_fluid_geom, int, vec, body_fluid_geom)
+
 // LDS pointers carry their address space in the type so that every access compiles to ds_read /
 // ds_write (a generic pointer would fall back to flat_* instructions and their global-class latency)
 #ifdef FB_EMULATE
