@@ -29,6 +29,7 @@ extern "C" { long long fb_stats[64]; }
 #include "fb_deriv.hpp"
 #include "fb_rollout.hpp"
 #include "fb_riccati.hpp"
+#include "fb_ray.hpp"
 #include "fb_host.hpp"                    // g_err / fail / HIPCHK, DevBuf, DevEvent
 #include "fb_model.hpp"                   // fb_model and the C-ABI's model entry points
 
@@ -533,6 +534,8 @@ struct fb_batch {
   int roll_fb_slots = 0;
   // fb_batch_lqr_backward (fb_riccati.hpp): the products' workspace of all nominals, grown as needed
   DevBuf<double> lqr_ws;
+  // fb_batch_ray (fb_ray.hpp): the call's small tables -- visible geoms, the frames' environments and terrain ids --, grown as needed
+  DevBuf<int> ray_tab; std::vector<int> ray_tab_host;
 };
 
 // one table of n elements, converted to E (int, or the batch's real), in a device allocation of its own that the batch keeps
@@ -1514,6 +1517,74 @@ extern "C" int fb_riccati_gemm(fb_batch* b, int m, int n, int k, int trans_x, in
   FB_GUARD_BEGIN
   HIPCHK(hipSetDevice(b->device));
   ric_gemm((hipStream_t)stream, 1, m, n, k, X, 0, trans_x ? 1 : k, trans_x ? m : 1, Y, 0, trans_y ? 1 : n, trans_y ? k : 1, D, 0, n, C, 0, nullptr);
+  HIPCHK(hipGetLastError());
+  return 0;
+  FB_GUARD_END
+}
+
+// ------------------------------------------------------------------ ray casting
+// mj_ray / mj_multiRay for n_ray rays in each of n_frames live environments (fb_ray.hpp: k_raycast), against the geoms as the last step left
+// them and an optional height field.  Not a control step and not a timed launch; the environments' rows are only read.  Everything the
+// kernel indexes with is validated HERE: it has no check of its own to fall back on.
+extern "C" int fb_batch_ray(fb_batch* b, const fb_ray_config* cfg, const double* rays, const fb_terrain* terrain, float* dist, int32_t* geomid, void* stream) {
+  const std::string fn = "fb_batch_ray";
+  if (!b || !cfg || !rays || !dist || !geomid) return fail(fn + ": null argument (batch, cfg, rays, dist or geomid)");
+  if (b->n_models() > 1) return fail(fn + ": per-model ray casting is not supported: this batch is a group of " + std::to_string(b->n_models()) + " models (fb_batch_create_group)");
+  const fb_model* m = b->m;
+  const int nf = cfg->n_frames, nr = cfg->n_ray;
+  if (nf < 1 || nr < 1) return fail(fn + ": n_frames and n_ray must be >= 1");
+  const long long tiles = ((long long)nr + FB_RAY_TILE - 1)/FB_RAY_TILE;
+  if (tiles*nf > (1ll << 23)) return fail(fn + ": too many rays for one call (more than 2^23 workgroups of " + std::to_string(FB_RAY_TILE) + " rays)");
+  if (cfg->per_frame != 0 && cfg->per_frame != 1) return fail(fn + ": per_frame must be 0 or 1");
+  if (side_check_env_ids(b, fn, cfg->env_ids, nf, "n_frames", "frame")) return -1;
+  if (cfg->body < -1 || cfg->body >= m->nbody) return fail(fn + ": body " + std::to_string(cfg->body) + " out of range (-1, or 0 .. " + std::to_string(m->nbody - 1) + ")");
+  if (cfg->bodyexclude < -1 || cfg->bodyexclude >= m->nbody) return fail(fn + ": bodyexclude " + std::to_string(cfg->bodyexclude) + " out of range (-1, or 0 .. " + std::to_string(m->nbody - 1) + ")");
+  if (!(cfg->cutoff >= 0)) return fail(fn + ": cutoff must be >= 0 (0 or +inf: none) and not NaN");
+  if (terrain) {
+    const fb_terrain& t = *terrain;
+    if (!t.data) return fail(fn + ": terrain data is NULL");
+    if (t.nrow < 2 || t.ncol < 2 || t.nrow > FB_RAY_MAXGRID || t.ncol > FB_RAY_MAXGRID) return fail(fn + ": terrain nrow and ncol must be 2 .. " + std::to_string(FB_RAY_MAXGRID));
+    if (t.n_terrain < 1) return fail(fn + ": n_terrain must be >= 1");
+    for (int k = 0; k < 4; k++) if (!std::isfinite(t.size[k])) return fail(fn + ": terrain size must be finite");
+    for (int k = 0; k < 3; k++) if (!std::isfinite(t.pos[k])) return fail(fn + ": terrain pos must be finite");
+    if (!(t.size[0] > 0) || !(t.size[1] > 0) || t.size[2] < 0 || t.size[3] < 0) return fail(fn + ": terrain size must be (rx > 0, ry > 0, elevation_z >= 0, base_z >= 0)");
+    if (t.terrain_ids) for (int k = 0; k < nf; k++) if (t.terrain_ids[k] < 0 || t.terrain_ids[k] >= t.n_terrain)
+      return fail(fn + ": terrain id " + std::to_string(t.terrain_ids[k]) + " out of range (frame " + std::to_string(k) + ")");
+  }
+  FB_GUARD_BEGIN
+  HIPCHK(hipSetDevice(b->device));
+  hipStream_t st = (hipStream_t)stream;
+  // the call's tables: [visible geoms | frame -> environment | frame -> terrain]
+  const int* gbody = m->i("geom_bodyid");
+  std::vector<int>& tab = b->ray_tab_host;
+  tab.clear();
+  for (int g = 0; g < m->ngeom; g++) if ((!cfg->geom_mask || cfg->geom_mask[g]) && (cfg->bodyexclude < 0 || gbody[g] != cfg->bodyexclude)) tab.push_back(g);
+  const int n_vis = (int)tab.size();
+  for (int k = 0; k < nf; k++) tab.push_back(cfg->env_ids ? cfg->env_ids[k] : k);
+  const bool tids = terrain && terrain->terrain_ids;
+  if (tids) tab.insert(tab.end(), terrain->terrain_ids, terrain->terrain_ids + nf);
+  if (b->ray_tab.count() < tab.size()) {
+    HIPCHK(hipDeviceSynchronize());                    // (an earlier call may still read the block)
+    if (b->ray_tab.reserve(tab.size() + 256)) return -1;
+  }
+  HIPCHK(hipMemcpyAsync(b->ray_tab.get(), tab.data(), tab.size()*sizeof(int), hipMemcpyHostToDevice, st));
+  with_model(b, [&](auto& M) {
+    using real = decltype(M.timestep);
+    RayArgs<real> A;
+    A.rarena = (const real*)b->rarena.get(); A.nreal = b->off.nreal;
+    A.o_gxpos = b->off.gxpos; A.o_gxmat = b->off.gxmat; A.o_xpos = b->off.xpos; A.o_xquat = b->off.xquat;
+    A.geom_size = M.geom_size; A.geom_rbound = M.geom_rbound; A.geom_type = M.geom_type;
+    A.vis = b->ray_tab.get(); A.n_vis = n_vis; A.frame_env = A.vis + n_vis; A.frame_terrain = tids ? A.frame_env + nf : nullptr;
+    A.rays = rays; A.dist = dist; A.geomid = (int*)geomid;
+    A.n_frames = nf; A.n_ray = nr; A.per_frame = cfg->per_frame; A.body = cfg->body; A.ngeom = m->ngeom; A.tiles = (int)tiles;
+    A.cutoff = cfg->cutoff > 0 ? (real)cfg->cutoff : (real)INFINITY;
+    A.hdata = terrain ? terrain->data : nullptr; A.nrow = terrain ? terrain->nrow : 2; A.ncol = terrain ? terrain->ncol : 2;
+    A.rx = terrain ? (real)terrain->size[0] : 1; A.ry = terrain ? (real)terrain->size[1] : 1;
+    A.elev = terrain ? (real)terrain->size[2] : 0; A.base = terrain ? (real)terrain->size[3] : 0;
+    for (int k = 0; k < 3; k++) A.tpos[k] = terrain ? (real)terrain->pos[k] : 0;
+    hipLaunchKernelGGL((k_raycast<real>), dim3((unsigned)(tiles*nf)), dim3(FB_RAY_THREADS), 0, st, A);
+    return 0;
+  });
   HIPCHK(hipGetLastError());
   return 0;
   FB_GUARD_END

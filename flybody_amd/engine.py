@@ -84,6 +84,10 @@ Feedback = collections.namedtuple('Feedback', ['x_nom', 'u_nom', 'K', 'k', 'alph
 # not positive definite); in stationary mode the time axes are 1 (K, k) and 2 (P, p)
 LQRBackward = collections.namedtuple('LQRBackward', ['K', 'k', 'P', 'p', 'dV', 'status'])
 
+# Batch.cast_rays: dist float32 [n_frames, n_ray], in units of |dir| (-1: a miss), and geomid int32 [n_frames, n_ray] (-1: a miss; ngeom: the
+# terrain)
+RayResult = collections.namedtuple('RayResult', ['dist', 'geomid'])
+
 _libs: Dict[str, C.CDLL] = {}
 
 
@@ -162,6 +166,8 @@ def load_library(lib_path: Optional[str] = None) -> C.CDLL:
     if hasattr(L, 'fb_batch_lqr_backward'):
         L.fb_batch_lqr_backward.argtypes = [C.c_void_p]*17
         L.fb_riccati_gemm.argtypes = [C.c_void_p] + [C.c_int]*5 + [C.c_void_p]*5
+    if hasattr(L, 'fb_batch_ray'):
+        L.fb_batch_ray.argtypes = [C.c_void_p]*7
     _libs[path] = L
     return L
 
@@ -236,7 +242,7 @@ def helper_batches(model: 'Model', n: int, batch_size: int, device: int = 0, row
 
 
 class _DeviceCall:
-    """The surroundings of one torch-facing device call of a batch (transition_fd, rollout, rollout_feedback, lqr_backward, riccati_gemm):
+    """The surroundings of one torch-facing device call of a batch (transition_fd, rollout, rollout_feedback, lqr_backward, riccati_gemm, cast_rays):
     `device`, the torch.device the batch computes on -- the CPU for the kernel-emulation build (`emulated`), whose "device" memory is host
     memory --; `stream`, the handle the C call gets: the caller's, else torch's current stream of that device (None when emulated); and
     the call's outputs and temporaries, made in that stream's order: zero-filled before the kernel writes them and freed behind it.  A
@@ -317,6 +323,18 @@ class _Feedback(C.Structure):
 class _LQRConfig(C.Structure):
     """fb_lqr_config (include/flybody_engine.h)."""
     _fields_ = [('n_nom', C.c_int32), ('horizon', C.c_int32), ('ndx', C.c_int32), ('nu', C.c_int32), ('stationary', C.c_int32)]
+
+
+class _Terrain(C.Structure):
+    """fb_terrain (include/flybody_engine.h)."""
+    _fields_ = [('nrow', C.c_int32), ('ncol', C.c_int32), ('n_terrain', C.c_int32), ('size', C.c_double*4), ('pos', C.c_double*3),
+                ('data', C.c_void_p), ('terrain_ids', C.c_void_p)]
+
+
+class _RayConfig(C.Structure):
+    """fb_ray_config (include/flybody_engine.h)."""
+    _fields_ = [('n_frames', C.c_int32), ('n_ray', C.c_int32), ('per_frame', C.c_int32), ('env_ids', C.c_void_p), ('body', C.c_int32),
+                ('bodyexclude', C.c_int32), ('geom_mask', C.c_void_p), ('cutoff', C.c_double)]
 
 
 class Model:
@@ -674,6 +692,50 @@ class Batch:
         Cm = call.empty(m, n)
         _check(self.L, self.L.fb_riccati_gemm(self.h, int(m), int(n), int(k), int(trans_x), int(trans_y), _ptr(X), _ptr(Y), _ptr(D), _ptr(Cm), call.stream))
         return Cm
+
+    def cast_rays(self, rays, body: int = -1, env_ids=None, geom_mask=None, bodyexclude: int = -1, cutoff: Optional[float] = None,
+                  terrain=None, terrain_ids=None, stream=None) -> 'RayResult':
+        """Rays against the geoms of live environments as the last step, reset or forward() left them, and against an optional
+        vision.Terrain (fb_batch_ray, MuJoCo's mj_ray / mj_multiRay; the semantics are the header's).  rays: float64 [n_ray, 6] -- one
+        set for every frame -- or [n_frames, n_ray, 6], rows (origin, dir), a torch tensor on the batch's device (anything else is
+        copied there); dir need not be unit length.  A frame is the environment env_ids[f] (None: frame f is environment f; one
+        shared ray set is cast in every environment); repeats are allowed.  body: the rays are given in this body's frame (-1: the
+        world's).  geom_mask [ngeom]: False / 0 hides a geom; bodyexclude: a body whose geoms are skipped.  cutoff: hits beyond it are
+        misses (None: no limit).  terrain_ids [n_frames]: which of the terrain's grids a frame sees (None: grid 0).  Returns
+        RayResult(dist float32 [n_frames, n_ray] in units of |dir|, -1 for a miss; geomid int32, -1 for a miss, ngeom for the terrain).
+        Both precisions; the environments are only read.  Asynchronous on `stream` (None: torch's current stream of the device)."""
+        import torch
+        call = _DeviceCall(self, stream)
+        if not (isinstance(rays, torch.Tensor) and rays.dtype == torch.float64 and rays.device == call.device and rays.is_contiguous()):
+            rays = call._ordered(lambda: torch.as_tensor(np.asarray(rays, np.float64) if not isinstance(rays, torch.Tensor) else rays,
+                                                         dtype=torch.float64, device=call.device).contiguous())
+        if rays.dim() not in (2, 3) or rays.shape[-1] != 6 or min(rays.shape) < 1:
+            raise ValueError('rays must be [n_ray, 6] or [n_frames, n_ray, 6]: rows (origin, dir)')
+        ids = as_env_ids(env_ids)
+        per_frame = rays.dim() == 3
+        n_frames = int(rays.shape[0]) if per_frame else (len(ids) if ids is not None else self.n_env)
+        if ids is not None and len(ids) != n_frames:
+            raise ValueError(f'env_ids names {len(ids)} environments for {n_frames} frames of rays')
+        n_ray = int(rays.shape[-2])
+        mask = None if geom_mask is None else np.ascontiguousarray(np.asarray(geom_mask).astype(bool), np.uint8).reshape(-1)
+        if mask is not None and len(mask) != self.model.dim('ngeom'):
+            raise ValueError(f'geom_mask must be [{self.model.dim("ngeom")}]')
+        ter = tids = None
+        if terrain is not None:
+            if terrain.heights.device != call.device:
+                raise ValueError(f'the terrain lives on {terrain.heights.device}, the batch computes on {call.device}')
+            tids = as_env_ids(terrain_ids)
+            if tids is not None and len(tids) != n_frames:
+                raise ValueError(f'terrain_ids names {len(tids)} terrains for {n_frames} frames')
+            ter = _Terrain(terrain.nrow, terrain.ncol, terrain.n_terrain, (C.c_double*4)(*terrain.size), (C.c_double*3)(*terrain.pos),
+                           terrain.heights.data_ptr(), None if tids is None else tids.ctypes.data)
+        elif terrain_ids is not None:
+            raise ValueError('terrain_ids without a terrain')
+        dist, gid = call.empty(n_frames, n_ray, dtype=torch.float32), call.empty(n_frames, n_ray, dtype=torch.int32)
+        cfg = _RayConfig(n_frames, n_ray, int(per_frame), None if ids is None else ids.ctypes.data, int(body), int(bodyexclude),
+                         None if mask is None else mask.ctypes.data, 0.0 if cutoff is None else float(cutoff))
+        _check(self.L, self.L.fb_batch_ray(self.h, C.byref(cfg), _ptr(rays), None if ter is None else C.byref(ter), _ptr(dist), _ptr(gid), call.stream))
+        return RayResult(dist, gid)
 
     def rollouts_run(self) -> int:
         """Rollouts the last rollout / rollout_feedback call finished (fb_batch_rollouts_run; synchronises the device)."""

@@ -211,6 +211,7 @@ class BatchedFlyEnv:
         self.random_state = random_state if random_state is not None else np.random.RandomState(seed)
         self._force_views = None; self._law_views = None; self._end_args = None; self._state_views = None
         self._model_view = None; self._model_gen = None; self._seed = seed
+        self._eye_cache = {}                                  # eye_depth: (size, fovy, see_body) -> (rays on the device, head body, geom mask)
         if (env_model is not None or resample_on_reset) and models is None:
             raise ValueError('env_model / resample_on_reset need models=[...]')
         self.resample_on_reset = bool(resample_on_reset)
@@ -442,6 +443,37 @@ class BatchedFlyEnv:
             raise ValueError(f'alpha must be [{ne}, {K}]: one step length per sample of every listed environment')
         return self._per_sample(ids, K, self.batch.rollout_feedback, fbk.x_nom, fbk.u_nom, fbk.K, fbk.k,
                                 None if fbk.alpha is None else fbk.alpha.reshape(ne*K), nom_ids=np.repeat(np.arange(ne, dtype=np.int32), K), **kw)
+
+    # ---- ray casting (flybody_amd.vision, csrc/fb_ray.hpp) --------------------------------------
+    def cast_rays(self, rays, **kw):
+        """Rays against the live environments' geoms and an optional vision.Terrain, between two control steps and without disturbing
+        them: engine.RayResult(dist, geomid) as torch tensors on the device (Batch.cast_rays: body, env_ids, geom_mask, bodyexclude,
+        cutoff, terrain, terrain_ids, stream).  Range sensors, height above terrain, depth images."""
+        return self.batch.cast_rays(rays, **kw)
+
+    def eye_depth(self, size: int = 32, fovy: float = 150.0, terrain=None, terrain_ids=None, cutoff: Optional[float] = None,
+                  see_body: bool = False):
+        """Depth images of the fly's two eye cameras (vision.EYES, on the `head` body; the vision task's fovy 150 and 32 x 32 pixels):
+        float32 [n_env, 2, size, size] on the device, in the order eye_right, eye_left, row 0 at the top; the distance along each
+        pixel's ray, -1 where it meets nothing (or nothing within `cutoff`).  Both eye origins lie inside the head's collision geoms,
+        so by default every geom of the fly is hidden and the eyes see the floor, other bodies and the terrain; see_body=True hides
+        only the head's own geoms.  terrain_ids [n_env]: the grid of every environment (None: grid 0)."""
+        from . import vision
+        a = self.model.arrays
+        # (the mask and the head's id come from names_body / geom_bodyid / body_rootid: integer tables, which every model of a group shares with
+        #  the first one -- fb_batch_create_group refuses anything else -- so env_model() and resampling cannot invalidate the cache)
+        key = (int(size), float(fovy), bool(see_body))
+        cache = self._eye_cache
+        if key not in cache:
+            import torch
+            names = [str(n) for n in a['names_body']]
+            head, gbody, root = names.index('head'), np.asarray(a['geom_bodyid']), np.asarray(a['body_rootid'])
+            hidden = (gbody == head) if see_body else (root[gbody] == root[head])
+            rays = np.concatenate([vision.camera_rays(fovy, size, size, pos, quat) for pos, quat in vision.EYES.values()])
+            cache[key] = (torch.from_numpy(rays).to(self.batch._torch_device()), head, ~hidden)
+        rays, head, mask = cache[key]
+        r = self.batch.cast_rays(rays, body=head, geom_mask=mask, cutoff=cutoff, terrain=terrain, terrain_ids=terrain_ids)
+        return r.dist.reshape(self.n_env, 2, int(size), int(size))
 
     # ---- the parts of a control step around the kernel ------------------------------------------
     @property

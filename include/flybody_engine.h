@@ -442,6 +442,53 @@ int fb_batch_lqr_backward(fb_batch* b, const fb_lqr_config* cfg,
 int fb_riccati_gemm(fb_batch* b, int m, int n, int k, int trans_x, int trans_y,
                     const double* X, const double* Y, const double* D, double* C, void* stream);
 
+/* Batched ray casting: MuJoCo's mj_ray / mj_multiRay and the rangefinder sensor, for n_ray rays in each of n_frames frames.  A frame is
+ * a live environment (env_ids); the rays meet the model's geoms where the last control step, reset or fb_batch_forward left them
+ * (FB_GEOM_XPOS / FB_GEOM_XMAT) and, optionally, a caller-supplied height field.  The environments are only read: nothing a later step
+ * reads changes.
+ * A RAY is (origin[3], dir[3]); dir need not be unit length.  The result is the smallest x >= 0 with origin + x dir on the boundary of a
+ * visible object -- mj_ray's convention, distance in units of |dir| -- so an origin INSIDE a closed geom reports the exit point.  A miss
+ * is dist = -1, geomid = -1.  A hit with x > cutoff is a miss (cutoff > 0 in the same units; +inf or 0: none).  A zero or non-finite ray
+ * is a miss, and so is one whose |dir|^2 underflows or overflows at the batch's precision or whose distance does not fit float32.  With body >= 0 the rays are given in that body's frame (FB_XPOS / FB_XQUAT of the frame's environment), else in the world's.
+ * GEOMS.  Plane: hit only from its front (the direction's local z < 0), and only where the hit point lies within +-size[0], +-size[1]
+ * wherever that size is > 0 (the fly's floor is 8 x 8, finite).  Sphere, ellipsoid: the quadratic in the geom's frame.  Capsule: the
+ * cylinder side between the cap centres plus the two half spheres.  Cylinder: the side plus the two discs.
+ * VISIBILITY.  geom_mask: optional bytes [ngeom], 0 hides the geom.  bodyexclude: -1, or a body whose geoms are skipped.
+ * TERRAIN, as MuJoCo's hfield asset: nrow x ncol float32 samples in [0, 1], row <-> y, column <-> x; size = (rx, ry, elevation_z, base_z)
+ * and a world position pos (no rotation).  Sample (r, c) sits at x = -rx + 2 rx c / (ncol - 1), y = -ry + 2 ry r / (nrow - 1) with height
+ * elevation_z * data[r][c]; every cell is split into the triangles (v00, v11, v10) and (v00, v11, v01): the diagonal joins (r, c) to
+ * (r + 1, c + 1).  The terrain is the SOLID {|x| <= rx, |y| <= ry, -base_z <= z <= h(x, y)}; the ray reports the first crossing of its
+ * boundary -- surface, side walls or bottom -- and from inside the exit.  A terrain hit has geomid = ngeom.  There may be n_terrain grids
+ * of one shape, with a terrain index per frame (terrain_ids): per-episode terrain without a re-upload.  Between geoms and terrain the
+ * nearest hit wins.  Samples outside [0, 1] are the caller's error: results are then wrong, nothing faults.
+ * Both precisions: the arithmetic runs at the batch's.  Works with applied forces or a control law set (it only reads poses).
+ * Refused, with the reason in fb_last_error(): a null batch, cfg, rays, dist or geomid; a grouped batch of more than one model; n_frames or
+ * n_ray < 1, or more than 2^23 workgroups of 1024 rays; per_frame not 0 or 1; an environment id, body, bodyexclude or terrain id out of
+ * range; a terrain with null data, nrow or ncol outside 2 .. 4096, n_terrain < 1, rx or ry not > 0, elevation_z or base_z < 0, or a
+ * non-finite size or pos; a negative or NaN cutoff.
+ * Asynchronous on `stream` after validation; the only uploads are the small host arrays (env_ids, terrain_ids, the visible geoms), into
+ * ONE block of the batch that every call rewrites: the calls on one batch must be stream-ordered (one stream, or events between them),
+ * as those of fb_batch_transition_fd and fb_batch_rollout must. */
+typedef struct fb_terrain {
+  int32_t nrow, ncol, n_terrain;          /* nrow, ncol in 2 .. 4096 */
+  double size[4], pos[3];
+  const float* data;                      /* DEVICE [n_terrain][nrow][ncol] */
+  const int32_t* terrain_ids;             /* HOST [n_frames], NULL: 0 */
+} fb_terrain;
+typedef struct fb_ray_config {
+  int32_t n_frames, n_ray;
+  int32_t per_frame;                      /* 0: rays [n_ray][6], shared by the frames; 1: rays [n_frames][n_ray][6] */
+  const int32_t* env_ids;                 /* HOST [n_frames], NULL: 0 .. n_frames-1; repeats allowed */
+  int32_t body;                           /* -1: world frame; else the rays are given in this body's frame */
+  int32_t bodyexclude;                    /* -1, or the body whose geoms are invisible */
+  const uint8_t* geom_mask;               /* HOST [ngeom] or NULL */
+  double cutoff;
+} fb_ray_config;
+int fb_batch_ray(fb_batch* b, const fb_ray_config* cfg, const double* rays /* DEVICE */,
+                 const fb_terrain* terrain /* NULL: none */,
+                 float* dist /* DEVICE [n_frames][n_ray] */,
+                 int32_t* geomid /* DEVICE [n_frames][n_ray] */, void* stream);
+
 /* External forces (FB_QFRC_APPLIED, FB_XFRC_APPLIED), MuJoCo's two user inputs for everything that is not an actuator, a contact or the
  * fluid model.  Every substep
  *     qfrc_smooth = qfrc_passive - qfrc_bias + qfrc_actuator + qfrc_applied + sum_b J_b(xipos_b)' xfrc_applied_b
