@@ -629,6 +629,7 @@ static int build_devmodel(fb_batch* b, const fb_model* m, const Switches& sw, De
   M.nlevel = m->nlevel; M.ntrunk = m->ntrunk; M.prefix_split = m->prefix_split; M.chmax = m->chmax; M.fk_dmax = m->fk_dmax; M.fk2_dlo = m->fk2_dlo;
   M.task = m->task_id; M.user_idx = m->i("user_action_idx")[0]; M.nact = m->nu + (M.user_idx >= 0 ? 1 : 0);
   M.timestep = (real)m->d("opt_timestep")[0]; M.control_timestep = (real)m->d("opt_control_timestep")[0];
+  M.clock_timestep = m->d("opt_timestep")[0]; M.clock_control_timestep = m->d("opt_control_timestep")[0];
   for (int k = 0; k < 3; k++) { M.grav[k] = (real)m->d("opt_gravity")[k]; M.com_offset[k] = (real)m->d("com_offset")[k]; }
   M.density = (real)m->d("opt_density")[0]; M.viscosity = (real)m->d("opt_viscosity")[0]; M.impratio = (real)m->d("opt_impratio")[0]; M.tolerance = (real)m->d("opt_tolerance")[0];
   M.noslip_tolerance = (real)m->d("opt_noslip_tolerance")[0]; M.meaninertia = (real)m->d("stat_meaninertia")[0]; M.totalmass = (real)m->totalmass;
@@ -832,7 +833,7 @@ extern "C" int fb_batch_set_reference(fb_batch* b, const double* ref_qpos, const
     if (alloc_obs(b, obs_width(m, m->task_id == FB_TASK_TEMPLATE ? 0 : future_steps + 1, false))) return -1;      // (template_task: the reference is the start pose only, no reference observables)
     M.ref_qpos = (const real*)b->ref_qpos.get(); M.ref_qvel = (const real*)b->ref_qvel.get(); M.T = T;
     M.future_steps = future_steps; M.episode_steps = episode_steps; M.nobs = b->nobs;
-    M.terminal_com_dist = (real)terminal_com_dist; M.time_limit = (real)time_limit;
+    M.terminal_com_dist = (real)terminal_com_dist; M.time_limit = time_limit;
     b->have_ref = true;
     return 0;
   });
@@ -846,7 +847,7 @@ extern "C" int fb_batch_set_time_limit(fb_batch* b, double time_limit) {
   if (alloc_obs(b, obs_width(m, 0, true))) return -1;
   return with_model(b, [&](auto& M) {
     using real = decltype(M.timestep);
-    M.nobs = b->nobs; M.T = 0; M.future_steps = 0; M.episode_steps = 0; M.time_limit = (real)time_limit;
+    M.nobs = b->nobs; M.T = 0; M.future_steps = 0; M.episode_steps = 0; M.time_limit = time_limit;
     M.terminal_com_dist = (real)1e30;
     b->have_ref = true;
     return 0;
@@ -897,7 +898,7 @@ extern "C" int fb_batch_set_walk_dataset(fb_batch* b, const fb_walk_dataset* ds)
     M.ds_qpos = q_; M.ds_qvel = v_; M.ds_r2s = r_; M.ds_jq = j_; M.ds_offset = o_; M.ds_jid = ji_; M.ds_sid = si_; M.ds_select = se_;
     M.ds_nj = nj; M.ds_ns = ns; M.ds_ntraj = ds->n_traj; M.ds_nselect = ds->n_select; M.ds_env_base = ds->env_id_base; M.max_episode_steps = max_steps;
     M.seed = ds->seed; M.future_steps = future_steps; M.nobs = b->nobs; M.T = 0; M.episode_steps = 0;
-    M.terminal_com_dist = (real)ds->terminal_com_dist; M.time_limit = (real)ds->time_limit;
+    M.terminal_com_dist = (real)ds->terminal_com_dist; M.time_limit = ds->time_limit;
     b->have_ref = true;
     return 0;
   });
@@ -927,7 +928,7 @@ extern "C" int fb_batch_set_flight_dataset(fb_batch* b, const fb_flight_dataset*
     M.ds_qpos = q_; M.ds_qvel = v_; M.ds_offset = o_; M.ds_select = se_; M.ds_nj = 0; M.ds_ns = 0; M.ds_ntraj = ds->n_traj;
     M.ds_nselect = ds->n_select; M.ds_env_base = ds->env_id_base; M.ds_random_start = ds->randomize_start_step ? 1 : 0;
     M.seed = ds->seed; M.future_steps = future_steps; M.nobs = b->nobs; M.T = 0; M.episode_steps = 0;
-    M.terminal_com_dist = (real)ds->terminal_com_dist; M.time_limit = (real)ds->time_limit;
+    M.terminal_com_dist = (real)ds->terminal_com_dist; M.time_limit = ds->time_limit;
     b->have_ref = true;
     return 0;
   });
@@ -1591,7 +1592,7 @@ extern "C" int fb_batch_ray(fb_batch* b, const fb_ray_config* cfg, const double*
 }
 
 // ------------------------------------------------------------------ field access
-enum FieldKind { REAL_ARENA, INT_ARENA, F32_ARRAY, I32_ARRAY, F64_ARRAY, REAL_ARRAY /* caller-owned input at the batch's precision: the applied forces */ };
+enum FieldKind { REAL_ARENA, F64_ARENA /* doubles in the real arena at either precision: the episode clock */, INT_ARENA, F32_ARRAY, I32_ARRAY, F64_ARRAY, REAL_ARRAY /* caller-owned input at the batch's precision: the applied forces */ };
 // rows of `width` at offset `off` of an arena row, or an array [n_env][width] of its own at `base`; `unset`: why such an array is not
 // allocated yet (the ones allocated with the batch need none)
 struct FieldDesc { FieldKind kind; size_t off, width; void* base = nullptr; const char* unset = nullptr; };
@@ -1620,6 +1621,7 @@ static int field_desc(fb_batch* b, int field, FieldDesc* f) {
     case FB_QFRC_ACTUATOR: *f = {REAL_ARENA, o.qfrc_actuator, (size_t)m->nv}; break;
     case FB_QFRC_CONSTRAINT: *f = {REAL_ARENA, o.qfrc_constraint, (size_t)m->nv}; break;
     case FB_SUBTREE_COM: *f = {REAL_ARENA, o.com, 3}; break;
+    case FB_TIME: *f = {F64_ARENA, o.simtime, 1}; break;
     case FB_NCON: *f = {INT_ARENA, o.istate + IS_NCON, 1}; break;
     case FB_NEFC: *f = {INT_ARENA, o.istate + IS_NEFC, 1}; break;
     case FB_SOLVER_NITER: *f = {INT_ARENA, o.istate + IS_NITER, 1}; break;
@@ -1803,6 +1805,10 @@ extern "C" int fb_batch_get(fb_batch* b, int field, void* dst, size_t bytes) {
   if (f.kind == REAL_ARENA) {
     if (bytes != (size_t)n*f.width*sizeof(double)) return fail("fb_batch_get: size mismatch (physics fields are returned as FP64)");
     return real_rows(b, f, (double*)dst, false);
+  } else if (f.kind == F64_ARENA) {
+    if (bytes != (size_t)n*f.width*sizeof(double)) return fail("fb_batch_get: size mismatch");
+    const size_t rs = real_size(b);
+    HIPCHK(hipMemcpy2D(dst, f.width*8, (char*)b->rarena.get() + f.off*rs, (size_t)b->off.nreal*rs, f.width*8, n, hipMemcpyDeviceToHost));
   } else if (f.kind == INT_ARENA) {
     if (bytes != (size_t)n*f.width*sizeof(int)) return fail("fb_batch_get: size mismatch");
     HIPCHK(hipMemcpy2D(dst, f.width*4, (char*)b->iarena.get() + f.off*4, (size_t)b->off.nint*4, f.width*4, n, hipMemcpyDeviceToHost));
@@ -1833,6 +1839,10 @@ extern "C" int fb_batch_set(fb_batch* b, int field, const void* src, size_t byte
   if (f.kind == REAL_ARENA) {
     if (bytes != (size_t)n*f.width*sizeof(double)) return fail("fb_batch_set: size mismatch (physics fields are passed as FP64)");
     return real_rows(b, f, (double*)src, true);
+  } else if (f.kind == F64_ARENA) {
+    if (bytes != (size_t)n*f.width*sizeof(double)) return fail("fb_batch_set: size mismatch");
+    const size_t rs = real_size(b);
+    HIPCHK(hipMemcpy2D((char*)b->rarena.get() + f.off*rs, (size_t)b->off.nreal*rs, src, f.width*8, f.width*8, n, hipMemcpyHostToDevice));
   } else if (f.kind == INT_ARENA) {
     if (bytes != (size_t)n*f.width*sizeof(int)) return fail("fb_batch_set: size mismatch");
     HIPCHK(hipMemcpy2D((char*)b->iarena.get() + f.off*4, (size_t)b->off.nint*4, src, f.width*4, f.width*4, n, hipMemcpyHostToDevice));

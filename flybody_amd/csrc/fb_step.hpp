@@ -339,7 +339,7 @@ __device__ __forceinline__ void d_integrate(const DevModel<real>& M, const WS<re
       } else w.qpos()[qa_] = qv[u][0] + h*vv[u][0];
     }
   }
-  if (lane == 0) w.simtime()[0] += h;
+  if (lane == 0) sim_clock(w) += M.clock_timestep;
   SYNC();
 }
 

@@ -7,6 +7,17 @@
 #include "fb_math.hpp"
 #include "fb_smooth.hpp"      // SYNC
 
+// ------------------------------------------------------------------ the episode clock
+// MuJoCo's d->time: a double that every substep advances by the model's timestep -- at EITHER precision.  The clock decides, it does not
+// enter the physics: which dataset frame the reward is scored against and whether the trajectory has ended (clock_step), and the time
+// limit (d_post_end).  Kept in `real` an FP32 build decided differently from FP64 and MuJoCo: its sum of 2e-4 falls half a control step
+// behind after 5.4 s, so that walk_imitation scored the reward against the previous frame on 2285 of an episode's 5000 steps, and three of
+// the four tasks ended their time-limited episodes one step off.  The slot (simtime) is two reals wide and starts its own cache line, so
+// the double is aligned in the FP32 arena too; field FB_TIME reads and writes it.
+template <typename real> FBD double& sim_clock(const WS<real>& w) { return *(double*)w.simtime(); }
+// the control step the clock stands at (the reference's round(time / control_timestep))
+template <typename real> FBD int clock_step(const DevModel<real>& M, const WS<real>& w) { return (int)floor(sim_clock(w) / M.clock_control_timestep + 0.5); }
+
 // ------------------------------------------------------------------ reference trajectory of an environment
 // inference mode: one root track shared by all environments (fb_batch_set_reference); training mode: the snippet the
 // environment picked from the dataset at episode start, shifted to start at x = y = 0 (trajectory_loaders.py:249)
@@ -130,7 +141,7 @@ template <typename real> FBD void d_retract(const DevModel<real>& M, const WS<re
   for (int k = lane; k < n; k += FB_WAVE) { int qa = M.jnt_qposadr[jnt[k]]; w.qpos()[qa] = M.qpos_spring[qa]; }
 }
 template <typename real> FBD void d_reset_counters(const WS<real>& w, int lane) {
-  if (lane == 0) { w.istate()[IS_STEP] = 0; w.istate()[IS_RESET_NEXT] = 0; w.simtime()[0] = 0; }
+  if (lane == 0) { w.istate()[IS_STEP] = 0; w.istate()[IS_RESET_NEXT] = 0; sim_clock(w) = 0; }
 }
 // a walker's episode starts (qpos is set): at rest, wings folded (fruitfly.py:390-405)
 template <typename real> FBD void d_start_walker(const DevModel<real>& M, const WS<real>& w, int lane) {
@@ -170,7 +181,7 @@ template <typename real> struct Outcome { real reward; bool term, traj_end; };
 // observation shows the sensors themselves, not their means; reward 0, discount 1, and IS_RESET_NEXT is the caller's business.
 template <typename real> FBD void d_post_end(const DevModel<real>& M, const WS<real>& w, bool first, const Outcome<real>& out,
                     float* obs, float* reward, float* discount, int* step_type, int lane) {
-  const bool terminating = out.term || (w.simtime()[0] >= M.time_limit);
+  const bool terminating = out.term || (sim_clock(w) >= M.time_limit);
   const int type = first ? 0 : (terminating ? 2 : 1);
   d_pack_obs(M, w, first ? w.sens() : w.sens_acc(), obs, lane);
   if (lane == 0) {
@@ -250,8 +261,8 @@ template <typename real> FBD real d_walk_training_reward(const DevModel<real>& M
   for (int k = lane; k < ns; k += FB_WAVE) {
     real df[3], ego[3];
     sub3(df, w.sxpos() + 3*M.ds_sid[k], w.qpos());
-    rotvecquat(ego, df, qinv);
-    for (int c = 0; c < 3; c++) { real e = ego[c] - r2s[3*k + c]; d_site += e*e; }
+    rotvecquat(ego, df, qinv);                                   // (quat2mat of a quaternion of norm^2 1/n2 is a rotation times 1/n2: undone below, get_egocentric_vec rotates whatever the norm)
+    for (int c = 0; c < 3; c++) { real e = ego[c]*n2 - r2s[3*k + c]; d_site += e*e; }
   }
   d_com = wave_sum(d_com); d_qvel = wave_sum(d_qvel); d_site = wave_sum(d_site); d_quat = wave_sum(d_quat);
   const real s_com = (real)0.078487, s_qvel = (real)53.7801, s_site = (real)0.0735, s_quat = (real)1.2247;     // tasks/rewards.py:101-108
@@ -266,7 +277,7 @@ template <typename real> FBD real d_walk_training_reward(const DevModel<real>& M
 // reward / termination (walk_imitation.py:152-203)
 template <typename real> FBD Outcome<real> d_walk_post(const DevModel<real>& M, const WS<real>& w, const PostHead<real>& h, int lane) {
   real linvel = norm3(w.sens() + 6), angvel = norm3(w.sens() + 3);
-  int tstep = (int)floor(w.simtime()[0] / M.control_timestep + (real)0.5);
+  int tstep = clock_step(M, w);
   const RefView<real> rv = ref_view(M, w);
   real rroot[7]; ref_root(rv, h.prev + 1, rroot);
   real dif[3]; sub3(dif, rroot, w.qpos());
@@ -318,7 +329,7 @@ template <typename real> FBD void d_flight_init(const DevModel<real>& M, const W
       double u2 = (double)hash_uniform(M.seed ^ 0x5bd1e995u, (unsigned)(M.ds_env_base + env), (unsigned)episode);
       start = (int)(u2*(s.len - 50)); if (start > s.len - 51) start = s.len - 51; if (start < 0) start = 0;
     }
-    int T = s.len - start, lim = (int)floor(M.time_limit / M.control_timestep + (real)0.5);
+    int T = s.len - start, lim = (int)floor(M.time_limit / M.clock_control_timestep + 0.5);
     const real* q0 = M.ds_qpos + (size_t)(s.off + start)*7;
     if (lane == 0) {
       w.istate()[IS_DS_OFF] = s.off + start; w.istate()[IS_DS_LEN] = T;
@@ -409,7 +420,7 @@ template <typename real> FBD Outcome<real> d_flight_post(const DevModel<real>& M
   int thorax = M.site_bodyid[M.site_thorax];
   real height = w.xpos()[3*thorax + 2];
   real cd[3]; sub3(cd, rnext, w.qpos());
-  int tstep = (int)floor(w.simtime()[0] / M.control_timestep + (real)0.5);
+  int tstep = clock_step(M, w);
   bool traj_end = (tstep == rview.episode_steps);
   // enabled legs: reward for keeping them retracted (flight_imitation.py:196-203; 1 when the legs are disabled)
   real r_legs = 1;

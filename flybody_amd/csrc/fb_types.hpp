@@ -88,7 +88,7 @@ template <typename T> struct GP {
 // Per-environment real arrays: X(name, element count expression in terms of DevModel M)
 #define FB_WS_REAL(X) \
   X(qpos, M.nq) X(qvel, M.nv) X(act, M.na + 1) X(ctrl, M.nu) X(qacc, M.nv) X(qacc_ws, M.nv) X(act_dot, M.na + 1) \
-  X(sens, FB_NSENS) X(sens_acc, FB_NSENS) X(simtime, 1) X(wbfreq, 1) X(dsshift, 2) X(rfac, 6) \
+  X(sens, FB_NSENS) X(sens_acc, FB_NSENS) X(simtime, 2) /* ONE double at either precision (fb_task.hpp: sim_clock) */ X(wbfreq, 1) X(dsshift, 2) X(rfac, 6) \
   X(xpos, 3*M.nbody) X(xquat, 4*M.nbody) /* rotation matrices, inertial frames, joint anchors: LDS / registers only (fb_smooth.hpp) */ \
   X(xaxis, 3*M.njnt) /* walk_imitation training reward only */ X(gxpos, 3*M.ngeom) X(gxmat, 9*M.ngeom) X(sxpos, 3*M.nsite) X(sxmat, 9*M.nsite) X(com, 4) \
   X(cinert, 10*M.nbody) X(cdof, 6*M.nv) X(cvel, 6*M.nbody) \
@@ -183,7 +183,10 @@ struct DevModel {
   // env-level (walk_imitation)
   GP<const real> ref_qpos, ref_qvel;
   int T, future_steps, episode_steps, nobs;
-  real terminal_com_dist, time_limit;
+  real terminal_com_dist;
+  // The episode clock and what it is compared with are doubles at either precision, as MuJoCo's d->time is: an FP32 sum of 2e-4 drifts
+  // by a control step's worth of frames within 5.4 s and ends time-limited episodes a step off (fb_task.hpp: sim_clock)
+  double clock_timestep, clock_control_timestep, time_limit;
   // task: FB_TASK_*.  flight_imitation: action layout, CoM offset, wing-beat pattern generator tables
   int task, nact, user_idx; unsigned seed;
   GP<const int> wing_act_idx, body_fluid_geom;

@@ -41,7 +41,7 @@ FIELDS = dict(
     STEP_TICKS=(30, _I32, 1), LAUNCH_ORDER=(31, _I32, 1), WARN=(32, _I32, 1), WARN_EVER=(33, _I32, 1), SIZE_STATS=(34, _I32, 4),
     SITE_XPOS=(35, _F64, (3, 'nsite')), IK_ERR=(36, _F64, 2), IK_STEPS=(37, _I32, 2), QFRC_INVERSE=(38, _F64, 'nv'),
     CONTACT_FORCE=(39, _F64, 3*MAXCON), QFRC_APPLIED=(40, _F64, 'nv'), XFRC_APPLIED=(41, _F64, (6, 'nbody')), ENV_MODEL=(42, _I32, 1),
-    QFRC_LAW=(43, _F64, 'nv'), CONTROL_LAW=(44, _F64, (5, 'nv')))
+    QFRC_LAW=(43, _F64, 'nv'), CONTROL_LAW=(44, _F64, (5, 'nv')), TIME=(45, _F64, 1))
 TASK_IDS = dict(walk_imitation=0, flight_imitation=1, walk_on_ball=2, template_task=3)      # FB_TASK_* (csrc/fb_types.hpp)
 LAW_ROWS = ('bias', 'act_gain', 'pos_gain', 'pos_ref', 'vel_gain')                          # rows of CONTROL_LAW (csrc/fb_law.hpp)
 # bits of WARN / WARN_EVER (include/flybody_engine.h): the caps MuJoCo reports as nconmax / njmax warnings, and iteration limits

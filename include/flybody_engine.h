@@ -90,6 +90,9 @@ enum {
                             evaluation); zero after a reset (read-only; allocated by fb_batch_set_control_law) */
   FB_CONTROL_LAW = 44,   /* [n_rows][5][nv] physics real: the law's coefficient block, rows bias, act_gain, pos_gain, pos_ref, vel_gain
                             (fb_batch_device_ptr only: torch rewrites gains between steps without a host copy) */
+  FB_TIME = 45,          /* [n_env] FP64 at either precision: the episode clock (MuJoCo's d->time) -- 0 at a reset, + opt_timestep per substep.  It picks
+                            the reference frame of the reward and ends the episode at the time limit; setting it moves an episode in front of such a
+                            boundary (the step counter FB_STEP_COUNT is not moved with it) */
   FB_NFIELD
 };
 

@@ -22,7 +22,12 @@ whose libm differs there is no comparison of the observations within a tolerance
 
 The physics and the rewards call the host's libm (sin, cos, exp, acos, atan2), and the synthetic walking dataset comes out of the CPU
 oracle: the file is portable between hosts that agree on those.  `python tests/test_task_hooks.py LIB [OUT]` records it from a strict
-build of the PARENT's sources; the parent's build reproduces the committed file on the development host and on the GPU host."""
+build of the PARENT's sources; the parent's build reproduces the committed file on the development host and on the GPU host.
+
+Three of the 150 arrays are no longer the parent's: walk_ds_64_REWARD_FACTORS, walk_ds_32_REWARD and walk_ds_32_REWARD_FACTORS were re-recorded
+after d_walk_training_reward stopped scaling the egocentric site vectors by 1 / |root quaternion|^2 (tests/test_task_layer.py found it): the
+product with |q|^2, one rounding from 1 for the quaternion the integrator leaves, moves them by at most 1.3e-7 relative.  Every other array,
+the FP32 rows behind the double episode clock included, is the parent's to the bit."""
 import hashlib
 import os
 import sys
