@@ -88,6 +88,58 @@ LQRBackward = collections.namedtuple('LQRBackward', ['K', 'k', 'P', 'p', 'dV', '
 # terrain)
 RayResult = collections.namedtuple('RayResult', ['dist', 'geomid'])
 
+# The C prototypes of include/flybody_engine.h as (restype, argtypes), in the header's order; tests/test_abi.py checks every entry
+# against the header.  Handles, arrays, streams and structs passed by reference are c_void_p; an out-parameter filled through byref() is a
+# POINTER of its scalar.
+_P, _I, _D, _Z = C.c_void_p, C.c_int, C.c_double, C.c_size_t
+_SIGNATURES = {
+    'fb_model_dim': (_I, [_P, C.c_char_p]),
+    'fb_model_load': (_I, [_P, _Z, C.POINTER(_P)]),
+    'fb_model_destroy': (None, [_P]),
+    'fb_batch_create': (_I, [_P, _I, _I, _I, C.POINTER(_P)]),
+    'fb_batch_destroy': (None, [_P]),
+    'fb_batch_set_reference': (_I, [_P, _P, _P, _I, _I, _D, _D]),
+    'fb_batch_set_time_limit': (_I, [_P, _D]),
+    'fb_batch_set_wbpg': (_I, [_P, _P, _P, _P, _P, _I, _D, _D, _D, C.c_uint32]),
+    'fb_batch_set_walk_dataset': (_I, [_P, _P]),
+    'fb_batch_set_flight_dataset': (_I, [_P, _P]),
+    'fb_batch_reset': (_I, [_P, _P, _I, _P]),
+    'fb_batch_step': (_I, [_P, _P, _P]),
+    'fb_batch_substep': (_I, [_P, _I, _P]),
+    'fb_batch_forward': (_I, [_P, _P]),
+    'fb_batch_stage': (_I, [_P, _I, _P, _P]),
+    'fb_batch_row': (_I, [_P, _I, _I, _P, _Z, _I, C.POINTER(_Z)]),
+    'fb_batch_get': (_I, [_P, _I, _P, _Z]),
+    'fb_batch_set': (_I, [_P, _I, _P, _Z]),
+    'fb_batch_device_ptr': (_P, [_P, _I]),
+    'fb_batch_synchronize': (_I, [_P, _P]),
+    'fb_batch_timing_begin': (_I, [_P, _P]),
+    'fb_batch_timing_end': (_I, [_P, _P, C.POINTER(C.c_float), C.POINTER(_I)]),
+    'fb_batch_timing_launches': (_I, [_P, _P, _I]),
+    'fb_batch_scheduler': (_I, [_P, C.POINTER(_I)]),
+    'fb_batch_forget_stream': (_I, [_P, _P]),
+    'fb_random_actions': (_I, [_P, _P, _I, _I, C.c_uint64, _I, _I, _I, _P]),
+    'fb_batch_ik': (_I, [_P, _P, _P, _P]),
+    'fb_batch_inverse': (_I, [_P, _I, _P]),
+    'fb_batch_transition_fd': (_I, [_P]*8),
+    'fb_batch_fd_tickets': (_I, [_P, C.POINTER(C.c_int64)]),
+    'fb_batch_rollout': (_I, [_P]*8),
+    'fb_batch_rollouts_run': (_I, [_P, C.POINTER(C.c_int64)]),
+    'fb_batch_rollout_feedback': (_I, [_P]*8),
+    'fb_batch_lqr_backward': (_I, [_P]*17),
+    'fb_riccati_gemm': (_I, [_P] + [_I]*5 + [_P]*5),
+    'fb_batch_ray': (_I, [_P]*7),
+    'fb_batch_clear_forces': (_I, [_P]),
+    'fb_batch_forces_active': (_I, [_P]),
+    'fb_batch_set_control_law': (_I, [_P, _P]),
+    'fb_batch_control_law_active': (_I, [_P]),
+    'fb_batch_end_episode': (_I, [_P, _P, _P, _P]),
+    'fb_batch_create_group': (_I, [_P, _I, _I, _I, _I, C.POINTER(_P)]),
+    'fb_batch_n_models': (_I, [_P]),
+    'fb_last_error': (C.c_char_p, []),
+    'fb_version': (C.c_char_p, []),
+}
+
 _libs: Dict[str, C.CDLL] = {}
 
 
@@ -110,64 +162,12 @@ def load_library(lib_path: Optional[str] = None) -> C.CDLL:
         except ImportError:
             pass
     L = C.CDLL(path)
-    L.fb_last_error.restype = C.c_char_p
-    L.fb_version.restype = C.c_char_p
-    L.fb_model_load.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]
-    L.fb_model_destroy.argtypes = [C.c_void_p]; L.fb_model_destroy.restype = None
-    L.fb_model_dim.argtypes = [C.c_void_p, C.c_char_p]
-    L.fb_batch_create.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
-    L.fb_batch_destroy.argtypes = [C.c_void_p]; L.fb_batch_destroy.restype = None
-    L.fb_batch_set_reference.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double]
-    L.fb_batch_set_wbpg.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_double, C.c_uint32]
-    L.fb_batch_set_walk_dataset.argtypes = [C.c_void_p, C.c_void_p]
-    L.fb_batch_set_flight_dataset.argtypes = [C.c_void_p, C.c_void_p]
-    L.fb_batch_set_time_limit.argtypes = [C.c_void_p, C.c_double]
-    L.fb_batch_reset.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
-    L.fb_batch_step.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-    L.fb_batch_substep.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
-    L.fb_batch_forward.argtypes = [C.c_void_p, C.c_void_p]
-    L.fb_batch_stage.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-    if hasattr(L, 'fb_batch_row'):          # (profiling entry point, round 5; A/B builds of older sources lack it)
-        L.fb_batch_row.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.POINTER(C.c_size_t)]
-    L.fb_batch_get.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]
-    L.fb_batch_set.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]
-    L.fb_batch_device_ptr.argtypes = [C.c_void_p, C.c_int]; L.fb_batch_device_ptr.restype = C.c_void_p
-    L.fb_batch_synchronize.argtypes = [C.c_void_p, C.c_void_p]
-    L.fb_batch_scheduler.argtypes = [C.c_void_p, C.POINTER(C.c_int)]; L.fb_batch_scheduler.restype = C.c_int
-    if hasattr(L, 'fb_batch_forget_stream'):
-        L.fb_batch_forget_stream.argtypes = [C.c_void_p, C.c_void_p]
-    L.fb_batch_timing_begin.argtypes = [C.c_void_p, C.c_void_p]
-    L.fb_random_actions.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_void_p]
-    L.fb_batch_timing_end.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_int)]
-    if hasattr(L, 'fb_batch_timing_launches'):
-        L.fb_batch_timing_launches.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
-    if hasattr(L, 'fb_batch_ik'):           # (A/B builds of older sources lack it)
-        L.fb_batch_ik.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    if hasattr(L, 'fb_batch_inverse'):
-        L.fb_batch_inverse.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
-    if hasattr(L, 'fb_batch_clear_forces'):
-        L.fb_batch_clear_forces.argtypes = [C.c_void_p]
-        L.fb_batch_forces_active.argtypes = [C.c_void_p]
-    if hasattr(L, 'fb_batch_create_group'):
-        L.fb_batch_create_group.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
-        L.fb_batch_n_models.argtypes = [C.c_void_p]
-    if hasattr(L, 'fb_batch_set_control_law'):
-        L.fb_batch_set_control_law.argtypes = [C.c_void_p, C.c_void_p]
-        L.fb_batch_control_law_active.argtypes = [C.c_void_p]
-        L.fb_batch_end_episode.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    if hasattr(L, 'fb_batch_transition_fd'):
-        L.fb_batch_transition_fd.argtypes = [C.c_void_p] + [C.c_void_p]*7
-        L.fb_batch_fd_tickets.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
-    if hasattr(L, 'fb_batch_rollout'):
-        L.fb_batch_rollout.argtypes = [C.c_void_p] + [C.c_void_p]*7
-        L.fb_batch_rollouts_run.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
-    if hasattr(L, 'fb_batch_rollout_feedback'):
-        L.fb_batch_rollout_feedback.argtypes = [C.c_void_p] + [C.c_void_p]*7
-    if hasattr(L, 'fb_batch_lqr_backward'):
-        L.fb_batch_lqr_backward.argtypes = [C.c_void_p]*17
-        L.fb_riccati_gemm.argtypes = [C.c_void_p] + [C.c_int]*5 + [C.c_void_p]*5
-    if hasattr(L, 'fb_batch_ray'):
-        L.fb_batch_ray.argtypes = [C.c_void_p]*7
+    for name, (restype, argtypes) in _SIGNATURES.items():
+        f = getattr(L, name, None)
+        if f is None:
+            raise EngineError(f'{path} does not export {name}: rebuild it with `python -c "import __graft_entry__ as g; g.build()"` '
+                              '(hipcc --offload-arch=gfx950)')
+        f.restype, f.argtypes = restype, argtypes
     _libs[path] = L
     return L
 
@@ -290,6 +290,20 @@ def observation_layout(model: 'Model', future_steps: int, ball: bool = False):
     for k, shp in sizes.items():
         n = int(np.prod(shp)); layout[k] = (off, n, shp); off += n
     return layout, off
+
+
+class _WalkDataset(C.Structure):
+    """fb_walk_dataset (include/flybody_engine.h)."""
+    _fields_ = [('n_traj', C.c_int32), ('n_joints', C.c_int32), ('n_sites', C.c_int32), ('n_select', C.c_int32), ('traj_offset', _P), ('qpos', _P),
+                ('qvel', _P), ('root2site', _P), ('joint_quat', _P), ('joint_ids', _P), ('site_ids', _P), ('select', _P), ('future_steps', C.c_int32),
+                ('terminal_com_dist', _D), ('time_limit', _D), ('seed', C.c_uint32), ('env_id_base', C.c_int32)]
+
+
+class _FlightDataset(C.Structure):
+    """fb_flight_dataset (include/flybody_engine.h)."""
+    _fields_ = [('n_traj', C.c_int32), ('n_select', C.c_int32), ('traj_offset', _P), ('qpos', _P), ('qvel', _P), ('select', _P),
+                ('future_steps', C.c_int32), ('randomize_start_step', C.c_int32), ('terminal_com_dist', _D), ('time_limit', _D),
+                ('seed', C.c_uint32), ('env_id_base', C.c_int32)]
 
 
 class _IKConfig(C.Structure):
@@ -426,35 +440,25 @@ class Batch:
     def set_walk_dataset(self, ds, joint_ids, site_ids, select=None, future_steps=64, terminal_com_dist=0.3, time_limit=10.0,
                          seed: int = 0, env_id_base: int = 0):
         """Training-mode walk_imitation on a trajectory_loaders.WalkingDataset (fb_batch_set_walk_dataset)."""
-        class _DS(C.Structure):
-            _fields_ = [('n_traj', C.c_int32), ('n_joints', C.c_int32), ('n_sites', C.c_int32), ('n_select', C.c_int32),
-                        ('traj_offset', C.c_void_p), ('qpos', C.c_void_p), ('qvel', C.c_void_p), ('root2site', C.c_void_p),
-                        ('joint_quat', C.c_void_p), ('joint_ids', C.c_void_p), ('site_ids', C.c_void_p), ('select', C.c_void_p),
-                        ('future_steps', C.c_int32), ('terminal_com_dist', C.c_double), ('time_limit', C.c_double),
-                        ('seed', C.c_uint32), ('env_id_base', C.c_int32)]
         sel = np.arange(ds.n_traj, dtype=np.int32) if select is None else np.ascontiguousarray(select, np.int32)
         keep = [np.ascontiguousarray(ds.offsets, np.int32), np.ascontiguousarray(ds.qpos, np.float64), np.ascontiguousarray(ds.qvel, np.float64),
                 np.ascontiguousarray(ds.root2site, np.float64), np.ascontiguousarray(ds.joint_quat, np.float64),
                 np.ascontiguousarray(joint_ids, np.int32), np.ascontiguousarray(site_ids, np.int32), sel]
         assert keep[1].shape[1] == 7 + len(keep[5]) and keep[2].shape[1] == 6 + len(keep[5])
-        d = _DS(ds.n_traj, len(keep[5]), len(keep[6]), len(sel), *(a.ctypes.data for a in keep), int(future_steps), float(terminal_com_dist),
-                float(time_limit), int(seed), int(env_id_base))
+        d = _WalkDataset(ds.n_traj, len(keep[5]), len(keep[6]), len(sel), *(a.ctypes.data for a in keep), int(future_steps), float(terminal_com_dist),
+                         float(time_limit), int(seed), int(env_id_base))
         _check(self.L, self.L.fb_batch_set_walk_dataset(self.h, C.byref(d)))
         self.nobs = observation_layout(self.model, future_steps)[1]
 
     def set_flight_dataset(self, offsets, root_qpos, qvel, select=None, future_steps=5, terminal_com_dist=2.0, time_limit=0.6,
                            randomize_start_step=True, seed: int = 0, env_id_base: int = 0):
         """flight_imitation on a reference dataset (fb_batch_set_flight_dataset); root_qpos = FlightDataset.root_qpos(com_offset)."""
-        class _FD(C.Structure):
-            _fields_ = [('n_traj', C.c_int32), ('n_select', C.c_int32), ('traj_offset', C.c_void_p), ('qpos', C.c_void_p),
-                        ('qvel', C.c_void_p), ('select', C.c_void_p), ('future_steps', C.c_int32), ('randomize_start_step', C.c_int32),
-                        ('terminal_com_dist', C.c_double), ('time_limit', C.c_double), ('seed', C.c_uint32), ('env_id_base', C.c_int32)]
         n_traj = len(offsets) - 1
         sel = np.arange(n_traj, dtype=np.int32) if select is None else np.ascontiguousarray(select, np.int32)
         keep = [np.ascontiguousarray(offsets, np.int32), np.ascontiguousarray(root_qpos, np.float64), np.ascontiguousarray(qvel, np.float64), sel]
         assert keep[1].shape == (keep[0][-1], 7) and keep[2].shape == (keep[0][-1], 6)
-        d = _FD(n_traj, len(sel), keep[0].ctypes.data, keep[1].ctypes.data, keep[2].ctypes.data, sel.ctypes.data, int(future_steps),
-                int(bool(randomize_start_step)), float(terminal_com_dist), float(time_limit), int(seed), int(env_id_base))
+        d = _FlightDataset(n_traj, len(sel), keep[0].ctypes.data, keep[1].ctypes.data, keep[2].ctypes.data, sel.ctypes.data, int(future_steps),
+                           int(bool(randomize_start_step)), float(terminal_com_dist), float(time_limit), int(seed), int(env_id_base))
         _check(self.L, self.L.fb_batch_set_flight_dataset(self.h, C.byref(d)))
         self.nobs = observation_layout(self.model, future_steps)[1]
 
@@ -842,6 +846,18 @@ class Batch:
         if not p:
             raise EngineError(f'no device pointer for {name}')
         return p
+
+    def device_view(self, name: str):
+        """A zero-copy torch tensor [n_env, width] over a field that device_ptr serves, on the batch's device (a GPU-backed library): the
+        table's element type, FP64 physics fields at the batch's precision.  QPOS and QVEL are windows of the arena (row stride
+        row_bytes(0)); CONTROL_LAW is [control_law_rows, 5 nv].  The view dangles once its array is freed (clear_forces, clear_control_law)."""
+        import torch
+        _, dt, w = self._field(name)
+        dt = np.dtype(np.float32 if dt is _F64 and self.precision == 32 else dt)
+        lead = self.control_law_rows if name == 'CONTROL_LAW' else self.n_env
+        row = self.row_bytes(0) if name in ('QPOS', 'QVEL') else w*dt.itemsize
+        iface = {'shape': (lead, w), 'strides': (row, dt.itemsize), 'typestr': dt.str, 'data': (self.device_ptr(name), False), 'version': 2}
+        return torch.as_tensor(type('DevBuf', (), {'__cuda_array_interface__': iface})(), device=f'cuda:{self.device}')
 
     @property
     def substep_scheduler(self) -> bool:

@@ -248,21 +248,9 @@ class BatchedFlyEnv:
     # ---- torch interface (zero-copy views of the engine's device buffers) -----------------------
     def torch_views(self):
         if self._torch_views is None:
-            import torch
-
-            def view(name, shape, dtype):
-                nbytes = int(np.prod(shape)) * torch.tensor([], dtype=dtype).element_size()
-                ptr = self.batch.device_ptr(name)
-                iface = {'shape': tuple(shape), 'typestr': {torch.float32: '<f4', torch.int32: '<i4'}[dtype],
-                         'data': (ptr, False), 'version': 2}
-                holder = type('DevBuf', (), {'__cuda_array_interface__': iface})()
-                t = torch.as_tensor(holder, device=f'cuda:{self.device}')
-                assert t.numel() * t.element_size() == nbytes
-                return t
-            self._torch_views = dict(obs=view('OBS', (self.n_env, self.nobs), torch.float32),
-                                     reward=view('REWARD', (self.n_env,), torch.float32),
-                                     discount=view('DISCOUNT', (self.n_env,), torch.float32),
-                                     step_type=view('STEP_TYPE', (self.n_env,), torch.int32))
+            view = self.batch.device_view
+            self._torch_views = dict(obs=view('OBS'), reward=view('REWARD').view(self.n_env), discount=view('DISCOUNT').view(self.n_env),
+                                     step_type=view('STEP_TYPE').view(self.n_env))
         return self._torch_views
 
     def state_views(self):
@@ -270,17 +258,7 @@ class BatchedFlyEnv:
         terminations computed on the device (reward_fn / termination_fn).  They are strided windows of the engine's arena: read them
         after a step; writing between steps is Batch.set without its checks."""
         if self._state_views is None:
-            import torch
-            f64 = self.batch.precision == 64
-            es = 8 if f64 else 4
-            row = self.batch.row_bytes(0)
-
-            def view(name, width):
-                iface = {'shape': (self.n_env, width), 'strides': (row, es), 'typestr': '<f8' if f64 else '<f4',
-                         'data': (self.batch.device_ptr(name), False), 'version': 2}
-                holder = type('DevBuf', (), {'__cuda_array_interface__': iface})()
-                return torch.as_tensor(holder, device=f'cuda:{self.device}')
-            self._state_views = dict(qpos=view('QPOS', self.model.dim('nq')), qvel=view('QVEL', self.model.dim('nv')))
+            self._state_views = dict(qpos=self.batch.device_view('QPOS'), qvel=self.batch.device_view('QVEL'))
         return self._state_views
 
     def applied_forces(self):
@@ -293,17 +271,8 @@ class BatchedFlyEnv:
         if not self.batch.forces_active:                  # freed behind our back (Batch.clear_forces): earlier views point at freed memory
             self._force_views = None
         if self._force_views is None:
-            import torch
-            dt = torch.float64 if self.batch.precision == 64 else torch.float32
-            nv, nbody = self.model.dim('nv'), self.model.dim('nbody')
-
-            def view(name, shape):
-                iface = {'shape': tuple(shape), 'typestr': {torch.float64: '<f8', torch.float32: '<f4'}[dt],
-                         'data': (self.batch.device_ptr(name), False), 'version': 2}
-                holder = type('DevBuf', (), {'__cuda_array_interface__': iface})()
-                return torch.as_tensor(holder, device=f'cuda:{self.device}')
-            self._force_views = dict(qfrc_applied=view('QFRC_APPLIED', (self.n_env, nv)),
-                                     xfrc_applied=view('XFRC_APPLIED', (self.n_env, nbody, 6)))
+            self._force_views = dict(qfrc_applied=self.batch.device_view('QFRC_APPLIED'),
+                                     xfrc_applied=self.batch.device_view('XFRC_APPLIED').view(self.n_env, self.model.dim('nbody'), 6))
         return self._force_views
 
     def env_model(self):
@@ -311,10 +280,7 @@ class BatchedFlyEnv:
         The engine reads it when it picks an environment up; change an entry at an episode boundary only -- before a reset of that
         environment, or while its step type is LAST (resample_on_reset does the latter)."""
         if self._model_view is None:
-            import torch
-            iface = {'shape': (self.n_env,), 'typestr': '<i4', 'data': (self.batch.device_ptr('ENV_MODEL'), False), 'version': 2}
-            holder = type('DevBuf', (), {'__cuda_array_interface__': iface})()
-            self._model_view = torch.as_tensor(holder, device=f'cuda:{self.device}')
+            self._model_view = self.batch.device_view('ENV_MODEL').view(self.n_env)
         return self._model_view
 
     def _resample_models(self):
@@ -345,17 +311,8 @@ class BatchedFlyEnv:
         if not self.batch.control_law_active:
             raise engine.EngineError('no control law is set (set_control_law)')
         if self._law_views is None:
-            import torch
-            dt = torch.float64 if self.batch.precision == 64 else torch.float32
-            nv = self.model.dim('nv')
-
-            def view(name, shape):
-                iface = {'shape': tuple(shape), 'typestr': '<f8' if dt == torch.float64 else '<f4', 'data': (self.batch.device_ptr(name), False), 'version': 2}
-                holder = type('DevBuf', (), {'__cuda_array_interface__': iface})()
-                return torch.as_tensor(holder, device=f'cuda:{self.device}')
-            n_rows = self.batch.control_law_rows
-            block = view('CONTROL_LAW', (n_rows, len(engine.LAW_ROWS), nv))
-            self._law_views = dict({k: block[:, r] for r, k in enumerate(engine.LAW_ROWS)}, qfrc_law=view('QFRC_LAW', (self.n_env, nv)))
+            block = self.batch.device_view('CONTROL_LAW').view(self.batch.control_law_rows, len(engine.LAW_ROWS), self.model.dim('nv'))
+            self._law_views = dict({k: block[:, r] for r, k in enumerate(engine.LAW_ROWS)}, qfrc_law=self.batch.device_view('QFRC_LAW'))
         return self._law_views
 
     def clear_control_law(self):

@@ -120,6 +120,16 @@ def test_no_cpu_fallback(walk_arrays):
                 assert 'from oracle' not in src and 'import oracle' not in src and 'libflybody_emu' not in src, f
 
 
+def test_a_library_without_a_declared_symbol_is_refused_at_load(monkeypatch):
+    """load_library applies engine._SIGNATURES to the whole library: a symbol the table declares and the binary lacks is an EngineError that
+    names the symbol and the build command, not a call without argtypes later."""
+    from flybody_amd import engine
+    monkeypatch.setattr(engine, '_libs', {})
+    monkeypatch.setitem(engine._SIGNATURES, 'fb_no_such_call', (C.c_int, [C.c_void_p]))
+    with pytest.raises(engine.EngineError, match=r'does not export fb_no_such_call.*g\.build\(\)'):
+        engine.load_library()
+
+
 def test_python_field_table_matches_header():
     """engine.FIELDS names every field of the header's field enum (FB_QPOS ... ) with the header's id, and no other."""
     from flybody_amd import engine
@@ -131,28 +141,76 @@ def test_python_field_table_matches_header():
     assert {name: f[0] for name, f in engine.FIELDS.items()} == ids
 
 
-def _learner_header():
-    hdr = open(os.path.join(ROOT, 'include', 'flybody_learner.h')).read()
-    return re.sub(r'/\*.*?\*/', '', hdr, flags=re.S)
+def test_python_warn_bits_match_header():
+    """engine.WARN_BITS names every bit of the header's FB_WARN_* enum with the header's value, and no other."""
+    from flybody_amd import engine
+    hdr = open(os.path.join(ROOT, 'include', 'flybody_engine.h')).read()
+    hdr = re.sub(r'/\*.*?\*/', '', hdr, flags=re.S)
+    block = next(b for b in re.findall(r'enum\s*\{(.*?)\}', hdr, flags=re.S) if 'FB_WARN_CONTACT_CAP' in b)
+    bits = {name: int(v) for name, v in re.findall(r'\bFB_WARN_([A-Z0-9_]+)\s*=\s*(\d+)', block)}
+    assert len(bits) >= 7 and bits['CONTACT_CAP'] == 1 and bits['MODEL_ID'] == 64
+    assert engine.WARN_BITS == bits
 
 
-_SCALARS = {'int': C.c_int, 'int32_t': C.c_int, 'int64_t': C.c_int64, 'float': C.c_float, 'size_t': C.c_size_t}
+_SCALARS = {'int': C.c_int, 'int32_t': C.c_int32, 'int64_t': C.c_int64, 'uint8_t': C.c_uint8, 'uint32_t': C.c_uint32, 'uint64_t': C.c_uint64,
+            'float': C.c_float, 'double': C.c_double, 'size_t': C.c_size_t}
+_STRUCT = r'typedef\s+struct\s*\w*\s*\{(.*?)\}\s*(\w+)\s*;'
 
 
-def _ctype_of(decl, base=None):
-    """ctypes kind of one C parameter / field declarator / return type: any pointer is c_void_p, a scalar the kind of its type name (`base`
-    for the later declarators of 'const float *a, *b')."""
-    return C.c_void_p if '*' in decl else _SCALARS[base or [t for t in re.findall(r'\w+', decl) if t != 'const'][0]]
+def _base(decl):
+    """The type name a declaration starts with: 'const float *a' -> 'float'."""
+    return [t for t in re.findall(r'\w+', decl) if t != 'const'][0]
 
 
-def _struct_fields(hdr, name):
-    """[(field, ctypes kind)] of `typedef struct name { ... } name;`, in order."""
-    body = re.search(r'typedef\s+struct\s+%s\s*\{(.*?)\}\s*%s\s*;' % (name, name), hdr, flags=re.S).group(1)
+def _kinds(decl, base=None):
+    """The ctypes kinds that may declare one C parameter or return type (`base`: its type name, for the later declarators of 'const float
+    *a, *b').  A scalar is the kind of its type name and void is None.  Any pointer is c_void_p, or the typed pointer that byref() of its
+    pointee needs: POINTER(scalar) for a scalar's, POINTER(c_void_p) for a pointer's; `char*` is c_char_p."""
+    base, stars = base or _base(decl), decl.count('*')
+    if not stars:
+        return (None,) if base == 'void' else (_SCALARS[base],)
+    if base == 'char':
+        return (C.c_char_p,)
+    typed = (C.POINTER(C.c_void_p),) if stars > 1 else (C.POINTER(_SCALARS[base]),) if base in _SCALARS else ()
+    return (C.c_void_p,) + typed
+
+
+def _struct_fields(body):
+    """[(field, ctypes kind)] of a struct's body, in order: a pointer is c_void_p, `double size[4]` is c_double*4."""
     out = []
     for decl in filter(None, (d.strip() for d in body.split(';'))):
-        base = [t for t in re.findall(r'\w+', decl) if t != 'const'][0]
-        out += [(re.search(r'(\w+)\s*$', piece).group(1), _ctype_of(piece, base)) for piece in decl.split(',')]
+        for piece in decl.split(','):
+            name, count = re.search(r'(\w+)\s*(?:\[(\d+)\])?\s*$', piece).groups()
+            kind = C.c_void_p if '*' in piece else _SCALARS[_base(decl)]
+            out.append((name, kind*int(count) if count else kind))
     return out
+
+
+def _name(t):
+    return getattr(t, '__name__', t)
+
+
+def _check_declarations(header, prefix, signatures, mirrors):
+    """A ctypes signature table {name: (restype, argtypes)} and the Structure mirrors {struct: mirror} of one library against the prototypes
+    and structs of its header: an entry for every function and no others, as many argument types as parameters, each of the parameter's
+    kind, the return type; a mirror for every struct, field by field.  Returns the names of the prototypes."""
+    hdr = re.sub(r'/\*.*?\*/', '', open(os.path.join(ROOT, 'include', header)).read(), flags=re.S)
+    hdr = re.sub(r'^\s*#.*$', '', hdr, flags=re.M)                            # (preprocessor lines: an #endif in front of a prototype)
+    structs = {name: body for body, name in re.findall(_STRUCT, hdr, flags=re.S)}
+    protos = re.findall(r'([\w\s\*]+?)\b(%s\w+)\s*\(([^()]*)\)\s*;' % prefix, re.sub(_STRUCT, '', hdr, flags=re.S))
+    for ret, name, params in protos:
+        assert name in signatures, f'{name}: declared in {header}, no ctypes declaration'
+        restype, argtypes = signatures[name]
+        params = [] if params.strip() == 'void' else params.split(',')
+        assert len(argtypes) == len(params), f'{name}: {len(argtypes)} argument types for {len(params)} parameters'
+        for i, (t, prm) in enumerate(zip(argtypes, params)):
+            assert any(t is k for k in _kinds(prm)), f'{name}: parameter {i} ({prm.strip()}) declared as {_name(t)}'
+        assert restype is _kinds(ret)[0], f'{name}: return type {ret.strip()} declared as {_name(restype)}'
+    assert set(signatures) == {name for _, name, _ in protos}
+    assert set(mirrors) == set(structs), set(mirrors) ^ set(structs)
+    for struct, mirror in mirrors.items():
+        assert [(n, t) for n, t in mirror._fields_] == _struct_fields(structs[struct]), struct
+    return {name for _, name, _ in protos}
 
 
 def test_learner_ctypes_declarations_match_header():
@@ -160,19 +218,23 @@ def test_learner_ctypes_declarations_match_header():
     fused.py), as many argument types as parameters, each of the parameter's kind, the return type; and the two Structure mirrors field by
     field.  A miscounted pointer would otherwise stay silent until it corrupts memory on a GPU."""
     from flybody_amd.dmpo import fused
-    hdr = _learner_header()
-    protos = re.findall(r'([\w\s\*]+?)\b(fbl_\w+)\s*\(([^()]*)\)\s*;', re.sub(r'typedef\s+struct.*?\}\s*\w+\s*;', '', hdr, flags=re.S))
-    assert len(protos) >= 24 and {'fbl_sgemm_op', 'fbl_mpo_loss', 'fbl_nstep_add'} <= {name for _, name, _ in protos}
-    for ret, name, params in protos:
-        assert name in fused._SIGNATURES, f'{name}: declared in flybody_learner.h, no ctypes declaration'
-        restype, argtypes = fused._SIGNATURES[name]
-        params = [] if params.strip() == 'void' else params.split(',')
-        assert len(argtypes) == len(params), f'{name}: {len(argtypes)} argument types for {len(params)} parameters'
-        for i, (t, prm) in enumerate(zip(argtypes, params)):
-            assert t is _ctype_of(prm), f'{name}: parameter {i} ({prm.strip()}) declared as {t.__name__}'
-        assert restype is (C.c_char_p if '*' in ret else _ctype_of(ret)), f'{name}: return type {ret.strip()} declared as {restype.__name__}'
-    assert set(fused._SIGNATURES) == {name for _, name, _ in protos}
+    protos = _check_declarations('flybody_learner.h', 'fbl_', fused._SIGNATURES, {'fbl_gemm_op': fused._GemmOp, 'fbl_mpo_args': fused._MpoArgs})
+    assert len(protos) >= 24 and {'fbl_sgemm_op', 'fbl_mpo_loss', 'fbl_nstep_add'} <= protos
     called = set(re.findall(r'lib\(\)\.(fbl_\w+)', open(os.path.join(ROOT, 'flybody_amd', 'dmpo', 'fused.py')).read()))
     assert len(called) >= 20 and called <= set(fused._SIGNATURES), called - set(fused._SIGNATURES)
-    for struct, mirror in (('fbl_gemm_op', fused._GemmOp), ('fbl_mpo_args', fused._MpoArgs)):
-        assert [(n, t) for n, t in mirror._fields_] == _struct_fields(hdr, struct), struct
+
+
+def test_engine_ctypes_declarations_match_header():
+    """engine._SIGNATURES against the prototypes of include/flybody_engine.h, as the learner's above: an entry for every function (and for
+    every .fb_*( call of engine.py), the argument count, each parameter's kind, the return type; and the ten Structure mirrors field by
+    field.  The engine's calls take device pointers from torch: ctypes would pass one as a C int where a declaration is missing."""
+    from flybody_amd import engine
+    mirrors = dict(fb_walk_dataset=engine._WalkDataset, fb_flight_dataset=engine._FlightDataset, fb_ik_config=engine._IKConfig,
+                   fb_fd_config=engine._FDConfig, fb_rollout_config=engine._RolloutConfig, fb_feedback=engine._Feedback,
+                   fb_lqr_config=engine._LQRConfig, fb_terrain=engine._Terrain, fb_ray_config=engine._RayConfig,
+                   fb_control_law=engine._ControlLaw)
+    protos = _check_declarations('flybody_engine.h', 'fb_', engine._SIGNATURES, mirrors)
+    assert len(protos) >= 45 and {'fb_batch_lqr_backward', 'fb_batch_ray', 'fb_random_actions'} <= protos
+    assert len(mirrors) == 10
+    called = set(re.findall(r'\.(fb_\w+)\(', open(os.path.join(ROOT, 'flybody_amd', 'engine.py')).read()))
+    assert len(called) >= 40 and called <= set(engine._SIGNATURES), called - set(engine._SIGNATURES)

@@ -209,8 +209,7 @@ def test_reassignment_while_last_takes_effect_at_the_first_observation():
         assert k < 20
     assert k >= 3
     old = B.get('ENV_MODEL').ravel().copy()
-    iface = {'shape': (n,), 'typestr': '<i4', 'data': (B.device_ptr('ENV_MODEL'), False), 'version': 2}
-    view = torch.as_tensor(type('DevBuf', (), {'__cuda_array_interface__': iface})(), device='cuda:0')
+    view = B.device_view('ENV_MODEL').view(n)
     view.copy_(1 - view); torch.cuda.synchronize()
     new = B.get('ENV_MODEL').ravel()
     assert (new == 1 - old).all()
